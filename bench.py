@@ -20,7 +20,20 @@ k = 100, with m = 500000 by default (configs[4] is 4M rows on 8 GPUs; pass
 --m 4000000 for the full size).  Both run the fp32 path (include/knn.h).
 
   python bench.py [--gpus N --steps K --warmup W] [--workload mnist|mnist-real|sift|gist]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: set-up, the
+warm-up steps, the K timed steps, the result line.  --dump-outputs DIR also
+writes what the last timed step computed (every query's neighbour indices
+and distances, DIR/idx.npy and DIR/distance.npy, float64; above
+DUMP_BUDGET_BYTES a fixed seeded sample of the rows, listed in DIR/rows.npy;
+at N > 1 each rank writes its own rows as <name>_rank<r>.npy).  The corpus
+is seeded, so two builds run with the same arguments can be compared array
+for array.  --full adds every other leg: the profiled steps behind
+`roofline`, the oracle spot check (`check`), the per-row hashes
+(`check_all_rows`), mnist's real-valued `secondary` run and the
+`cpu_baseline`; without it those fields of the line are null.
 
 N > 1: one process per GPU, RCCL (torch.distributed "nccl") ring of corpus
 blocks, strong scaling (total work fixed).  Rank 0 prints one JSON line.
@@ -45,6 +58,9 @@ FP32_MFMA_PEAK_TFLOPS = 157.3  # dense fp32 matrix (spec, MI355X_MICROARCH.md; 1
 FP16_MFMA_PEAK_TFLOPS = 2500.0  # dense fp16 matrix (spec ~2.5 PF, MI355X_MICROARCH.md)
 I8_MFMA_PEAK_TOPS = 5000.0      # dense int8 matrix: 2x the fp16 rate per clock (MI355X_MICROARCH.md)
 HBM_PEAK_GBS = 8000.0           # HBM3E, ~8 TB/s (MI355X_MICROARCH.md)
+
+DUMP_BUDGET_BYTES = 48 << 20    # --dump-outputs: all files of a run together stay below 64 MB
+DUMP_SEED = 0xD0A7              # the row sample of a larger result
 
 METRIC = "all-kNN queries/sec (MNIST-784, k=30) at 1/2/4/8 GPUs + % MFMA peak"   # BASELINE.json
 
@@ -149,13 +165,20 @@ def main():
     ap.add_argument("--m", type=int, default=None)
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--k", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: roofline (profiled steps), oracle checks, "
+                         "mnist's real-valued secondary run, the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--check", type=int, default=8, help="queries re-checked against the oracle")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baseline out")
+    ap.add_argument("--check", type=int, default=8, help="--full: queries re-checked against the oracle")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
     ap.add_argument("--secondary-steps", type=int, default=3,
-                    help="mnist: also time the real-valued GEMM path this many steps (0: off)")
+                    help="--full, mnist: also time the real-valued GEMM path this many steps (0: off)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus is not None and args.gpus > 1:
@@ -202,12 +225,12 @@ def main():
     args.backend = backend if dist is not None else None
 
     res = run_workload(args.workload, args.steps, args.warmup, args, torch, dist, rank, P, local,
-                       args.check, args.m, args.n, args.k)
+                       args.check, args.m, args.n, args.k, dump_dir=args.dump_outputs)
     # configs[1]'s real-valued form (mnist_train_svd.mat): the
     # GEMM-mode contraction (split-fp16 filter + exact fp64 re-rank), timed by
     # the same clock a few steps, reported beside the int8 headline
     secondary = None
-    if args.workload == "mnist" and args.secondary_steps > 0:
+    if args.full and args.workload == "mnist" and args.secondary_steps > 0:
         secondary = run_workload("mnist-real", args.secondary_steps, 1, args, torch, dist, rank, P, local,
                                  min(args.check, 4), None, None, None)
     if rank != 0:
@@ -223,17 +246,40 @@ def main():
                             "ms_per_step": sl["ms_per_step"], "steps": sl["steps"], "warmup": sl["warmup"],
                             "engine": sl["engine"], "check": sl["check"],
                             "check_all_rows": sl["check_all_rows"], "roofline": sl["roofline"]}
-    if P == 1 and not args.no_cpu_baseline:
+    if args.full and P == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(res["X"].astype(np.float64, copy=False), res["k"], args.cpu_seconds)
     print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
 
 
-def run_workload(workload, steps, warmup, args, torch, dist, rank, P, local, ncheck, m_arg, n_arg, k_arg):
+def dump_outputs(dump_dir, nb, rank, P):
+    """--dump-outputs: this rank's result of the last timed step (the (rows, k)
+    neighbour records a caller of the search receives) as float64 arrays,
+    idx.npy (1-based corpus rows) and distance.npy; <name>_rank<r>.npy when
+    P > 1.  A result above this rank's share of DUMP_BUDGET_BYTES is cut to a
+    fixed seeded sample of its rows, their numbers in rows.npy."""
+    os.makedirs(dump_dir, exist_ok=True)
+    sfx = "_rank%d" % rank if P > 1 else ""
+    nq, k = nb.shape
+    fit = (DUMP_BUDGET_BYTES // P) // (2 * 8 * max(k, 1))
+    arrays = {}
+    if nq > fit:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(nq, size=fit, replace=False))
+        nb = nb[pick]
+        arrays["rows"] = pick.astype(np.float64)
+    arrays["idx"] = nb["idx"].astype(np.float64)
+    arrays["distance"] = nb["distance"].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, "%s%s.npy" % (name, sfx)), np.ascontiguousarray(a))
+
+
+def run_workload(workload, steps, warmup, args, torch, dist, rank, P, local, ncheck, m_arg, n_arg, k_arg,
+                 dump_dir=None):
     """Time `steps` all-kNN passes of one workload on this rank (after
     `warmup` untimed ones), barrier + synchronize on both sides, the max
-    over ranks; returns the JSON line (rank 0) and the corpus."""
+    over ranks; returns the JSON line (rank 0) and the corpus.  Everything
+    after the timed steps and the dump runs under --full only."""
     import mpiknn
     import mpiknn.ring as ring
     from mpiknn import synth
@@ -309,6 +355,45 @@ def run_workload(workload, steps, warmup, args, torch, dist, rank, P, local, nch
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dump_dir:
+        dump_outputs(dump_dir, engine.result(), rank, P)
+    mode, splits = engine.ctx.info()
+    ms_per_step = elapsed / steps * 1e3
+    line = {
+        "metric": METRIC if workload == "mnist" else
+                  "all-kNN queries/sec (%s, k=%d) at %d GPUs + %% MFMA peak" % (
+                      wdesc.split(" k=")[0].replace("all-kNN ", ""), k, P),
+        "value": m / (ms_per_step * 1e-3),
+        "unit": "queries/s",
+        "n_gpus": P,
+        "steps": steps,
+        "warmup": warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        # BASELINE.md publishes no number for this metric ("published": {}),
+        # so there is nothing to divide by (DESIGN.md sec.6)
+        "vs_baseline": None,
+        "dtype": dtype,
+        "data": data,
+        "config": {"workload": wdesc % (k, m, n), "m": m, "n": n, "k": k,
+                   "parallelism": "ring%d" % P},
+        # the ranks' process group: RCCL ("nccl") across P GPUs, one process
+        # each; null at P = 1 (no collective)
+        "rccl_world": P if args.backend == "nccl" else None,
+        "launcher": os.environ.get("KNN_BENCH_LAUNCHER") or ("torch.distributed.run" if P > 1 else None),
+        "engine": {"mode": ("cpu stand-in (test only)" if standin else mpiknn.MODE_NAMES.get(mode, str(mode))),
+                   "splits": splits,
+                   "unresolved_queries": unresolved},
+        # the legs of --full (below); null in a plain run
+        "check": None,
+        "check_all_rows": None,
+        "roofline": None,
+        "cpu_baseline": None,
+    }
+    if not args.full:
+        return {"line": line if rank == 0 else None, "X": X, "k": k}
+
     # the roofline's kernel time: the same step again with the HIP timing
     # events on (knn_ctx_profile), outside the timed region -- each event
     # record sits on the launch queues, so they stay out of ms_per_step
@@ -344,7 +429,6 @@ def run_workload(workload, steps, warmup, args, torch, dist, rank, P, local, nch
         es_blk = 8 if dtype == "f64" else 4
         pack_bytes = rows * n * es_src + rows * (n + 1) * es_blk
         pack_form = "element block (k_pack_col / k_pack_row)"
-    mode, splits = engine.ctx.info()
     cbits = engine.ctx.contraction_bits()
 
     # parity spot-check of this rank's first queries against the oracle
@@ -382,7 +466,6 @@ def run_workload(workload, steps, warmup, args, torch, dist, rank, P, local, nch
     if rank != 0:
         return {"line": None, "X": X, "k": k}
 
-    ms_per_step = elapsed / steps * 1e3
     # dominant kernel k_dist_topk: algorithmic FLOP = 2 * queries * corpus * n
     # per rank per step, over its measured event time
     flops_rank = 2.0 * rows * m * n * prof_steps
@@ -481,37 +564,7 @@ def run_workload(workload, steps, warmup, args, torch, dist, rank, P, local, nch
             "frac": (pack_bytes / (pack_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if pack_ms > 0 else None,
         },
     }
-    line = {
-        "metric": METRIC if workload == "mnist" else
-                  "all-kNN queries/sec (%s, k=%d) at %d GPUs + %% MFMA peak" % (
-                      wdesc.split(" k=")[0].replace("all-kNN ", ""), k, P),
-        "value": m / (ms_per_step * 1e-3),
-        "unit": "queries/s",
-        "n_gpus": P,
-        "steps": steps,
-        "warmup": warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong",
-        # BASELINE.md publishes no number for this metric ("published": {}),
-        # so there is nothing to divide by (DESIGN.md sec.6)
-        "vs_baseline": None,
-        "dtype": dtype,
-        "data": data,
-        "config": {"workload": wdesc % (k, m, n), "m": m, "n": n, "k": k,
-                   "parallelism": "ring%d" % P},
-        # the ranks' process group: RCCL ("nccl") across P GPUs, one process
-        # each; null at P = 1 (no collective)
-        "rccl_world": P if args.backend == "nccl" else None,
-        "launcher": os.environ.get("KNN_BENCH_LAUNCHER") or ("torch.distributed.run" if P > 1 else None),
-        "engine": {"mode": ("cpu stand-in (test only)" if standin else mpiknn.MODE_NAMES.get(mode, str(mode))),
-                   "splits": splits,
-                   "unresolved_queries": unresolved},
-        "check": check,
-        "check_all_rows": all_rows,
-        "roofline": roofline,
-        "cpu_baseline": None,
-    }
+    line.update(check=check, check_all_rows=all_rows, roofline=roofline)
     return {"line": line, "X": X, "k": k}
 
 

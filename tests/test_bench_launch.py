@@ -17,7 +17,7 @@ import pytest
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 BENCH = os.path.join(ROOT, "bench.py")
-SMALL = ["--m", "240", "--n", "784", "--steps", "2", "--warmup", "1", "--secondary-steps", "0",
+SMALL = ["--m", "240", "--n", "784", "--steps", "2", "--warmup", "1", "--full", "--secondary-steps", "0",
          "--check", "8"]
 
 
@@ -48,6 +48,59 @@ def test_bench_gpus_n_runs_n_ranks(gpus, schedule):
     assert line["check"]["mismatches"] == 0   # rank 0's rows against the oracle
     assert np.isclose(line["value"], 240 / (line["ms_per_step"] * 1e-3))
     assert line["cpu_baseline"] is None       # P > 1: no CPU leg
+
+
+def test_bench_plain_run_dumps_last_step(tmp_path):
+    """a plain run (no --full) times --steps steps, leaves the legs beside the
+    headline out of the line, and --dump-outputs writes the last step's
+    neighbour records as float64 arrays: the oracle's on the seeded corpus"""
+    sys.path.insert(0, os.path.join(ROOT, "mpi-knn_amd"))
+    import oracle
+    from mpiknn import synth
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--m", "240", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=300,
+                       env=_env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = _lines(r.stdout)
+    assert len(lines) == 1, r.stdout
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "queries/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert np.isclose(line["value"], 240 / (line["ms_per_step"] * 1e-3))
+    for leg in ("check", "check_all_rows", "roofline", "cpu_baseline"):
+        assert line[leg] is None, leg
+    assert "secondary" not in line
+    assert sorted(p.name for p in out.iterdir()) == ["distance.npy", "idx.npy"]
+    idx, dist = np.load(out / "idx.npy"), np.load(out / "distance.npy")
+    assert idx.dtype == np.float64 and dist.dtype == np.float64
+    ref = oracle.knn(synth.mnist_like(240, 784)[0], 30)
+    assert np.array_equal(idx, ref["idx"].astype(np.float64))
+    assert np.array_equal(dist.view(np.uint64), ref["distance"].view(np.uint64))
+
+
+def test_bench_dump_samples_large_results():
+    """above its byte budget the dump is a fixed seeded sample of the rows"""
+    import importlib.util
+    import tempfile
+    spec = importlib.util.spec_from_file_location("knn_bench", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    import oracle
+    k = 64
+    nq = bench.DUMP_BUDGET_BYTES // (16 * k) + 1000
+    nb = np.zeros((nq, k), dtype=oracle.NB_DTYPE)
+    nb["idx"] = np.arange(nq, dtype=np.int32)[:, None]
+    picks = []
+    for _ in range(2):
+        with tempfile.TemporaryDirectory() as d:
+            bench.dump_outputs(d, nb, 0, 1)
+            files = {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+        assert sorted(files) == ["distance.npy", "idx.npy", "rows.npy"]
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert np.array_equal(files["idx.npy"][:, 0], files["rows.npy"])
+        picks.append(files["rows.npy"])
+    assert np.array_equal(picks[0], picks[1]) and np.all(np.diff(picks[0]) > 0)
 
 
 def test_bench_world_size_must_match_gpus():

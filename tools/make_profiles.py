@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Turn a `tools/gpu.sh bench:WL trace:WL pmc:WL:REP` session (files under
-gpurun_out/) into the committed evidence under profiles/: the rocprofv3
+$KNN_GPU_OUT, default gpu_out/; its bench and trace steps run `bench.py
+--full`) into the committed evidence under profiles/: the rocprofv3
 kernel stats, the PMC traffic of the dominant kernel that bench.py reports
 as roofline.traffic (median of the REP passes, merged into
 profiles/pmc_traffic.json under bench.py's key) and a short summary.
@@ -23,7 +24,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r02"
 WL = sys.argv[2] if len(sys.argv) > 2 else "mnist"
-OUT = os.path.join(ROOT, "gpurun_out")
+OUT = os.path.join(ROOT, os.environ.get("KNN_GPU_OUT", "gpu_out"))
 DST = os.path.join(ROOT, "profiles")
 
 
