@@ -57,6 +57,10 @@
  *   KNN_XCD_ORDER=1 / 0   distance launches in the XCD-grouped / the
  *                         split-major workgroup order (unset: XCD-grouped
  *                         for split-filter launches of <= 2 splits)
+ *   KNN_QUERY_BLOCK=rows  knn_query folds the corpus in blocks of this many
+ *                         rows instead of the capacity it chooses
+ *   KNN_QUERY_TILE=rows   knn_query searches the queries in tiles of this many
+ *                         rows instead of all at once (up to 2^18)
  *   KNN_MAT / KNN_MPI_COMPAT  the CLIs: .mat path, bug-compatible mode
  *   (mpiknn/ring.py: KNN_NO_S8=1 packs element blocks, not the byte block
  *   of knn_block_pack_s8)
@@ -162,7 +166,42 @@ KNN_API int knn_search_mpi_compat(const double *X, size_t m, size_t n, int layou
                                   const double *labels, int k, int procs,
                                   knn_neighbour_t *out);
 
-/* Search wall time of the last knn_search() on this thread, seconds: the
+/* ---------------------------------------------------------------------- *
+ * Out-of-sample queries -- the fold of blk:217-242 (a rank's own block
+ * against the blocks it receives) with a query block that is no part of the
+ * corpus: for every row of Q (mq x n, same layout as X) the k nearest of the
+ * m corpus rows of X, on one GPU (several GPUs: the device-resident API
+ * below, each rank a slice of Q or of X, as the ring does).  out: mq*k
+ * records, idx the 1-based CORPUS row, label from labels[idx - 1] when labels
+ * (nullable, m doubles) is given.  Semantics, order, arithmetic and empty
+ * slots as knn_search; dtype as knn_search.
+ *
+ * flags = 0 keeps the reference's zero rule (blk:217-242 admits a distance
+ * only if it is not 0: a corpus row equal to the query is left out, as
+ * every exact duplicate is in knn_search).  KNN_QUERY_KEEP_ZERO makes S == 0
+ * an ordinary result: distance 0.0, ordered by lower idx among equals -- a
+ * test point identical to a training point gets that point as its nearest
+ * neighbour.  Nothing else changes.
+ *
+ * The queries take the ids m .. m+mq-1 inside the engine (no query id equals
+ * a corpus id; m + mq <= INT32_MAX).  The corpus is folded in blocks of a
+ * capacity the call chooses (KNN_QUERY_BLOCK overrides it), the meta is the
+ * MAX-reduction over every corpus block and the queries, and the int8 / fp16
+ * / split-filter paths are taken when that meta allows, with the int8
+ * re-search and the exact rescan behind them -- the same exact results on
+ * every path.  Query sets too large for one context are tiled
+ * (KNN_QUERY_TILE sets the tile); every tile's records stay on the device
+ * until the last is done, so the reported span holds no copy to the host.
+ * KNN_ERR_INVALID: NULL X, Q or out, zero m, mq or n, k <= 0, a bad layout,
+ * unknown flag bits; KNN_ERR_UNSUPPORTED: an unknown dtype, k above the
+ * dtype's limit -- all before any device call.
+ * knn_last_search_seconds() reports its device span as for knn_search.
+ * ---------------------------------------------------------------------- */
+#define KNN_QUERY_KEEP_ZERO 1   /* flags bit; 0 = the reference's rule (zeros excluded, blk:217-242) */
+KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, size_t n, int layout,
+                      const double *labels, int k, int dtype, int flags, knn_neighbour_t *out);
+
+/* Search wall time of the last knn_search() / knn_query() on this thread, seconds: the
  * span the reference times (serial:70-98, blk:120-250) -- device compute
  * only, excluding load, H2D, D2H and vote. */
 KNN_API double knn_last_search_seconds(void);
@@ -177,6 +216,14 @@ KNN_API double knn_last_search_seconds(void);
  * ---------------------------------------------------------------------- */
 KNN_API int knn_classify(const knn_neighbour_t *nb, size_t m, int k, int nclasses,
                  int vote_rule, const double *labels, int *pred, size_t *matches);
+/* The same vote for knn_query's records: nb holds mq*k records whose idx are
+ * corpus rows, labels the m corpus labels (idx 0 and idx > m are skipped as
+ * empty), qlabels (nullable) the mq query labels.  pred (nullable): mq
+ * predictions; *matches: queries whose prediction equals qlabels[q] (0 when
+ * qlabels is NULL -- only pred is written then). */
+KNN_API int knn_classify_query(const knn_neighbour_t *nb, size_t mq, int k, int nclasses, int vote_rule,
+                               const double *labels, size_t m, const double *qlabels,
+                               int *pred, size_t *matches);
 
 /* The same vote on the device, on the records knn_ctx_end / rescan_end
  * wrote (no host round trip).  d_nb: m*k records of queries with global ids
@@ -185,7 +232,11 @@ KNN_API int knn_classify(const knn_neighbour_t *nb, size_t m, int k, int nclasse
  * d_pred (nullable): m predictions; d_matches (nullable): one device
  * counter, set to the number of queries predicted as their own label.
  * nclasses <= KNN_VOTE_MAX_CLASSES (else KNN_ERR_UNSUPPORTED: use the host
- * knn_classify). */
+ * knn_classify).  Out-of-sample queries need no other entry point: with
+ * q_base = m and d_labels = the m corpus labels followed by the mq query
+ * labels (nlabels = m + mq), query q's own label is d_labels[m + q] and its
+ * neighbours' are corpus labels -- knn_classify_query's result on the
+ * device. */
 #define KNN_VOTE_MAX_CLASSES 1024
 KNN_API int knn_classify_device(knn_neighbour_t *d_nb, size_t m, int k, int nclasses,
                         int vote_rule, const double *d_labels, size_t nlabels, size_t q_base,
@@ -434,6 +485,15 @@ KNN_API int knn_ctx_profile_merge(knn_ctx_t *ctx, double *merge_kernel_ms, int *
  * not wait for the caller's stream on the host first.  A second step in such
  * a search falls back to the step schedule (exact either way).  Default 0. */
 KNN_API int knn_ctx_set_solo(knn_ctx_t *ctx, int on);
+/* The keep-zero distance rule (knn_query's KNN_QUERY_KEEP_ZERO) for the
+ * context's searches: read by knn_ctx_begin* and held for the search begun,
+ * its re-search and its rescan.  Default 0, the reference's rule (blk:217-242,
+ * serial:86: S == 0 is no result).  on != 0: a candidate with S == 0 is a
+ * result like any other (distance 0.0, lower idx first).  Under either rule a
+ * query's own global id (q_base + its row) is never a candidate: the kernels
+ * leave it out by id, so the rule only shows on OTHER rows at distance 0 --
+ * for queries outside the corpus give them ids past it (q_base = m). */
+KNN_API int knn_ctx_set_keep_zero(knn_ctx_t *ctx, int on);
 /* The 8 meta doubles the last search's kernels read (copied to mapped host
  * memory by its last kernel; valid after knn_ctx_end returned KNN_OK): a
  * caller that began the search from a meta hint checks it with this,

@@ -5,7 +5,8 @@
  *   knn_block_pack  -> k_pack_col / k_pack_row (blk:100-109 packing)
  *   knn_ctx_step    -> k_dist_topk + k_merge (one ring step, blk:217-242)
  *   knn_ctx_end     -> k_finalize            (+ rescan pass when needed)
- * and implements the one-call knn_search() of include/knn.h on top.
+ * and implements the one-call knn_search() and knn_query() of include/knn.h
+ * on top.
  */
 #include "knn_internal.h"
 
@@ -108,6 +109,10 @@ struct knn_ctx {
      * ms_keep holds the merge stream meanwhile) */
     int solo, solo_on;
     hipStream_t ms_keep;
+    /* knn_ctx_set_keep_zero: the setting, and its value for the current
+     * search (kz: copied by knn_ctx_begin_meta / _begin_s8; the re-search's
+     * sub-context gets its parent search's kz) */
+    int keep_zero, kz;
     int nsplit_last;
     /* choose_splits cache: (corpus rows, list shape, kernel) -> split count;
      * a direct-exchange pass alternates two launch sizes, and one model
@@ -437,6 +442,16 @@ int knn_ctx_set_solo(knn_ctx_t *c, int on)
     return KNN_OK;
 }
 
+int knn_ctx_set_keep_zero(knn_ctx_t *c, int on)
+{
+    if (!c) return KNN_ERR_INVALID;
+    c->keep_zero = on ? 1 : 0;
+    return KNN_OK;
+}
+
+/* the keep-zero bit of the kernels' filt / xord arguments (knn_internal.h) */
+static int kz_bit(const knn_ctx_t *c) { return c->kz ? KNN_KARG_KEEP0 : 0; }
+
 int knn_ctx_search_meta(const knn_ctx_t *c, double *meta)
 {
     if (!c || !meta || !c->ended) return KNN_ERR_INVALID;
@@ -758,6 +773,7 @@ int knn_ctx_begin_meta(knn_ctx_t *c, const void *d_qblock, size_t q_cap, size_t 
                        const double *d_meta, const double *h_meta, void *stream)
 {
     if (!c || !d_qblock || !d_meta || q_cap < c->nq) return KNN_ERR_INVALID;
+    c->kz = c->keep_zero;
     return ctx_begin(c, d_qblock, NULL, q_cap, q_base, d_meta, h_meta, stream);
 }
 
@@ -766,6 +782,7 @@ int knn_ctx_begin_s8(knn_ctx_t *c, const void *d_sblock, size_t q_cap, size_t q_
 {
     if (!c || !d_sblock || !d_meta || !h_meta || q_cap < c->nq) return KNN_ERR_INVALID;
     if (!knn_s8_spec_ok(h_meta, c->n, c->dtype) || env_on("KNN_NO_I8")) return KNN_ERR_INVALID;
+    c->kz = c->keep_zero;
     return ctx_begin(c, NULL, d_sblock, q_cap, q_base, d_meta, h_meta, stream);
 }
 
@@ -1135,7 +1152,7 @@ static int launch_merge_sets_fin(knn_ctx_t *c, int set, int nsets, int nsplit_to
         RCHK(knn_launch_merge(c->dtype, c->kp, c->k, c->part_d[set], c->part_i[set], c->part_T[set],
                               nsplit_total, c->lpq, c->klx, (int)c->nq, (int)c->nq_pad, !c->merged, c->st_d, c->st_x,
                               c->st_i, c->st_T, c->qblk, c->q_rows_pad, cblk, c_base, (int)nc, (int)c->n,
-                              c->meta, c->qthr, c->split, perm, c->ms));
+                              c->meta, c->qthr, c->split | kz_bit(c), perm, c->ms));
     }
     if (mk) HIPCHK(hipEventRecord(mk[1], c->ms));
     c->merged = 1;
@@ -1369,14 +1386,15 @@ static int ctx_step_impl(knn_ctx_t *c, const void *d_cblock, const void *d_sbloc
         RCHK(knn_launch_dist_i8(c->kp, c->klx, c->lpq, c->k, c->q8, c->q_rows_pad, c->q_base, (int)c->nq, &tab,
                                 knn_rows_pad(c->block_cap), (int)c->n, nsplit, c->part_d[set],
                                 c->part_i[set], c->part_T[set], (int)c->nq_pad, c->qthr,
-                                c->qsum, ds));
+                                c->qsum, c->kz, ds));
     } else
         RCHK(knn_launch_dist_topk(c->dtype, c->kp, c->k, c->qblk, c->q_rows_pad, c->q_base, (int)c->nq,
                                   cblk, knn_rows_pad(c->block_cap), c_base, (int)nc, (int)c->n, c->meta,
                                   nsplit, c->part_d[set], c->part_i[set], c->part_T[set], (int)c->nq_pad,
                                   c->qthr, c->split ? c->qsp : c->qsh, csh, cn_ptr,
                                   (xord_for(c, nsplit) ? KNN_DIST_XORD : 0) | (c->h16 ? KNN_DIST_H16 : 0) |
-                                      (c->shadow ? KNN_DIST_SHADOW : 0) | (c->split ? KNN_DIST_SPLIT : 0),
+                                      (c->shadow ? KNN_DIST_SHADOW : 0) | (c->split ? KNN_DIST_SPLIT : 0) |
+                                      (c->kz ? KNN_DIST_KEEP0 : 0),
                                   c->split ? (float)(-2.0 / ((double)c->sscale * c->sscale)) : -2.f, ds));
     if (ev) HIPCHK(hipEventRecord(ev[1], ds));
     /* one event a step behind its distance kernel (each record is a marker
@@ -1547,7 +1565,8 @@ static int ctx_step_split_n(knn_ctx_t *c, int nblk, const void *const *d_cblocks
     }
     RCHK(knn_launch_dist_split_n(c->dtype, c->kp, c->k, c->qblk, c->q_rows_pad, c->q_base, (int)c->nq, c->qsp, &tab,
                                  (int)c->n, c->meta, nsplit, c->part_d[set], c->part_i[set], c->part_T[set],
-                                 (int)c->nq_pad, c->qthr, xord_for(c, nsplit), (float)(-2.0 / ((double)c->sscale * c->sscale)),
+                                 (int)c->nq_pad, c->qthr, xord_for(c, nsplit) | kz_bit(c),
+                                 (float)(-2.0 / ((double)c->sscale * c->sscale)),
                                  ds));
     if (ev) HIPCHK(hipEventRecord(ev[1], ds));
     HIPCHK(hipEventRecord(c->ev_ds[set], ds));
@@ -1574,7 +1593,8 @@ static int ctx_step_split_n(knn_ctx_t *c, int nblk, const void *const *d_cblocks
     }
     RCHK(knn_launch_merge_n(c->dtype, c->kp, c->k, c->part_d[mset], c->part_i[mset], c->part_T[mset], mnsplit,
                             c->lpq, c->klx, (int)c->nq, (int)c->nq_pad, !c->merged, c->st_d, c->st_x, c->st_i,
-                            c->st_T, c->qblk, c->q_rows_pad, &mb, (int)c->n, c->meta, c->qthr, c->split, perm, c->ms));
+                            c->st_T, c->qblk, c->q_rows_pad, &mb, (int)c->n, c->meta, c->qthr, c->split | kz_bit(c), perm,
+                            c->ms));
     c->merged = 1;
     HIPCHK(hipEventRecord(c->ev_m[set], c->ms));
     if (share) HIPCHK(hipEventRecord(c->ev_m[mset], c->ms));
@@ -1658,6 +1678,7 @@ static int research8_run(knn_ctx_t *c, int nblk, const void *const *blk, const s
     }
     knn_ctx_t *u = c->sub;
     u->nq = (size_t)nf;   /* within the capacity it was created with */
+    u->kz = c->kz;        /* this sub-search under the search's zero rule (ctx_begin leaves kz alone) */
     u->nq_pad = knn_round_up((size_t)nf, KNN_TQ);
     /* q_base just past the block's last row id: no row is masked as "the
      * query itself" (its d^2 = 0 is dropped like every exact duplicate,
@@ -1713,6 +1734,10 @@ static int research8(knn_ctx_t *c, knn_neighbour_t *d_out, hipStream_t s)
         c->step0_cbase != c->q_base || c->q_rows_pad != knn_rows_pad(c->block_cap) || c->kp > KNN_KP_M ||
         env_on("KNN_FORCE_RESCAN") || env_on("KNN_NO_RESEARCH8"))
         return KNN_OK;
+    /* keep-zero on the search's own block: the re-search's gathered queries
+     * carry no ids, so their own rows could only be told by the zero -- which
+     * is now a result.  The exact rescan (which knows the ids) takes them. */
+    if (c->kz) return KNN_OK;
     return research8_run(c, 0, NULL, NULL, NULL, c->step0_cbase + c->step0_nc, d_out, s);
 }
 
@@ -1754,6 +1779,10 @@ int knn_ctx_research_blocks(knn_ctx_t *c, int nblk, const void *const *d_sblocks
         if (!d_sblocks[b] || nc[b] == 0 || nc[b] > c->block_cap) return KNN_ERR_INVALID;
         if (c_base[b] + nc[b] > q_end) q_end = c_base[b] + nc[b];
     }
+    /* keep-zero: only when no block holds a query's own row (above) */
+    if (c->kz)
+        for (int b = 0; b < nblk; b++)
+            if (c_base[b] < c->q_base + c->nq && c->q_base < c_base[b] + nc[b]) return KNN_OK;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int before = c->nfail;
@@ -1783,7 +1812,7 @@ static int ctx_end_device(knn_ctx_t *c, knn_neighbour_t *d_out, hipStream_t s)
         RCHK(knn_launch_finalize(c->dtype, c->kp, c->st_d, c->st_x, c->st_i, c->st_T, c->qblk, c->q_rows_pad,
                                  (int)c->nq, (int)c->n, c->k, c->meta, d_out, c->fail_count,
                                  c->fail_list, c->mode_dev, c->fbound, env_on("KNN_FORCE_RESCAN"),
-                                 c->split, c->ms));
+                                 c->split | kz_bit(c), c->ms));
     HIPCHK(hipEventRecord(c->ev_end, c->ms));
     HIPCHK(hipStreamWaitEvent(s, c->ev_end, 0));
     return KNN_OK;
@@ -1802,7 +1831,7 @@ static int ctx_end_merge(knn_ctx_t *c, knn_neighbour_t *d_out)
         RCHK(knn_launch_finalize(c->dtype, c->kp, c->st_d, c->st_x, c->st_i, c->st_T, c->qblk, c->q_rows_pad,
                                  (int)c->nq, (int)c->n, c->k, c->meta, d_out, c->fail_count,
                                  c->fail_list, c->mode_dev, c->fbound, env_on("KNN_FORCE_RESCAN"),
-                                 c->split, c->ms));
+                                 c->split | kz_bit(c), c->ms));
     c->h_count[0] = c->h_count[1] = -1;
     RCHK(knn_launch_count_out(c->fail_count, c->h_count_dev, c->meta,
                               (double *)((char *)c->h_count_dev + 16), c->ms));
@@ -1893,7 +1922,7 @@ int knn_ctx_rescan_step(knn_ctx_t *c, const void *d_cblock, size_t nc, size_t c_
     HIPCHK(hipSetDevice(c->device));
     return knn_launch_rescan_step(c->dtype, c->kp, c->fail_list, c->nfail, c->fbound, c->qblk,
                                   d_cblock, c_base, (int)nc, (int)c->n, c->k, c->rs_d, c->rs_i,
-                                  stream);
+                                  c->kz ? (long long)c->q_base : -1LL, stream);
 }
 
 int knn_ctx_rescan_end(knn_ctx_t *c, knn_neighbour_t *d_out, void *stream)
@@ -1920,6 +1949,193 @@ int knn_search_packed(knn_ctx_t *c, const void *d_block, size_t m, knn_neighbour
         RCHK(knn_ctx_rescan_end(c, d_out, stream));
     }
     return KNN_OK;
+}
+
+/* knn_query (include/knn.h): out-of-sample queries on one GPU.  The corpus is
+ * packed into resident blocks of one capacity (KNN_QUERY_BLOCK=rows overrides
+ * the choice), the queries into tiles of at most KNN_QUERY_TILE_MAX rows
+ * (KNN_QUERY_TILE=rows overrides that, for tests) with
+ * ids m.. (past every corpus id, so no row is ever "the query itself"), and
+ * each tile runs the ring rank's sequence against foreign blocks
+ * (blk:217-242): begin on the MAX-reduced meta of every block and tile, the
+ * fold of every corpus block, end, the int8 re-search where it applies, then
+ * the exact rescan over every block.  The records of every tile stay on the
+ * device until the last tile is done: the timed span holds no copy to the
+ * host. */
+#define KNN_QUERY_BYTES_MAX ((size_t)1 << 30)   /* element bytes of one block / tile */
+#define KNN_QUERY_TILE_MAX ((size_t)1 << 18)
+
+static int query_tile(knn_ctx_t *ctx, size_t nblk, void *const *cblk, void *const *cs8,
+                      const size_t *cnc, const size_t *cbase, const void *qblk, const void *qs8, size_t tcap,
+                      size_t rows, size_t q_base, const double *d_meta, const double *h_meta,
+                      knn_neighbour_t *d_out)
+{
+    /* the tile's rows within the context's capacity (as research8_run) */
+    ctx->nq = rows;
+    ctx->nq_pad = knn_round_up(rows, KNN_TQ);
+    size_t unresolved = 0;
+    if (qs8) {
+        RCHK(knn_ctx_begin_s8(ctx, qs8, tcap, q_base, d_meta, h_meta, NULL));
+        RCHK(knn_ctx_step_shadow_n(ctx, (int)nblk, (const void *const *)cs8, cnc, cbase, NULL));
+    } else {
+        RCHK(knn_ctx_begin_meta(ctx, qblk, tcap, q_base, d_meta, h_meta, NULL));
+        RCHK(knn_ctx_step_n(ctx, (int)nblk, (const void *const *)cblk, cnc, cbase, NULL));
+    }
+    RCHK(knn_ctx_end(ctx, d_out, &unresolved, NULL));
+    if (unresolved && qs8) {
+        /* the re-search takes every block at once: together they are the corpus */
+        RCHK(knn_ctx_attach_qblock(ctx, qblk, tcap));
+        RCHK(knn_ctx_research_blocks(ctx, (int)nblk, (const void *const *)cs8, cnc, cbase, d_out, &unresolved, NULL));
+    }
+    if (unresolved) {
+        for (size_t b = 0; b < nblk; b++) RCHK(knn_ctx_rescan_step(ctx, cblk[b], cnc[b], cbase[b], NULL));
+        RCHK(knn_ctx_rescan_end(ctx, d_out, NULL));
+    }
+    return KNN_OK;
+}
+
+int knn_query(const double *X, size_t m, const double *Q, size_t mq, size_t n, int layout, const double *labels,
+              int k, int dtype, int flags, knn_neighbour_t *out)
+{
+    if (!X || !Q || !out || m == 0 || mq == 0 || n == 0 || k <= 0) return KNN_ERR_INVALID;
+    if (!dtype_ok(dtype)) return KNN_ERR_UNSUPPORTED;
+    if (k > (dtype == KNN_F32 ? KNN_MAX_K_F32 : KNN_MAX_K)) return KNN_ERR_UNSUPPORTED;
+    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (flags & ~KNN_QUERY_KEEP_ZERO) return KNN_ERR_INVALID;
+    if (m > 0x7fffffffULL || mq > 0x7fffffffULL || m + mq > 0x7fffffffULL || n > 0x7fffffffULL)
+        return KNN_ERR_INVALID;
+
+    /* block and tile capacities: at most KNN_QUERY_BYTES_MAX of elements each */
+    const size_t row_bytes = knn_n_pad_dt(n, dtype) * knn_esize(dtype);
+    size_t fit = KNN_QUERY_BYTES_MAX / row_bytes;
+    if (fit < 1024) fit = 1024;
+    size_t cap = m < fit ? m : fit;
+    {
+        const char *e = getenv("KNN_QUERY_BLOCK");
+        if (e && atol(e) > 0) cap = (size_t)atol(e) < m ? (size_t)atol(e) : m;
+    }
+    size_t tcap = mq < fit ? mq : fit;
+    if (tcap > KNN_QUERY_TILE_MAX) tcap = KNN_QUERY_TILE_MAX;
+    {
+        const char *e = getenv("KNN_QUERY_TILE");
+        if (e && atol(e) > 0) tcap = (size_t)atol(e) < mq ? (size_t)atol(e) : mq;
+    }
+    const size_t nblk = (m + cap - 1) / cap, ntile = (mq + tcap - 1) / tcap;   /* (both <= INT32_MAX) */
+
+    knn_ctx_t *ctx = NULL;
+    int rc = knn_ctx_create_dt(&ctx, 0, tcap, n, cap, k, dtype);
+    if (rc) return rc;
+    knn_ctx_set_keep_zero(ctx, (flags & KNN_QUERY_KEEP_ZERO) != 0);
+
+    double *d_X = NULL, *d_Q = NULL, *d_meta = NULL;
+    knn_neighbour_t *d_out = NULL;
+    hipEvent_t e0 = NULL, e1 = NULL;
+    /* [corpus blocks][query tiles]: element blocks, byte blocks (int8 path) */
+    const size_t nall = nblk + ntile;
+    void **blk = (void **)calloc(2 * nall, sizeof(void *));
+    size_t *cnc = (size_t *)calloc(2 * nblk, sizeof(size_t));
+    double *hm = (double *)calloc(nall * KNN_META_DOUBLES, sizeof(double));
+    if (!blk || !cnc || !hm) {
+        rc = KNN_ERR_NOMEM;
+        goto done;
+    }
+    void **s8 = blk + nall;
+    size_t *cbase = cnc + nblk;
+    if (hipMalloc((void **)&d_X, m * n * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&d_Q, mq * n * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&d_meta, KNN_META_DOUBLES * sizeof(double)) != hipSuccess ||
+        hipMalloc((void **)&d_out, mq * (size_t)k * sizeof(knn_neighbour_t)) != hipSuccess) {
+        rc = KNN_ERR_NOMEM;
+        goto done;
+    }
+    for (size_t b = 0; b < nall; b++)
+        if (hipMalloc(&blk[b], knn_block_bytes_dt(b < nblk ? cap : tcap, n, dtype)) != hipSuccess) {
+            rc = KNN_ERR_NOMEM;
+            goto done;
+        }
+    if (hipMemcpy(d_X, X, m * n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_Q, Q, mq * n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
+        rc = KNN_ERR_HIP;
+        goto done;
+    }
+    hipEventRecord(e0, NULL);
+    /* pack every block and tile, then MAX-reduce their meta on the host */
+    for (size_t b = 0; b < nall && !rc; b++) {
+        const int corpus = b < nblk;
+        const size_t bc = corpus ? cap : tcap, r0 = corpus ? b * cap : (b - nblk) * tcap;
+        const size_t tot = corpus ? m : mq, rows = tot - r0 < bc ? tot - r0 : bc;
+        const double *src = (corpus ? d_X : d_Q) + (layout == KNN_COLMAJOR ? r0 : r0 * n);
+        if (corpus) {
+            cnc[b] = rows;
+            cbase[b] = r0;
+        }
+        rc = knn_block_pack_dt(blk[b], dtype, bc, rows, n, src, KNN_F64, layout == KNN_COLMAJOR ? tot : n, layout,
+                               NULL);
+        if (!rc && hipMemcpyAsync(hm + b * KNN_META_DOUBLES,
+                                  (const char *)blk[b] + knn_block_meta_offset_dt(bc, n, dtype),
+                                  KNN_META_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, NULL) != hipSuccess)
+            rc = KNN_ERR_HIP;
+    }
+    if (!rc && hipStreamSynchronize(NULL) != hipSuccess) rc = KNN_ERR_HIP;
+    if (rc) goto done;
+    double red[KNN_META_DOUBLES];
+    for (int j = 0; j < KNN_META_DOUBLES; j++) {
+        red[j] = hm[j];
+        for (size_t b = 1; b < nall; b++)
+            if (hm[b * KNN_META_DOUBLES + j] > red[j]) red[j] = hm[b * KNN_META_DOUBLES + j];
+    }
+    if (hipMemcpy(d_meta, red, sizeof(red), hipMemcpyHostToDevice) != hipSuccess) {
+        rc = KNN_ERR_HIP;
+        goto done;
+    }
+    /* 8-bit data: the byte blocks straight from the source (knn_block_pack_s8);
+     * they stay resident for the re-search */
+    const int use_s8 = knn_s8_spec_ok(red, n, dtype);
+    for (size_t b = 0; b < nall && use_s8 && !rc; b++) {
+        const int corpus = b < nblk;
+        const size_t bc = corpus ? cap : tcap, r0 = corpus ? b * cap : (b - nblk) * tcap;
+        const size_t tot = corpus ? m : mq, rows = tot - r0 < bc ? tot - r0 : bc;
+        const double *src = (corpus ? d_X : d_Q) + (layout == KNN_COLMAJOR ? r0 : r0 * n);
+        if (hipMalloc(&s8[b], knn_s8_bytes(bc, n)) != hipSuccess) {
+            rc = KNN_ERR_NOMEM;
+            break;
+        }
+        rc = knn_block_pack_s8(s8[b], dtype, bc, rows, n, src, KNN_F64, layout == KNN_COLMAJOR ? tot : n, layout,
+                               NULL);
+    }
+    for (size_t t = 0; t < ntile && !rc; t++) {
+        const size_t r0 = t * tcap, rows = mq - r0 < tcap ? mq - r0 : tcap;
+        rc = query_tile(ctx, nblk, blk, use_s8 ? s8 : NULL, cnc, cbase, blk[nblk + t],
+                        use_s8 ? s8[nblk + t] : NULL, tcap, rows, m + r0, d_meta, red, d_out + r0 * (size_t)k);
+    }
+    if (!rc) {
+        float ms = 0.f;
+        hipEventRecord(e1, NULL);
+        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
+            rc = KNN_ERR_HIP;
+        g_last_search_s = ms * 1e-3;
+    }
+    if (!rc && hipMemcpy(out, d_out, mq * (size_t)k * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = KNN_ERR_HIP;
+done:
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    if (blk)
+        for (size_t b = 0; b < 2 * nall; b++) hipFree(blk[b]);
+    hipFree(d_X);
+    hipFree(d_Q);
+    hipFree(d_meta);
+    hipFree(d_out);
+    free(blk);
+    free(cnc);
+    free(hm);
+    knn_ctx_destroy(ctx);
+    if (!rc && labels) {
+        for (size_t i = 0; i < mq * (size_t)k; i++)
+            out[i].label = out[i].idx > 0 ? (int32_t)labels[out[i].idx - 1] : 0;
+    }
+    return rc;
 }
 
 /* Multi-GPU one-call path lives in knn_ring.c. */

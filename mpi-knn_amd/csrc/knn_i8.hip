@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void k_shadow8(signed char *__restrict__ dst, 
 // entry a round through the insertion network) and refreshes the bounds, so
 // the network runs on dense rounds instead of once per survivor of the
 // busiest lane per tile.  d^2 is exact, so "S != 0" (serial:86) is d^2 > 0,
-// applied at the merge.
+// applied at the merge (not at all when zeros are kept: uj bit 17).
 //
 // Ablations of this kernel (no epilogue, keys only, no DMA, no barrier, no
 // MFMA, survivor counters) were measured with the tuning
@@ -518,7 +518,10 @@ __global__ __launch_bounds__(64 * W, WPS) void k_dist_topk_i8(
             if (e < cnt[g]) {
                 d = bk[64 * e];
                 id = bi[64 * e];
-                d = d > 0 ? d : I8_INF;   // d^2 == 0: an exact duplicate (serial:86)
+                // d^2 == 0: an exact duplicate (serial:86) -- unless zeros
+                // are kept (uj bit 17, knn_ctx_set_keep_zero; wave-uniform)
+                // -- the floor is 0, or -1 below every d^2: no branch
+                d = d > -((uj >> 17) & 1) ? d : I8_INF;
             }
             i8_insert<KL>(L[g], I[g], d, id);
         }
@@ -1008,7 +1011,8 @@ static void launch_i8(dim3 grid, hipStream_t s, const void *qsh, size_t q_rows_p
 extern "C" int knn_launch_dist_i8(int kp, int kl, int lpq, int k, const void *qsh, size_t q_rows_pad, size_t q_base,
                                   int nq, const knn_i8_blocks_t *cbp, size_t c_rows_pad, int n,
                                   int nsplit, double *part_d, int *part_i, double *part_T,
-                                  int nq_pad, double *qthr, unsigned long long *qsum, void *stream)
+                                  int nq_pad, double *qthr, unsigned long long *qsum, int keep_zero,
+                                  void *stream)
 {
     const int rs = (int)knn_s8_rs((size_t)n), nks = rs / 32;
     const int qg = knn_i8_qg(kl, lpq, (size_t)n);
@@ -1049,6 +1053,7 @@ extern "C" int knn_launch_dist_i8(int kp, int kl, int lpq, int k, const void *qs
     if (lpq == 4 && 4 * kl < k + 1) return KNN_ERR_INVALID;   // the 4-lane bound needs 4 KL >= k + 1
     uj |= uj4 << 8;
     if (no2) uj |= 1 << 16;
+    if (keep_zero) uj |= KNN_I8_UJ_KEEP0;
     const dim3 grid((unsigned)(nqb * nsplit));
     hipStream_t s = (hipStream_t)stream;
     // cross-split summaries combine 4 x 8 or 2 x 16 rows: for k + 1 <= 32

@@ -144,6 +144,16 @@ int knn_launch_dist_topk(int dtype, int kp, int k, const void *qblk, size_t q_ro
 #define KNN_DIST_SHADOW 4  /* with H16: stage the fp16 shadow rows qsh / csh      */
 #define KNN_DIST_SPLIT  8  /* fp32 blocks: split fp16 filter on the split shadow rows
                               qsh / csh (knn_launch_shadow_split); m2s = -2 / S^2   */
+#define KNN_DIST_KEEP0 16  /* the keep-zero rule (knn_ctx_set_keep_zero)               */
+/* The keep-zero rule reaches the kernels inside an int argument they already
+ * take, so a search with the rule off launches with exactly the arguments it
+ * always had: bit 1 of `xord` (k_dist_topk, k_dist_split; knn_launch_dist_split
+ * and _split_n take the argument as is), bit 1 of `filt` (k_merge, k_finalize),
+ * bit 17 of `uj` (k_dist_topk_i8).  k_rescan_step takes self_base: -1, or the
+ * search's q_base when zeros are kept (the query's own row is then left out
+ * by id, as the distance kernels do, not by its zero distance). */
+#define KNN_KARG_KEEP0 2
+#define KNN_I8_UJ_KEEP0 (1 << 17)
 /* k_dist_split (knn_split.hip): the split fp16 filter on 256-row tiles,
  * over up to KNN_SPLIT_MAXBLK corpus blocks in one launch (block b: split
  * rows sp[b], norms nrm[b] of its element block, global ids base[b].., nc[b]
@@ -222,7 +232,7 @@ int knn_launch_shadow8(void *dst, const void *blk, int dtype, size_t rows_pad, s
 int knn_launch_dist_i8(int kp, int kl, int lpq, int k, const void *qsh, size_t q_rows_pad, size_t q_base, int nq,
                        const knn_i8_blocks_t *cb, size_t c_rows_pad, int n, int nsplit,
                        double *part_d, int *part_i, double *part_T, int nq_pad, double *qthr,
-                       unsigned long long *qsum, void *stream);
+                       unsigned long long *qsum, int keep_zero, void *stream);
 int knn_launch_merge(int dtype, int kp, int k, const double *part_d, const int *part_i,
                      const double *part_T, int nsplit, int lpq, int kl, int nq, int nq_pad,
                      int first_step,
@@ -244,7 +254,7 @@ int knn_launch_rescan_init(int kp, double *rs_d, int *rs_i, int nfail, void *str
 int knn_launch_rescan_step(int dtype, int kp, const int *fail_list, int nfail,
                            const double *fbound, const void *qblk, const void *cblk,
                            size_t c_base, int nc, int n, int k, double *rs_d, int *rs_i,
-                           void *stream);
+                           long long self_base, void *stream);
 int knn_launch_rescan_end(int kp, const int *fail_list, int nfail, const double *rs_d,
                           const int *rs_i, int k, knn_neighbour_t *out, void *stream);
 int knn_launch_vote(knn_neighbour_t *nb, size_t m, int k, int nclasses, int rule,

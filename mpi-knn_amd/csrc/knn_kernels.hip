@@ -555,8 +555,9 @@ __global__ __launch_bounds__(512, 2) void k_dist_topk(
     // (qb % 8): one XCD, dispatched back to back -- they stream the same
     // query chunks in step (L2 hits), and co-resident blocks of one split
     // share corpus tiles.  The grid is padded to whole groups of 8 blocks.
+    // (xord bit 1, KNN_KARG_KEEP0: the keep-zero rule, below)
     int qb, split;
-    if (xord) {
+    if (xord & 1) {
         const int slot = blockIdx.x >> 3;
         split = slot % nsplit;
         qb = ((slot / nsplit) << 3) + (blockIdx.x & 7);
@@ -736,8 +737,9 @@ __global__ __launch_bounds__(512, 2) void k_dist_topk(
         // applied (masking here made hipcc copy all 32 d^2 at the join)
         const bool any = masked || __ballot(lanemin <= lim) != 0ull;   // rare late in the scan
         if (any) {
-            // INT mode: d^2 is exact and >= 0, so "S != 0" (serial:86) is d^2 > 0
-            const T zfloor = (mode == KNN_MODE_INT) ? (T)0 : (T)-KNN_INF;
+            // INT mode: d^2 is exact and >= 0, so "S != 0" (serial:86) is d^2 > 0;
+            // keep-zero (knn_ctx_set_keep_zero): no floor, a zero is a result
+            const T zfloor = (mode == KNN_MODE_INT && !(xord & KNN_KARG_KEEP0)) ? (T)0 : (T)-KNN_INF;
             unsigned pend_all = 0;
 #pragma unroll
             for (int mt = 0; mt < 8; mt++)
@@ -1082,6 +1084,14 @@ __global__ __launch_bounds__(256) void k_merge(
     const unsigned long long segm = (S == 64) ? ~0ull : (0xffffffffull << (32 * seg));
     const int mode = knn_mode<TE>(meta, n);
     const int nl = lpq * nsplit;   // partial lists: [split][query][lpq][kl]
+    // keep-zero (bit 1 of filt, wave-uniform): an S == 0 candidate is a
+    // result like any other, so no slot is set aside for excluded zeros --
+    // z = 0 in the window, the early stop and the publication below.  The
+    // state still keeps k + 1 entries and publishes the (k+1)-th: the
+    // certificates compare the k-th kept key with the bound the filters
+    // rejected at (tau < T), which the k-th itself as the bound would fail.
+    const bool keep0 = (filt & KNN_KARG_KEEP0) != 0;
+    filt &= 1;
 
     static_assert(PF == 0 || (PF == 8 && KP % PF == 0), "prefetch depth");
     constexpr int NST = PF > 0 ? KP / PF : 1;   // state lanes
@@ -1230,7 +1240,7 @@ __global__ __launch_bounds__(256) void k_merge(
         if (live) {
             if (r < KP) {
                 nsel++;
-                if (wd <= Eq) nzs++;
+                if (!keep0 && wd <= Eq) nzs++;
                 else if (nsel - nzs == k) dkc = wd;
                 if (sl == r % S) {
 #pragma unroll
@@ -1285,7 +1295,7 @@ __global__ __launch_bounds__(256) void k_merge(
         int z = 0;
 #pragma unroll
         for (int x = 0; x < NS; x++) z += __popcll(__ballot(sl + S * x < KP && sd[x] == 0.0) & segm);
-        const int rk = k + z;
+        const int rk = keep0 ? k : k + z;
         if (rk < KP) {
             double u = KNN_INF;
 #pragma unroll
@@ -1319,7 +1329,7 @@ __global__ __launch_bounds__(256) void k_merge(
         int z = 0;
 #pragma unroll
         for (int x = 0; x < NS; x++) z += __popcll(__ballot(sl + S * x < KP && sd[x] <= E) & segm);
-        const int rk = k - 1 + z;
+        const int rk = keep0 ? k - 1 : k - 1 + z;
         double dk = KNN_INF;
         if (rk < KP) {
 #pragma unroll
@@ -1372,7 +1382,8 @@ __global__ __launch_bounds__(256) void k_merge(
 
 // ---------------------------------------------------------------------------
 // k_merge_rank: the INT-mode merge of int8 lane lists (k_dist_topk_i8: exact
-// integer d^2 < 2^31, zeros never admitted) by ranking instead of argmin
+// integer d^2 < 2^31; zeros never admitted, or -- keep-zero -- admitted as
+// the results they are: nothing here tells them apart) by ranking instead of argmin
 // rounds.  One wave per query.  The shared bound qthr[q] is an upper bound on
 // the query's (k+1)-th smallest d^2 over all rows (k + 1 distinct rows lie at
 // or below it), so no entry above it can be among the k + 1 smallest; the
@@ -1938,6 +1949,9 @@ __global__ __launch_bounds__(256) void k_finalize(
     if (blockIdx.x == 0 && threadIdx.x == 0) *mode_out = mode;
     if (q >= nq) return;
     knn_neighbour_t *o = out + (size_t)q * k;
+    // keep-zero (bit 1 of filt): S == 0 is a result, distance 0.0
+    const bool keep0 = (filt & KNN_KARG_KEEP0) != 0;
+    filt &= 1;
 
     // force_fail: tests of the rescan pass; no query norms (a context begun
     // from a byte block alone, knn_ctx_begin_s8) outside INT mode: nothing
@@ -1967,7 +1981,8 @@ __global__ __launch_bounds__(256) void k_finalize(
     const double T = st_T[2 * (size_t)q], Td = st_T[2 * (size_t)q + 1];
     const int kl = k - 1;
     if (mode == KNN_MODE_INT) {
-        // state is sorted by exact (d^2, idx) and zeros were never admitted.
+        // state is sorted by exact (d^2, idx) and zeros were never admitted
+        // (or, with keep-zero, admitted as the results they are).
         // A candidate a lane filter turned away has d^2 >= T; with d^2 == T
         // it may precede the k-th by index, so certify only tau < T.
         bool valid[NS];
@@ -2015,7 +2030,7 @@ __global__ __launch_bounds__(256) void k_finalize(
     int kid[NS], rank[NS];
 #pragma unroll
     for (int x = 0; x < NS; x++) {
-        valid[x] = (si[x] >= 0) && (sx[x] == sx[x]) && (sx[x] != 0.0) && (sx[x] < KNN_INF);
+        valid[x] = (si[x] >= 0) && (sx[x] == sx[x]) && (keep0 || sx[x] != 0.0) && (sx[x] < KNN_INF);
         key[x] = valid[x] ? sqrt(sx[x]) : KNN_INF;
         kid[x] = valid[x] ? si[x] : 0x7fffffff;
         rank[x] = 0;
@@ -2104,7 +2119,7 @@ __global__ __launch_bounds__(256) void k_rescan_step(
     const int *__restrict__ fail_list, int nfail, const double *__restrict__ fbound,
     const TE *__restrict__ qblk, int n_pad_q, const TE *__restrict__ cblk, size_t c_base,
     int nc, int n, int n_pad, int k, const double *rs_bound, double *rs_d, int *rs_i,
-    int rows_per_chunk, size_t chunk_stride)
+    int rows_per_chunk, size_t chunk_stride, long long self_base)
 {
 #pragma clang fp contract(off)
     constexpr int KT = 4, QW = 4;
@@ -2124,15 +2139,19 @@ __global__ __launch_bounds__(256) void k_rescan_step(
     rs_d += blockIdx.y * chunk_stride;
     rs_i += blockIdx.y * chunk_stride;
 
+    // self_base >= 0: keep-zero -- a zero distance is admitted, and the
+    // query's own row (global id self_base + q) is left out by id instead
+    const bool keep0 = self_base >= 0;
     const TE *qp[QW];
     double dcut[QW];
-    int slot[QW];
+    int slot[QW], self[QW];
     bool done[QW];
 #pragma unroll
     for (int x = 0; x < QW; x++) {
         slot[x] = slot0 + x;
         done[x] = slot[x] >= nfail;
         const int q = done[x] ? fail_list[slot0] : fail_list[slot[x]];
+        self[x] = keep0 ? (int)(self_base + q) : -1;
         qp[x] = qblk + (size_t)q * n_pad_q;
         const double kth = rs_bound[(size_t)(done[x] ? slot0 : slot[x]) * KP + (k - 1)];
         dcut[x] = fmin(fbound[q], kth);
@@ -2188,7 +2207,7 @@ __global__ __launch_bounds__(256) void k_rescan_step(
 #pragma unroll
             for (int x = 0; x < QW; x++) {
                 const double d = sqrt(S[x]);
-                if (!done[x] && d != 0.0 && d < KNN_INF && d <= dcut[x] &&
+                if (!done[x] && (keep0 ? id != self[x] : d != 0.0) && d < KNN_INF && d <= dcut[x] &&
                     (d > fd[x] || (d == fd[x] && id > fi[x]))) {
                     cnt[x]++;
                     list_insert<KT>(L[x], I[x], d, id);   // rows ascend: ties stay in id order
@@ -2651,6 +2670,8 @@ static int launch_dist_topk(const T *qblk, size_t q_rows_pad, size_t q_base, int
                             const void *cn_ptr, int flags, float m2s, hipStream_t s)
 {
     const int xord = flags & 1;
+    // the kernels' xord argument: bit 0 the workgroup order, bit 1 keep-zero
+    const int xarg = xord | ((flags & KNN_DIST_KEEP0) ? KNN_KARG_KEEP0 : 0);
     constexpr int dt = sizeof(T) == 8 ? KNN_F64 : KNN_F32;
     const int np = (int)knn_n_pad_dt(n, dt);
     const int nqb = (nq + KNN_TQ - 1) / KNN_TQ;
@@ -2687,7 +2708,7 @@ static int launch_dist_topk(const T *qblk, size_t q_rows_pad, size_t q_base, int
         cb.nc[0] = nc;
         cb.lim[0] = (int)c_rows_pad;
         return knn_launch_dist_split(dt, KL, qsh, qnorm, q_base, nq, &cb, n, meta, nsplit, part_d, part_i, part_T,
-                                     nq_pad, qthr, uj, xord, m2s, s);
+                                     nq_pad, qthr, uj, xarg, m2s, s);
     }
     if ((flags & KNN_DIST_SHADOW) && (flags & KNN_DIST_H16)) {
         if (!qsh || !csh) return KNN_ERR_INVALID;
@@ -2700,12 +2721,12 @@ static int launch_dist_topk(const T *qblk, size_t q_rows_pad, size_t q_base, int
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dist_topk<T, KL, KP, 0, 2>), grid, dim3(512), 0, s,
                                (const T *)qsh, qnorm, q_base, nq, (const T *)csh, cnorm, c_base, nc, n,
                                nps, ntiles, nsplit, nqb, meta, part_d, part_i, part_T, nq_pad,
-                               (unsigned long long *)qthr, uj, xord);
+                               (unsigned long long *)qthr, uj, xarg);
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dist_topk<T, KL, KP, 1, 2>), grid, dim3(512), 0, s,
                                (const T *)qsh, qnorm, q_base, nq, (const T *)csh, cnorm, c_base, nc, n,
                                nps, ntiles, nsplit, nqb, meta, part_d, part_i, part_T, nq_pad,
-                               (unsigned long long *)qthr, uj, xord);
+                               (unsigned long long *)qthr, uj, xarg);
         return hip_status();
     }
     {
@@ -2713,13 +2734,13 @@ static int launch_dist_topk(const T *qblk, size_t q_rows_pad, size_t q_base, int
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dist_topk<T, KL, KP, 0, 1>), grid, dim3(512), 0, s,
                                qblk, qnorm, q_base, nq, cblk, cnorm, c_base, nc, n, np, ntiles, nsplit,
                                nqb, meta, part_d, part_i, part_T, nq_pad, (unsigned long long *)qthr,
-                               uj, xord);
+                               uj, xarg);
             return hip_status();
         }
     }
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dist_topk<T, KL, KP>), grid, dim3(512), 0, s, qblk, qnorm,
                        q_base, nq, cblk, cnorm, c_base, nc, n, np, ntiles, nsplit, nqb, meta, part_d,
-                       part_i, part_T, nq_pad, (unsigned long long *)qthr, uj, xord);
+                       part_i, part_T, nq_pad, (unsigned long long *)qthr, uj, xarg);
     return hip_status();
 }
 
@@ -2933,7 +2954,7 @@ extern "C" int knn_launch_rescan_init(int kp, double *rs_d, int *rs_i, int nfail
 extern "C" int knn_launch_rescan_step(int dtype, int kp, const int *fail_list, int nfail,
                                       const double *fbound, const void *qblk, const void *cblk,
                                       size_t c_base, int nc, int n, int k, double *rs_d,
-                                      int *rs_i, void *stream)
+                                      int *rs_i, long long self_base, void *stream)
 {
     if (nfail <= 0) return KNN_OK;
     if (k <= 0 || k > kp || nc <= 0) return KNN_ERR_INVALID;
@@ -2959,7 +2980,7 @@ extern "C" int knn_launch_rescan_step(int dtype, int kp, const int *fail_list, i
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rescan_step<T, KP>),                                    \
                        dim3((unsigned)((nfail + 15) / 16), (unsigned)C), dim3(256), 0, s,         \
                        fail_list, nfail, fbound, (const T *)qblk, np, (const T *)cblk, c_base, nc, \
-                       n, np, k, rs_d, ld, li, rpc, C > 1 ? stride : 0);                          \
+                       n, np, k, rs_d, ld, li, rpc, C > 1 ? stride : 0, self_base);               \
     if (C > 1)                                                                                   \
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rescan_merge<KP>), dim3((unsigned)((nfail + 3) / 4)), \
                            dim3(256), 0, s, nfail, k, C, rs_d, rs_i);                            \

@@ -108,9 +108,9 @@ __global__ __launch_bounds__(512) void k_dist_split(
     const int g = lane >> 4, j16 = lane & 15;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
     // workgroup order: split-major (xord 0) or XCD-grouped (xord 1), as
-    // k_dist_topk
+    // k_dist_topk (bit 1 of the argument: the keep-zero rule, below)
     int qb, split;
-    if (xord) {
+    if (xord & 1) {
         const int slot = blockIdx.x >> 3;
         split = slot % nsplit;
         qb = ((slot / nsplit) << 3) + (blockIdx.x & 7);
@@ -267,7 +267,8 @@ __global__ __launch_bounds__(512) void k_dist_split(
             for (int r = (mt == 0 ? 1 : 0); r < 4; r++) lanemin = fminf(lanemin, acc[mt][r]);
         const bool any = masked || __ballot(lanemin <= lim) != 0ull;
         if (any) {
-            const float zfloor = (mode == KNN_MODE_INT) ? 0.f : -__builtin_inff();
+            // (keep-zero, knn_ctx_set_keep_zero: no floor in any mode)
+            const float zfloor = (mode == KNN_MODE_INT && !(xord & KNN_KARG_KEEP0)) ? 0.f : -__builtin_inff();
             unsigned long long pend = 0;
 #pragma unroll
             for (int mt = 0; mt < 16; mt++)
@@ -457,7 +458,7 @@ static int launch_split(const void *qsp, const T *qnorm, size_t q_base, int nq, 
 {
     const int rsb = (int)knn_split_rs((size_t)n);
     const int nqb = (nq + SP_TQ - 1) / SP_TQ;
-    const int nqb_grid = xord ? (nqb + 7) / 8 * 8 : nqb;
+    const int nqb_grid = (xord & 1) ? (nqb + 7) / 8 * 8 : nqb;   // (bit 1: keep-zero, KNN_KARG_KEEP0)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dist_split<T, KL, D>), dim3((unsigned)(nqb_grid * nsplit)), dim3(512), 0, s,
                        (const char *)qsp, qnorm, q_base, nq, cb, n, rsb, nsplit, nqb, meta, part_d, part_i, part_T,
                        nq_pad, (unsigned long long *)qthr, uj, xord, m2s);

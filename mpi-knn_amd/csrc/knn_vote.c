@@ -16,8 +16,10 @@
 #include <stdlib.h>
 #include <string.h>
 
-int knn_classify(const knn_neighbour_t *nb, size_t m, int k, int nclasses, int vote_rule,
-                 const double *labels, int *pred, size_t *matches)
+/* m queries' votes over `labels` (nlabels of them; 0: unchecked, as the
+ * reference reads them); qlabels (nullable): the queries' own labels */
+static int vote(const knn_neighbour_t *nb, size_t m, int k, int nclasses, int vote_rule,
+                const double *labels, size_t nlabels, const double *qlabels, int *pred, size_t *matches)
 {
     if (!nb || !labels || k <= 0 || nclasses <= 0 || nclasses > 65536) return KNN_ERR_INVALID;
     if (vote_rule != KNN_VOTE_SERIAL && vote_rule != KNN_VOTE_MPI &&
@@ -30,7 +32,7 @@ int knn_classify(const knn_neighbour_t *nb, size_t m, int k, int nclasses, int v
         const knn_neighbour_t *L = nb + q * (size_t)k;
         memset(cls, 0, (size_t)nclasses * sizeof(int));          /* serial:114 */
         for (int i = 0; i < k; i++) {                             /* serial:116-119 */
-            if (L[i].idx <= 0) continue;                             /* empty slot */
+            if (L[i].idx <= 0 || (nlabels && (size_t)L[i].idx > nlabels)) continue;   /* empty slot */
             const int lab = (int)labels[L[i].idx - 1];
             if (lab >= 1 && lab <= nclasses) cls[lab - 1]++;      /* F6: no class[-1] */
         }
@@ -40,7 +42,7 @@ int knn_classify(const knn_neighbour_t *nb, size_t m, int k, int nclasses, int v
             for (int j = 0; j < nclasses; j++)
                 if (cls[j] > best) best = cls[j];
             for (int i = 0; i < k && best > 0; i++) {
-                if (L[i].idx <= 0) continue;
+                if (L[i].idx <= 0 || (nlabels && (size_t)L[i].idx > nlabels)) continue;
                 const int lab = (int)labels[L[i].idx - 1];
                 if (lab >= 1 && lab <= nclasses && cls[lab - 1] == best) {
                     most = lab;
@@ -48,17 +50,33 @@ int knn_classify(const knn_neighbour_t *nb, size_t m, int k, int nclasses, int v
                 }
             }
         } else {
-            const int nn0 = L[0].idx > 0 ? (int)labels[L[0].idx - 1] : 0;
+            const int nn0 = (L[0].idx > 0 && !(nlabels && (size_t)L[0].idx > nlabels)) ? (int)labels[L[0].idx - 1] : 0;
             const int tie = vote_rule == KNN_VOTE_MPI ? nn0 - 1 : nn0;  /* blk:265 vs serial:123 */
             for (int j = 0; j < nclasses; j++)                          /* serial:121-124 */
                 if (cls[j] > most || ((cls[j] == most) && ((j + 1) == tie))) most = j + 1;
         }
         if (pred) pred[q] = most;
-        if (most == labels[q]) hit++;                             /* serial:126-127 */
+        if (qlabels && most == qlabels[q]) hit++;                 /* serial:126-127 */
     }
     free(cls);
     if (matches) *matches = hit;
     return KNN_OK;
+}
+
+int knn_classify(const knn_neighbour_t *nb, size_t m, int k, int nclasses, int vote_rule,
+                 const double *labels, int *pred, size_t *matches)
+{
+    return vote(nb, m, k, nclasses, vote_rule, labels, 0, labels, pred, matches);
+}
+
+/* The vote of out-of-sample queries (knn_query's records): neighbours are
+ * corpus rows 1..m with labels[idx - 1], the prediction is compared with
+ * qlabels[q] (NULL: *matches = 0, only pred is written). */
+int knn_classify_query(const knn_neighbour_t *nb, size_t mq, int k, int nclasses, int vote_rule,
+                       const double *labels, size_t m, const double *qlabels, int *pred, size_t *matches)
+{
+    if (m == 0) return KNN_ERR_INVALID;
+    return vote(nb, mq, k, nclasses, vote_rule, labels, m, qlabels, pred, matches);
 }
 
 /* The same stage on device-resident records (k_vote in knn_kernels.hip):

@@ -49,7 +49,7 @@ API_SYMBOLS = (
     "knn_ctx_shadow_pack", "knn_ctx_step_shadow_n", "knn_ctx_split", "knn_s8_block_bytes",
     "knn_s8_block_meta_offset", "knn_block_pack_s8", "knn_s8_spec_ok", "knn_ctx_begin_s8",
     "knn_ctx_attach_qblock", "knn_ctx_research_blocks", "knn_ctx_step_n", "knn_ctx_profile_merge",
-    "knn_ctx_set_solo", "knn_ctx_search_meta",
+    "knn_ctx_set_solo", "knn_ctx_search_meta", "knn_query", "knn_classify_query", "knn_ctx_set_keep_zero",
 )
 DTYPES = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 
@@ -136,6 +136,9 @@ def _load():
         "knn_ctx_attach_qblock": ([p, p, sz], i),
         "knn_ctx_research_blocks": ([p, i, pp, psz, psz, p, psz, p], i),
         "knn_ctx_step_n": ([p, i, pp, psz, psz, p], i),
+        "knn_query": ([p, sz, p, sz, sz, i, p, i, i, i, p], i),
+        "knn_classify_query": ([p, sz, i, i, i, p, sz, p, p, psz], i),
+        "knn_ctx_set_keep_zero": ([p, i], i),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -206,6 +209,50 @@ def search(X, k=30, ngpus=1, labels=None, layout="row", dtype="f64"):
     rc = lib.knn_search(_ptr(buf), m, n, lay, _ptr(lab), k, ngpus, DTYPES[dtype], _ptr(out))
     _check(rc, "knn_search")
     return out, lib.knn_last_search_seconds()
+
+
+QUERY_KEEP_ZERO = 1  # KNN_QUERY_KEEP_ZERO
+
+
+def query(X, Q, k=30, labels=None, layout="row", dtype="f64", keep_zero=True):
+    """knn_query: the k nearest corpus rows (of X, (m, n)) of every row of Q
+    ((mq, n)) -- queries that are no part of the corpus (blk:217-242 with a
+    foreign query block).  keep_zero=True returns a corpus row equal to the
+    query at distance 0.0; False keeps the reference's rule (zero distances
+    excluded).  idx is the 1-based corpus row; labels ((m,), optional) fill
+    .label.  Returns (neighbours (mq, k) NB_DTYPE, search seconds)."""
+    X = np.asarray(X, dtype=np.float64)
+    Q = np.asarray(Q, dtype=np.float64)
+    m, n = X.shape
+    mq = Q.shape[0]
+    if Q.ndim != 2 or Q.shape[1] != n:
+        raise ValueError("Q must be (mq, %d), got %r" % (n, Q.shape))
+    if layout == "col":
+        xb, qb, lay = np.asfortranarray(X), np.asfortranarray(Q), COLMAJOR
+    else:
+        xb, qb, lay = np.ascontiguousarray(X), np.ascontiguousarray(Q), ROWMAJOR
+    out = np.zeros((mq, k), dtype=NB_DTYPE)
+    lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.float64)
+    rc = lib.knn_query(_ptr(xb), m, _ptr(qb), mq, n, lay, _ptr(lab), k, DTYPES[dtype],
+                       QUERY_KEEP_ZERO if keep_zero else 0, _ptr(out))
+    _check(rc, "knn_query")
+    return out, lib.knn_last_search_seconds()
+
+
+def classify_query(nb, labels, qlabels=None, nclasses=10, rule=VOTE_SERIAL):
+    """knn_classify_query: the vote of query()'s records over the corpus
+    labels; matches counts predictions equal to qlabels (0 without them).
+    Returns (pred, matches)."""
+    nb = np.ascontiguousarray(nb)
+    mq, k = nb.shape
+    lab = np.ascontiguousarray(labels, dtype=np.float64)
+    ql = None if qlabels is None else np.ascontiguousarray(qlabels, dtype=np.float64)
+    pred = np.zeros(mq, dtype=np.int32)
+    matches = ctypes.c_size_t()
+    rc = lib.knn_classify_query(_ptr(nb), mq, k, nclasses, rule, _ptr(lab), lab.shape[0], _ptr(ql),
+                                _ptr(pred), ctypes.byref(matches))
+    _check(rc, "knn_classify_query")
+    return pred, matches.value
 
 
 def search_mpi_compat(X, k=30, procs=2, labels=None, layout="row"):
@@ -451,6 +498,11 @@ class Context:
     def set_solo(self, on):
         """knn_ctx_set_solo: one-step searches (P = 1) on the caller's stream."""
         _check(lib.knn_ctx_set_solo(self._h, 1 if on else 0), "knn_ctx_set_solo")
+
+    def set_keep_zero(self, on):
+        """knn_ctx_set_keep_zero: S == 0 candidates are results (searches
+        begun after the call)."""
+        _check(lib.knn_ctx_set_keep_zero(self._h, 1 if on else 0), "knn_ctx_set_keep_zero")
 
     def search_meta(self):
         """knn_ctx_search_meta: the meta the last search's kernels read."""
