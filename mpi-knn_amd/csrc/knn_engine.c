@@ -67,16 +67,20 @@ struct knn_ctx {
     double *pp_T[KNN_PSETS / 2];
     int pp_cap[KNN_PSETS / 2];        /* splits per pair allocation */
     size_t pp_per[KNN_PSETS / 2];     /* list entries per split it was sized for */
-    /* an even step whose merge waits for the next step (pairing) */
-    int pend, pend_set, pend_nsplit, pend_nc, merged;
-    /* a paired merge of a fused step, deferred to the next step or to
-     * knn_ctx_end (which then merges and finalizes in one launch) */
-    int pend2, pend2_set, pend2_nsplit;
-    hipEvent_t *pend2_ev[2];
+    /* The merge that waits: the lists of `sets` consecutive partial sets from
+     * `set` on, `nsplit` splits in all.  One set: an even step whose merge the
+     * next step may share (pairing); that step merges it alone otherwise.
+     * Two sets: a fused step and its pending partner, always flushed first by
+     * the next step or by knn_ctx_end (which then merges and finalizes in one
+     * launch). */
+    struct {
+        int sets, set, nsplit;
+        knn_merge_blocks_t mb;        /* the block(s) the merge re-ranks from */
+        size_t rows;                  /* their rows (want_order) */
+        hipEvent_t *ev[2];            /* the steps' profiling events to close */
+    } def;
+    int merged;
     int even_nsplit;                  /* splits of the last even step: the odd set's offset */
-    const void *pend_cblk;
-    size_t pend_cbase;
-    hipEvent_t *pend_ev;
     /* overlapped step schedule (knn_ctx_step): distance kernels alternate
      * over two streams, merges run in order on a third */
     hipStream_t ds[2], ms;
@@ -659,6 +663,19 @@ static float knn_split_scale(const double *meta, size_t n, int dtype)
     return (float)ldexp(1.0, 14 - e);
 }
 
+/* a conversion buffer of at least `need` bytes (its last reader is on `stream`) */
+static int grow_buffer(void **buf, size_t *have, size_t need, void *stream)
+{
+    if (need <= *have) return KNN_OK;
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    hipFree(*buf);
+    *buf = NULL;
+    *have = 0;
+    if (hipMalloc(buf, need) != hipSuccess) return KNN_ERR_NOMEM;
+    *have = need;
+    return KNN_OK;
+}
+
 /* d_s8: the query block as a byte block already (knn_block_pack_s8, valid by
  * knn_s8_spec_ok); d_qblock is then NULL until knn_ctx_attach_qblock */
 static int ctx_begin(knn_ctx_t *c, const void *d_qblock, const void *d_s8, size_t q_cap, size_t q_base,
@@ -677,9 +694,7 @@ static int ctx_begin(knn_ctx_t *c, const void *d_qblock, const void *d_s8, size_
         c->solo_on = 0;
     }
     c->nstep = 0;
-    c->pend = 0;
-    c->pend_nsplit = 0;
-    c->pend2 = 0;
+    c->def.sets = 0;
     c->even_nsplit = 0;
     c->merged = 0;
     c->nfail = 0;
@@ -729,37 +744,16 @@ static int ctx_begin(knn_ctx_t *c, const void *d_qblock, const void *d_s8, size_
         c->q8 = d_s8;   /* the caller's byte block: no conversion */
     } else if (c->i8) {
         const size_t need = knn_s8_bytes(q_cap, c->n);
-        if (need > c->qs8_bytes) {
-            HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-            hipFree(c->qs8);
-            c->qs8 = NULL;
-            c->qs8_bytes = 0;
-            if (hipMalloc(&c->qs8, need) != hipSuccess) return KNN_ERR_NOMEM;
-            c->qs8_bytes = need;
-        }
+        RCHK(grow_buffer(&c->qs8, &c->qs8_bytes, need, stream));
         RCHK(knn_launch_shadow8(c->qs8, d_qblock, c->dtype, c->q_rows_pad, c->n, d_meta, stream));
         c->q8 = c->qs8;
     } else if (c->split) {
         const size_t need = c->q_rows_pad * knn_split_rs(c->n);
-        if (need > c->qsp_bytes) {
-            HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-            hipFree(c->qsp);
-            c->qsp = NULL;
-            c->qsp_bytes = 0;
-            if (hipMalloc(&c->qsp, need) != hipSuccess) return KNN_ERR_NOMEM;
-            c->qsp_bytes = need;
-        }
+        RCHK(grow_buffer(&c->qsp, &c->qsp_bytes, need, stream));
         RCHK(knn_launch_shadow_split(c->qsp, d_qblock, c->dtype, c->q_rows_pad, c->n, c->sscale, stream));
     } else if (c->shadow) {
         const size_t need = c->q_rows_pad * knn_round_up(c->n, 64) * 2;
-        if (need > c->qsh_bytes) {
-            HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-            hipFree(c->qsh);
-            c->qsh = NULL;
-            c->qsh_bytes = 0;
-            if (hipMalloc(&c->qsh, need) != hipSuccess) return KNN_ERR_NOMEM;
-            c->qsh_bytes = need;
-        }
+        RCHK(grow_buffer(&c->qsh, &c->qsh_bytes, need, stream));
         RCHK(knn_launch_shadow(c->qsh, d_qblock, c->dtype, c->q_rows_pad, c->n, stream));
     }
     /* fail_count and mode_dev are one allocation: one launch resets both,
@@ -1011,6 +1005,17 @@ static int choose_splits(knn_ctx_t *c, size_t nc)
     return split_cache_put(c, nc, best);
 }
 
+static void free_pair(knn_ctx_t *c, int pr)
+{
+    hipFree(c->pp_d[pr]);
+    hipFree(c->pp_i[pr]);
+    hipFree(c->pp_T[pr]);
+    c->pp_d[pr] = NULL;
+    c->pp_i[pr] = NULL;
+    c->pp_T[pr] = NULL;
+    c->pp_cap[pr] = 0;
+}
+
 /* Partial lists of set `set` for nsplit splits.  Even set: the pair
  * allocation grows to 2*nsplit splits (room for an odd step of the same
  * size behind it).  Odd set: right behind the even set's `off` splits,
@@ -1022,28 +1027,16 @@ static int ensure_part_buffers(knn_ctx_t *c, int nsplit, int set, int off)
     const size_t per = c->nq_pad * (size_t)c->lpq * c->klx;
     if (per != c->pp_per[pr]) {
         /* list shape changed (another kernel): the old sets hold nothing pending */
-        if (c->pend) return KNN_ERR_INVALID;
+        if (c->def.sets) return KNN_ERR_INVALID;
         if (c->pp_cap[pr]) HIPCHK(hipStreamSynchronize(c->ms));
-        hipFree(c->pp_d[pr]);
-        hipFree(c->pp_i[pr]);
-        hipFree(c->pp_T[pr]);
-        c->pp_d[pr] = NULL;
-        c->pp_i[pr] = NULL;
-        c->pp_T[pr] = NULL;
-        c->pp_cap[pr] = 0;
+        free_pair(c, pr);
         c->pp_per[pr] = per;
     }
     if (need > c->pp_cap[pr]) {
-        if ((set & 1) && c->pend) return KNN_ERR_INVALID;   /* caller merges first */
+        if ((set & 1) && c->def.sets) return KNN_ERR_INVALID;   /* caller merges first */
         /* the pair may still be read by an earlier step's merge */
         HIPCHK(hipStreamSynchronize(c->ms));
-        hipFree(c->pp_d[pr]);
-        hipFree(c->pp_i[pr]);
-        hipFree(c->pp_T[pr]);
-        c->pp_d[pr] = NULL;
-        c->pp_i[pr] = NULL;
-        c->pp_T[pr] = NULL;
-        c->pp_cap[pr] = 0;
+        free_pair(c, pr);
         const int cap = need > 2 * nsplit ? need : 2 * nsplit;
         if (hipMalloc((void **)&c->pp_d[pr], (size_t)cap * per * sizeof(double)) != hipSuccess ||
             hipMalloc((void **)&c->pp_i[pr], (size_t)cap * per * sizeof(int)) != hipSuccess ||
@@ -1110,8 +1103,8 @@ static int find_order(knn_ctx_t *c, int set, int nsplit)
 
 /* fin_out: the search's last merge -- with the rank merge it finalizes
  * too (records into fin_out, *finalized = 1) */
-static int launch_merge_sets_fin(knn_ctx_t *c, int set, int nsets, int nsplit_total, const void *cblk,
-                                 size_t c_base, size_t nc, knn_neighbour_t *fin_out, int *finalized)
+static int launch_merge_sets_fin(knn_ctx_t *c, int set, int nsets, int nsplit_total, const knn_merge_blocks_t *mb,
+                                 size_t rows, knn_neighbour_t *fin_out, int *finalized)
 {
     if (finalized) *finalized = 0;
     hipEvent_t *mk = NULL;
@@ -1145,14 +1138,14 @@ static int launch_merge_sets_fin(knn_ctx_t *c, int set, int nsets, int nsplit_to
         if (fin_out && finalized) *finalized = 1;
     } else {
         const int *perm = NULL;
-        if (want_order(c, nc)) {
+        if (want_order(c, rows)) {
             if (!c->ord_ready) RCHK(find_order(c, set, nsplit_total));
             perm = c->ord_perm;
         }
-        RCHK(knn_launch_merge(c->dtype, c->kp, c->k, c->part_d[set], c->part_i[set], c->part_T[set],
-                              nsplit_total, c->lpq, c->klx, (int)c->nq, (int)c->nq_pad, !c->merged, c->st_d, c->st_x,
-                              c->st_i, c->st_T, c->qblk, c->q_rows_pad, cblk, c_base, (int)nc, (int)c->n,
-                              c->meta, c->qthr, c->split | kz_bit(c), perm, c->ms));
+        RCHK(knn_launch_merge_n(c->dtype, c->kp, c->k, c->part_d[set], c->part_i[set], c->part_T[set],
+                                nsplit_total, c->lpq, c->klx, (int)c->nq, (int)c->nq_pad, !c->merged, c->st_d,
+                                c->st_x, c->st_i, c->st_T, c->qblk, c->q_rows_pad, mb, (int)c->n, c->meta, c->qthr,
+                                c->split | kz_bit(c), perm, c->ms));
     }
     if (mk) HIPCHK(hipEventRecord(mk[1], c->ms));
     c->merged = 1;
@@ -1163,37 +1156,19 @@ static int launch_merge_sets_fin(knn_ctx_t *c, int set, int nsets, int nsplit_to
     return KNN_OK;
 }
 
-static int launch_merge_sets(knn_ctx_t *c, int set, int nsets, int nsplit_total, const void *cblk,
-                             size_t c_base, size_t nc)
-{
-    return launch_merge_sets_fin(c, set, nsets, nsplit_total, cblk, c_base, nc, NULL, NULL);
-}
-
-/* the deferred merge of a fused step and its pending partner */
-static int flush_pend2(knn_ctx_t *c, knn_neighbour_t *fin_out, int *finalized)
+/* The merge that waits (c->def), now: its lists in one launch, its steps'
+ * profiling events closed behind it. */
+static int flush_deferred(knn_ctx_t *c, knn_neighbour_t *fin_out, int *finalized)
 {
     if (finalized) *finalized = 0;
-    if (!c->pend2) return KNN_OK;
-    c->pend2 = 0;
-    RCHK(launch_merge_sets_fin(c, c->pend2_set, 2, c->pend2_nsplit, NULL, 0, 0, fin_out, finalized));
-    for (int x = 0; x < 2; x++)
-        if (c->pend2_ev[x]) HIPCHK(hipEventRecord(c->pend2_ev[x][2], c->ms));
+    const int nsets = c->def.sets;
+    if (!nsets) return KNN_OK;
+    c->def.sets = 0;
+    RCHK(launch_merge_sets_fin(c, c->def.set, nsets, c->def.nsplit, &c->def.mb, c->def.rows, fin_out, finalized));
+    for (int x = 0; x < nsets; x++)
+        if (c->def.ev[x]) HIPCHK(hipEventRecord(c->def.ev[x][2], c->ms));
     return KNN_OK;
 }
-
-/* merge the pending even step by itself */
-static int merge_pending_fin(knn_ctx_t *c, knn_neighbour_t *fin_out, int *finalized)
-{
-    if (finalized) *finalized = 0;
-    if (!c->pend) return KNN_OK;
-    c->pend = 0;
-    RCHK(launch_merge_sets_fin(c, c->pend_set, 1, c->pend_nsplit, c->pend_cblk, c->pend_cbase,
-                               (size_t)c->pend_nc, fin_out, finalized));
-    if (c->pend_ev) HIPCHK(hipEventRecord(c->pend_ev[2], c->ms));
-    return KNN_OK;
-}
-
-static int merge_pending(knn_ctx_t *c) { return merge_pending_fin(c, NULL, NULL); }
 
 /* Step schedule.  Step s runs k_dist_topk on stream ds[s % 2] into partial
  * set p = s % 4 and k_merge on stream ms (high priority), in step order:
@@ -1213,6 +1188,172 @@ static int merge_pending(knn_ctx_t *c) { return merge_pending_fin(c, NULL, NULL)
  * enqueues after step s returns is ordered after step s-2 only, so a ring
  * rotates KNN_STEP_LAG + 2 receive buffers (knn.h).  knn_ctx_end joins
  * all. */
+/* One step, as its helpers hand it on: step_open chooses, step_enter orders
+ * the distance stream, the step itself converts and launches between
+ * step_prof and step_close, which merges or defers. */
+typedef struct {
+    int set, nsplit;
+    int fused;            /* several blocks in one launch */
+    int can_pair;         /* an even step of this size may wait for the next one's merge */
+    int pair;             /* shares its merge with the pending even step before it */
+    int solo;             /* runs on the caller's stream (step_enter) */
+    hipStream_t cs, ds;   /* the caller's stream, the distance kernel's */
+    hipEvent_t *ev;       /* the step's three profiling events, or NULL */
+} knn_step_t;
+
+/* Step open: the splits of a launch over nc rows, its partial set and
+ * streams, and what becomes of a merge that waits.  nblk: the blocks this
+ * step's merge re-ranks from. */
+static int step_open(knn_ctx_t *c, knn_step_t *st, size_t nc, int fused, int nblk, void *stream)
+{
+    HIPCHK(hipSetDevice(c->device));
+    if (c->def.sets == 2) RCHK(flush_deferred(c, NULL, NULL));   /* a deferred merge goes first, in step order */
+    memset(st, 0, sizeof(*st));
+    const int nsplit = choose_splits(c, nc);
+    const int set = c->nstep % KNN_PSETS;
+    st->set = set;
+    st->nsplit = nsplit;
+    st->fused = fused;
+    st->cs = (hipStream_t)stream;
+    st->ds = c->ds[c->nstep & 1];
+    c->nsplit_last = nsplit;
+    /* pairing: in exact-integer (fp16) searches two consecutive steps share
+     * one k_merge (8*nsplit + 1 <= 64 lists; INT mode never reads the
+     * block rows in k_merge) -- half the merges, which at P = 8 cost about
+     * as much as the contraction. */
+    st->can_pair = (c->h16 || c->i8) && 2 * c->lpq * nsplit + 1 <= 64;
+    if (c->def.sets) {   /* (one set: the even step right before this one) */
+        /* a fused step behind a pending single-block step (the direct exchange:
+         * own block, then the received ones) shares its merge when the lists fit
+         * one merge wave (a split-filter one: and the block table): the own
+         * block's merge could not run beside the fused
+         * launch anyway (every CU holds a distance workgroup; measured: the
+         * merge ran on the ~20 CUs the fused launch left idle and ended after
+         * it), so pairing drops a launch and its starved tail */
+        const int fit = c->lpq * (c->def.nsplit + nsplit) + 1 <= 64;
+        if (c->split) st->pair = fused && fit && nblk + 1 <= KNN_SPLIT_MAXBLK;
+        else st->pair = fused ? fit : (st->can_pair && nsplit == c->def.nsplit);
+        if (!st->pair) RCHK(flush_deferred(c, NULL, NULL));
+    }
+    if (!(set & 1)) c->even_nsplit = nsplit;
+    const int rc0 = ensure_part_buffers(c, nsplit, set, c->even_nsplit);
+    if (rc0 == KNN_ERR_INVALID && c->def.sets) {
+        /* the pair's lists cannot grow under the pending step's: merge it
+         * alone first */
+        RCHK(flush_deferred(c, NULL, NULL));
+        st->pair = 0;
+        RCHK(ensure_part_buffers(c, nsplit, set, c->even_nsplit));
+    } else if (rc0) {
+        return rc0;
+    }
+    if (c->solo_on) {
+        /* a second step after a solo first one: back to the step schedule
+         * (step 0's kernel ran on the caller's stream; its merge is pending
+         * and will run on the merge stream) */
+        HIPCHK(hipEventRecord(c->ev_ds[0], (hipStream_t)c->ms));
+        HIPCHK(hipStreamWaitEvent(c->ms_keep, c->ev_ds[0], 0));
+        c->ms = c->ms_keep;
+        c->solo_on = 0;
+    }
+    return KNN_OK;
+}
+
+/* Stream entry: the distance stream behind the caller's stream and behind
+ * the last reader of its partial set. */
+static int step_enter(knn_ctx_t *c, knn_step_t *st)
+{
+    /* a solo search (one block, one step: P = 1): the distance kernel on the
+     * caller's stream, its merge behind it there -- no event record or
+     * stream wait between pack, kernel and merge (each a queue packet of
+     * 5-20 us, rocprofv3) */
+    st->solo = c->solo && c->nstep == 0 && !st->fused;
+    if (st->solo) {
+        st->ds = st->cs;
+        c->ms_keep = c->ms;
+        c->ms = st->cs;
+        c->solo_on = 1;
+    } else {
+        HIPCHK(hipEventRecord(c->ev_in, st->cs));
+        HIPCHK(hipStreamWaitEvent(st->ds, c->ev_in, 0));
+    }
+    if (c->nstep >= KNN_PSETS) HIPCHK(hipStreamWaitEvent(st->ds, c->ev_m[st->set], 0));
+    return KNN_OK;
+}
+
+/* the step's profiling events: [0] here, in front of the distance kernel,
+ * [1] behind it (step_close), [2] behind its merge (flush_deferred) */
+static int step_prof(knn_ctx_t *c, knn_step_t *st)
+{
+    if (c->prof_on && c->prof_pending < KNN_PROF_STEPS) {
+        st->ev = &c->prof_ev[3 * c->prof_pending++];
+        HIPCHK(hipEventRecord(st->ev[0], st->ds));
+    }
+    return KNN_OK;
+}
+
+/* Step close, behind the distance launch: its event, then the step's merge
+ * -- over mb (`rows` rows), now, or with the pending even step's, or (hold:
+ * an even step that may be paired) waiting for the next step -- and the
+ * caller's lag wait. */
+static int step_close(knn_ctx_t *c, knn_step_t *st, const knn_merge_blocks_t *mb, size_t rows, int hold)
+{
+    if (st->ev) HIPCHK(hipEventRecord(st->ev[1], st->ds));
+    /* one event a step behind its distance kernel (each record is a marker
+     * packet on the queue, ~5 us before whatever follows it there): the
+     * merge stream, the caller's lag wait and knn_ctx_end all use ev_ds.
+     * (The distance kernel waited for ev_in: ev_ds covers the block's
+     * arrival too -- a second wait would add its own latency) */
+    if (!st->solo) {
+        HIPCHK(hipEventRecord(c->ev_ds[st->set], st->ds));
+        HIPCHK(hipStreamWaitEvent(c->ms, c->ev_ds[st->set], 0));
+    }
+    if (st->pair) {
+        /* the pending even step (step s - 1, on the other distance stream) */
+        HIPCHK(hipStreamWaitEvent(c->ms, c->ev_ds[(st->set + KNN_PSETS - 1) % KNN_PSETS], 0));
+        /* one merge of both steps: the pending set's lists, then this one's,
+         * re-ranking from this step's blocks and then (the split filter's
+         * GEMM mode; an exact-integer merge reads no block rows) the pending
+         * step's */
+        knn_merge_blocks_t both = *mb;
+        if (c->split) {
+            both.ptr[both.nblk] = c->def.mb.ptr[0];
+            both.base[both.nblk] = c->def.mb.base[0];
+            both.nc[both.nblk] = c->def.mb.nc[0];
+            both.nblk++;
+        }
+        c->def.sets = 2;
+        c->def.nsplit += st->nsplit;
+        c->def.mb = both;
+        c->def.rows += rows;
+        c->def.ev[1] = st->ev;
+        /* the fused step (the direct exchange's last): its merge waits
+         * for the next call -- knn_ctx_end merges and finalizes in one
+         * launch (a separate k_finalize cost its launch and ~20 us of
+         * queue gap, rocprofv3) */
+        hold = st->fused && rank_merge_ok(c, c->def.nsplit);
+    } else {
+        c->def.sets = 1;
+        c->def.set = st->set;
+        c->def.nsplit = st->nsplit;
+        c->def.mb = *mb;
+        c->def.rows = rows;
+        c->def.ev[0] = st->ev;
+        c->def.ev[1] = NULL;
+    }
+    if (!hold) RCHK(flush_deferred(c, NULL, NULL));
+    /* step s - 2 is merged by now (a pending step is always s itself); the
+     * exact-integer contractions wait for its distance kernel alone (Step
+     * schedule, above) */
+    if (c->nstep >= KNN_STEP_LAG) {
+        const int ps = (c->nstep - KNN_STEP_LAG) % KNN_PSETS;
+        HIPCHK(hipStreamWaitEvent(st->cs, (c->i8 || c->h16) ? c->ev_ds[ps] : c->ev_m[ps], 0));
+    }
+    c->first_step = 0;
+    c->ended = 0;
+    c->nstep++;
+    return KNN_OK;
+}
+
 /* d_sblock: a shadow block (knn_shadow_pack) used in place of d_cblock.
  * xb (int8 contraction only, byte blocks): further byte blocks folded by the
  * same launch -- xb->ptr[0..nblk) with the rows / bases beside them, in any
@@ -1251,80 +1392,12 @@ static int ctx_step_impl(knn_ctx_t *c, const void *d_cblock, const void *d_sbloc
     }
     if (d_sblock && !c->shadow) return KNN_ERR_INVALID;
     if (!d_cblock) d_cblock = d_sblock;   /* INT mode: k_merge never reads its rows */
-    HIPCHK(hipSetDevice(c->device));
-    RCHK(flush_pend2(c, NULL, NULL));   /* a deferred merge goes first, in step order */
     c->split_solo = c->i8 && c->nstep == 0 && !xb && d_sblock != NULL && d_sblock == c->q8 && nc == c->nq;
-    int nsplit = choose_splits(c, nc);
-    const int set = c->nstep % KNN_PSETS, ds_i = c->nstep & 1;
-    c->nsplit_last = nsplit;
-    /* pairing: in exact-integer (fp16) searches two consecutive steps share
-     * one k_merge (8*nsplit + 1 <= 64 lists; INT mode never reads the
-     * block rows in k_merge) -- half the merges, which at P = 8 cost about
-     * as much as the contraction. */
-    const int can_pair = (c->h16 || c->i8) && 2 * c->lpq * nsplit + 1 <= 64;
-    /* a fused step behind a pending single-block step (the direct exchange:
-     * own block, then the received ones) shares its merge when the lists fit
-     * one merge wave: the own block's merge could not run beside the fused
-     * launch anyway (every CU holds a distance workgroup; measured: the
-     * merge ran on the ~20 CUs the fused launch left idle and ended after
-     * it), so pairing drops a launch and its starved tail */
-    const int pair_fused = xb && c->pend && (set & 1) && c->lpq * (c->pend_nsplit + nsplit) + 1 <= 64;
-    /* a fused step (the direct exchange's received blocks) is never paired:
-     * the previous step's merge runs beside it and publishes the (k+1)-th
-     * d^2 of the blocks folded so far into qthr, which the fused launch's
-     * workgroups re-read as they go (k_dist_topk_i8), so most of the rank's
-     * work filters with the running answer instead of cold lane lists
-     * (making the launch wait for that merge measured no faster, DESIGN.md
-     * sec.5). */
-    /* a split-filter (GEMM) search's first step on its own query block keeps
-     * its merge pending: the direct exchange's fused step (knn_ctx_step_n)
-     * merges both in one k_merge over a table of all their blocks -- the
-     * own block's merge could not run beside the fused launch anyway (its
-     * workgroups hold every register of every CU), so it ran alone after
-     * it; any other next step merges it first, as a single merge */
-    const int gemm_own = c->split && !xb && c->nstep == 0 && d_cblock == c->qblk;
-    int pairing = 0;
-    if ((set & 1) && c->pend) {
-        pairing = (can_pair && nsplit == c->pend_nsplit && !xb) || pair_fused;
-        if (!pairing) RCHK(merge_pending(c));
-    }
-    {
-        if (!(set & 1)) c->even_nsplit = nsplit;
-        const int rc0 = ensure_part_buffers(c, nsplit, set, c->even_nsplit);
-        if (rc0 == KNN_ERR_INVALID && c->pend) {
-            RCHK(merge_pending(c));
-            pairing = 0;
-            RCHK(ensure_part_buffers(c, nsplit, set, c->even_nsplit));
-        } else if (rc0) {
-            return rc0;
-        }
-    }
-    const void *cblk = d_cblock;
-    hipStream_t cs = (hipStream_t)stream, ds = c->ds[ds_i];
-    if (c->solo_on) {
-        /* a second step after a solo first one: back to the step schedule
-         * (step 0's kernel ran on the caller's stream; its merge is pending
-         * and will run on the merge stream) */
-        HIPCHK(hipEventRecord(c->ev_ds[0], (hipStream_t)c->ms));
-        HIPCHK(hipStreamWaitEvent(c->ms_keep, c->ev_ds[0], 0));
-        c->ms = c->ms_keep;
-        c->solo_on = 0;
-    }
-    /* a solo search (one block, one step: P = 1): the distance kernel on the
-     * caller's stream, its merge behind it there -- no event record or
-     * stream wait between pack, kernel and merge (each a queue packet of
-     * 5-20 us, rocprofv3) */
-    const int solo = c->solo && c->nstep == 0 && !xb;
-    if (solo) {
-        ds = cs;
-        c->ms_keep = c->ms;
-        c->ms = cs;
-        c->solo_on = 1;
-    } else {
-        HIPCHK(hipEventRecord(c->ev_in, cs));
-        HIPCHK(hipStreamWaitEvent(ds, c->ev_in, 0));
-    }
-    if (c->nstep >= KNN_PSETS) HIPCHK(hipStreamWaitEvent(ds, c->ev_m[set], 0));
+    knn_step_t st;
+    RCHK(step_open(c, &st, nc, xb != NULL, 1, stream));
+    RCHK(step_enter(c, &st));
+    const int set = st.set, nsplit = st.nsplit;
+    hipStream_t ds = st.ds;
     const void *csh = d_sblock, *cn_ptr = NULL;
     if (c->i8) {
         if (!d_sblock && d_cblock == c->qblk && knn_rows_pad(c->block_cap) == c->q_rows_pad) {
@@ -1368,11 +1441,7 @@ static int ctx_step_impl(knn_ctx_t *c, const void *d_cblock, const void *d_sbloc
         RCHK(knn_launch_shadow(c->csh[set], d_cblock, c->dtype, knn_rows_pad(nc), c->n, ds));
         csh = c->csh[set];
     }
-    hipEvent_t *ev = NULL;
-    if (c->prof_on && c->prof_pending < KNN_PROF_STEPS) {
-        ev = &c->prof_ev[3 * c->prof_pending++];
-        HIPCHK(hipEventRecord(ev[0], ds));
-    }
+    RCHK(step_prof(c, &st));
     if (c->i8) {
         c->one_block_q8 = c->nstep == 0 && !xb && csh == c->q8;
         c->step0_nc = nc;
@@ -1389,63 +1458,27 @@ static int ctx_step_impl(knn_ctx_t *c, const void *d_cblock, const void *d_sbloc
                                 c->qsum, c->kz, ds));
     } else
         RCHK(knn_launch_dist_topk(c->dtype, c->kp, c->k, c->qblk, c->q_rows_pad, c->q_base, (int)c->nq,
-                                  cblk, knn_rows_pad(c->block_cap), c_base, (int)nc, (int)c->n, c->meta,
+                                  d_cblock, knn_rows_pad(c->block_cap), c_base, (int)nc, (int)c->n, c->meta,
                                   nsplit, c->part_d[set], c->part_i[set], c->part_T[set], (int)c->nq_pad,
                                   c->qthr, c->split ? c->qsp : c->qsh, csh, cn_ptr,
                                   (xord_for(c, nsplit) ? KNN_DIST_XORD : 0) | (c->h16 ? KNN_DIST_H16 : 0) |
                                       (c->shadow ? KNN_DIST_SHADOW : 0) | (c->split ? KNN_DIST_SPLIT : 0) |
                                       (c->kz ? KNN_DIST_KEEP0 : 0),
                                   c->split ? (float)(-2.0 / ((double)c->sscale * c->sscale)) : -2.f, ds));
-    if (ev) HIPCHK(hipEventRecord(ev[1], ds));
-    /* one event a step behind its distance kernel (each record is a marker
-     * packet on the queue, ~5 us before whatever follows it there): the
-     * merge stream, the caller's lag wait and knn_ctx_end all use ev_ds.
-     * (The distance kernel waited for ev_in: ev_ds covers the block's
-     * arrival too -- a second wait would add its own latency) */
-    if (!solo) {
-        HIPCHK(hipEventRecord(c->ev_ds[set], ds));
-        HIPCHK(hipStreamWaitEvent(c->ms, c->ev_ds[set], 0));
-    }
-    if (pairing) {
-        /* the pending even step (step s - 1, on the other distance stream) */
-        HIPCHK(hipStreamWaitEvent(c->ms, c->ev_ds[(set + KNN_PSETS - 1) % KNN_PSETS], 0));
-        c->pend = 0;
-        if (xb && rank_merge_ok(c, c->pend_nsplit + nsplit)) {
-            /* the fused step (the direct exchange's last): its merge waits
-             * for the next call -- knn_ctx_end merges and finalizes in one
-             * launch (a separate k_finalize cost its launch and ~20 us of
-             * queue gap, rocprofv3) */
-            c->pend2 = 1;
-            c->pend2_set = c->pend_set;
-            c->pend2_nsplit = c->pend_nsplit + nsplit;
-            c->pend2_ev[0] = c->pend_ev;
-            c->pend2_ev[1] = ev;
-        } else {
-            RCHK(launch_merge_sets(c, c->pend_set, 2, c->pend_nsplit + nsplit, cblk, c_base, nc));
-            if (c->pend_ev) HIPCHK(hipEventRecord(c->pend_ev[2], c->ms));
-            if (ev) HIPCHK(hipEventRecord(ev[2], c->ms));
-        }
-    } else if (!(set & 1) && (can_pair || gemm_own)) {
-        c->pend = 1;
-        c->pend_set = set;
-        c->pend_nsplit = nsplit;
-        c->pend_cblk = cblk;
-        c->pend_cbase = c_base;
-        c->pend_nc = (int)nc;
-        c->pend_ev = ev;
-    } else {
-        RCHK(launch_merge_sets(c, set, 1, nsplit, cblk, c_base, nc));
-        if (ev) HIPCHK(hipEventRecord(ev[2], c->ms));
-    }
-    /* step s - 2 is merged by now (a pending step is always s itself) */
-    if (c->nstep >= KNN_STEP_LAG) {
-        const int ps = (c->nstep - KNN_STEP_LAG) % KNN_PSETS;
-        HIPCHK(hipStreamWaitEvent(cs, (c->i8 || c->h16) ? c->ev_ds[ps] : c->ev_m[ps], 0));
-    }
-    c->first_step = 0;
-    c->ended = 0;
-    c->nstep++;
-    return KNN_OK;
+    /* a split-filter (GEMM) search's first step on its own query block keeps
+     * its merge pending: the direct exchange's fused step (knn_ctx_step_n)
+     * merges both in one k_merge over a table of all their blocks -- the
+     * own block's merge could not run beside the fused launch anyway (its
+     * workgroups hold every register of every CU), so it ran alone after
+     * it; any other next step merges it first, as a single merge */
+    const int gemm_own = c->split && !xb && c->nstep == 0 && d_cblock == c->qblk;
+    knn_merge_blocks_t mb;
+    memset(&mb, 0, sizeof(mb));
+    mb.nblk = 1;
+    mb.ptr[0] = d_cblock;
+    mb.base[0] = (int64_t)c_base;
+    mb.nc[0] = (int)nc;
+    return step_close(c, &st, &mb, nc, !(set & 1) && (st.can_pair || gemm_own));
 }
 
 int knn_ctx_step(knn_ctx_t *c, const void *d_cblock, size_t nc, size_t c_base, void *stream)
@@ -1495,35 +1528,15 @@ int knn_ctx_step_shadow_n(knn_ctx_t *c, int nblk, const void *const *d_sblocks, 
 static int ctx_step_split_n(knn_ctx_t *c, int nblk, const void *const *d_cblocks, const size_t *nc,
                             const size_t *c_base, void *stream)
 {
-    HIPCHK(hipSetDevice(c->device));
-    RCHK(flush_pend2(c, NULL, NULL));
     size_t nct = 0;   /* tile-rounded rows of the launch: the split model's input */
     for (int b = 0; b < nblk; b++) nct += knn_round_up(nc[b], KNN_SPLIT_TC);
     nct -= knn_round_up(nc[nblk - 1], KNN_SPLIT_TC) - nc[nblk - 1];
     c->split_solo = 0;
-    const int nsplit = choose_splits(c, nct);
-    const int set = c->nstep % KNN_PSETS, ds_i = c->nstep & 1;
-    /* the pending own-block step (odd set right behind its lists) shares
-     * this step's merge when the lists and the block table fit */
-    int share = c->pend && (set & 1) && nblk + 1 <= KNN_SPLIT_MAXBLK &&
-                c->lpq * (c->pend_nsplit + nsplit) + 1 <= 64;
-    if (!share) RCHK(merge_pending(c));
-    c->nsplit_last = nsplit;
-    if (!(set & 1)) c->even_nsplit = nsplit;
-    const int rc0 = ensure_part_buffers(c, nsplit, set, c->even_nsplit);
-    if (rc0 == KNN_ERR_INVALID && c->pend) {
-        /* the pair's lists cannot grow under the pending step's: merge it
-         * alone first (as ctx_step_impl does) */
-        RCHK(merge_pending(c));
-        share = 0;
-        RCHK(ensure_part_buffers(c, nsplit, set, c->even_nsplit));
-    } else if (rc0) {
-        return rc0;
-    }
-    hipStream_t cs = (hipStream_t)stream, ds = c->ds[ds_i];
-    HIPCHK(hipEventRecord(c->ev_in, cs));
-    HIPCHK(hipStreamWaitEvent(ds, c->ev_in, 0));
-    if (c->nstep >= KNN_PSETS) HIPCHK(hipStreamWaitEvent(ds, c->ev_m[set], 0));
+    knn_step_t st;
+    RCHK(step_open(c, &st, nct, 1, nblk, stream));
+    RCHK(step_enter(c, &st));
+    const int set = st.set;
+    hipStream_t ds = st.ds;
     const size_t per = knn_rows_pad(c->block_cap) * knn_split_rs(c->n);
     if (c->cspm_bytes[set] < per * (size_t)nblk) {
         /* (the set's last reader, merge s - 4, is ordered before ds above;
@@ -1558,54 +1571,14 @@ static int ctx_step_split_n(knn_ctx_t *c, int nblk, const void *const *d_cblocks
         tab.lim[b] = (int)knn_rows_pad(c->block_cap);
         mb.ptr[b] = d_cblocks[b];
     }
-    hipEvent_t *ev = NULL;
-    if (c->prof_on && c->prof_pending < KNN_PROF_STEPS) {
-        ev = &c->prof_ev[3 * c->prof_pending++];
-        HIPCHK(hipEventRecord(ev[0], ds));
-    }
+    RCHK(step_prof(c, &st));
     RCHK(knn_launch_dist_split_n(c->dtype, c->kp, c->k, c->qblk, c->q_rows_pad, c->q_base, (int)c->nq, c->qsp, &tab,
-                                 (int)c->n, c->meta, nsplit, c->part_d[set], c->part_i[set], c->part_T[set],
-                                 (int)c->nq_pad, c->qthr, xord_for(c, nsplit) | kz_bit(c),
+                                 (int)c->n, c->meta, st.nsplit, c->part_d[set], c->part_i[set], c->part_T[set],
+                                 (int)c->nq_pad, c->qthr, xord_for(c, st.nsplit) | kz_bit(c),
                                  (float)(-2.0 / ((double)c->sscale * c->sscale)),
                                  ds));
-    if (ev) HIPCHK(hipEventRecord(ev[1], ds));
-    HIPCHK(hipEventRecord(c->ev_ds[set], ds));
-    HIPCHK(hipStreamWaitEvent(c->ms, c->ev_ds[set], 0));
-    int mset = set, mnsplit = nsplit;
-    hipEvent_t *pev = NULL;
-    if (share) {
-        /* one merge of both steps: the pending set's lists, then this one's */
-        HIPCHK(hipStreamWaitEvent(c->ms, c->ev_ds[(set + KNN_PSETS - 1) % KNN_PSETS], 0));
-        c->pend = 0;
-        mb.ptr[nblk] = c->pend_cblk;
-        mb.base[nblk] = (int64_t)c->pend_cbase;
-        mb.nc[nblk] = c->pend_nc;
-        mb.nblk = nblk + 1;
-        mset = c->pend_set;
-        mnsplit = c->pend_nsplit + nsplit;
-        nct += (size_t)c->pend_nc;
-        pev = c->pend_ev;
-    }
-    const int *perm = NULL;
-    if (want_order(c, nct)) {
-        if (!c->ord_ready) RCHK(find_order(c, mset, mnsplit));
-        perm = c->ord_perm;
-    }
-    RCHK(knn_launch_merge_n(c->dtype, c->kp, c->k, c->part_d[mset], c->part_i[mset], c->part_T[mset], mnsplit,
-                            c->lpq, c->klx, (int)c->nq, (int)c->nq_pad, !c->merged, c->st_d, c->st_x, c->st_i,
-                            c->st_T, c->qblk, c->q_rows_pad, &mb, (int)c->n, c->meta, c->qthr, c->split | kz_bit(c), perm,
-                            c->ms));
-    c->merged = 1;
-    HIPCHK(hipEventRecord(c->ev_m[set], c->ms));
-    if (share) HIPCHK(hipEventRecord(c->ev_m[mset], c->ms));
-    if (pev) HIPCHK(hipEventRecord(pev[2], c->ms));
-    if (ev) HIPCHK(hipEventRecord(ev[2], c->ms));
-    /* step s - 2 is merged by now (its merge read its blocks' rows) */
-    if (c->nstep >= KNN_STEP_LAG) HIPCHK(hipStreamWaitEvent(cs, c->ev_m[(c->nstep - KNN_STEP_LAG) % KNN_PSETS], 0));
-    c->first_step = 0;
-    c->ended = 0;
-    c->nstep++;
-    return KNN_OK;
+    /* (its merge re-ranks from its blocks' rows: never held for a later step) */
+    return step_close(c, &st, &mb, nct, 0);
 }
 
 int knn_ctx_step_n(knn_ctx_t *c, int nblk, const void *const *d_cblocks, const size_t *nc, const size_t *c_base,
@@ -1798,6 +1771,20 @@ int knn_ctx_research_blocks(knn_ctx_t *c, int nblk, const void *const *d_sblocks
     return KNN_OK;
 }
 
+/* The search's last merge (the one that waits, if any), which finalizes too
+ * when it is the rank merge (INT-mode int8 lists); else k_finalize. */
+static int last_merge_or_finalize(knn_ctx_t *c, knn_neighbour_t *d_out)
+{
+    int fin = 0;
+    RCHK(flush_deferred(c, d_out, &fin));
+    if (!fin)
+        RCHK(knn_launch_finalize(c->dtype, c->kp, c->st_d, c->st_x, c->st_i, c->st_T, c->qblk, c->q_rows_pad,
+                                 (int)c->nq, (int)c->n, c->k, c->meta, d_out, c->fail_count,
+                                 c->fail_list, c->mode_dev, c->fbound, env_on("KNN_FORCE_RESCAN"),
+                                 c->split | kz_bit(c), c->ms));
+    return KNN_OK;
+}
+
 /* The device side of knn_ctx_end: the last merge / finalize on the merge
  * stream, `stream` ordered after them.  The records, the fail list and its
  * count are then on the device; no host read (research8's sub-context). */
@@ -1805,14 +1792,7 @@ static int ctx_end_device(knn_ctx_t *c, knn_neighbour_t *d_out, hipStream_t s)
 {
     HIPCHK(hipEventRecord(c->ev_in, s));
     HIPCHK(hipStreamWaitEvent(c->ms, c->ev_in, 0));
-    int fin = 0;
-    RCHK(flush_pend2(c, d_out, &fin));
-    if (!fin) RCHK(merge_pending_fin(c, d_out, &fin));
-    if (!fin)
-        RCHK(knn_launch_finalize(c->dtype, c->kp, c->st_d, c->st_x, c->st_i, c->st_T, c->qblk, c->q_rows_pad,
-                                 (int)c->nq, (int)c->n, c->k, c->meta, d_out, c->fail_count,
-                                 c->fail_list, c->mode_dev, c->fbound, env_on("KNN_FORCE_RESCAN"),
-                                 c->split | kz_bit(c), c->ms));
+    RCHK(last_merge_or_finalize(c, d_out));
     HIPCHK(hipEventRecord(c->ev_end, c->ms));
     HIPCHK(hipStreamWaitEvent(s, c->ev_end, 0));
     return KNN_OK;
@@ -1822,16 +1802,7 @@ static int ctx_end_device(knn_ctx_t *c, knn_neighbour_t *d_out, hipStream_t s)
  * caller's stream has been waited for on the host) */
 static int ctx_end_merge(knn_ctx_t *c, knn_neighbour_t *d_out)
 {
-    /* the last merge (deferred or pending) finalizes too when it is the
-     * rank merge (INT-mode int8 lists) */
-    int fin = 0;
-    RCHK(flush_pend2(c, d_out, &fin));
-    if (!fin) RCHK(merge_pending_fin(c, d_out, &fin));
-    if (!fin)
-        RCHK(knn_launch_finalize(c->dtype, c->kp, c->st_d, c->st_x, c->st_i, c->st_T, c->qblk, c->q_rows_pad,
-                                 (int)c->nq, (int)c->n, c->k, c->meta, d_out, c->fail_count,
-                                 c->fail_list, c->mode_dev, c->fbound, env_on("KNN_FORCE_RESCAN"),
-                                 c->split | kz_bit(c), c->ms));
+    RCHK(last_merge_or_finalize(c, d_out));
     c->h_count[0] = c->h_count[1] = -1;
     RCHK(knn_launch_count_out(c->fail_count, c->h_count_dev, c->meta,
                               (double *)((char *)c->h_count_dev + 16), c->ms));

@@ -171,7 +171,8 @@ typedef struct {
     int nblk;
 } knn_split_blocks_t;
 /* the element blocks a GEMM-mode merge re-ranks from (k_merge's exact S):
- * block j holds global ids base[j] .. base[j] + nc[j] - 1 */
+ * block j holds global ids base[j] .. base[j] + nc[j] - 1 (one entry: a
+ * single-block step) */
 typedef struct {
     const void *ptr[KNN_SPLIT_MAXBLK];
     int64_t base[KNN_SPLIT_MAXBLK];
@@ -233,12 +234,6 @@ int knn_launch_dist_i8(int kp, int kl, int lpq, int k, const void *qsh, size_t q
                        const knn_i8_blocks_t *cb, size_t c_rows_pad, int n, int nsplit,
                        double *part_d, int *part_i, double *part_T, int nq_pad, double *qthr,
                        unsigned long long *qsum, int keep_zero, void *stream);
-int knn_launch_merge(int dtype, int kp, int k, const double *part_d, const int *part_i,
-                     const double *part_T, int nsplit, int lpq, int kl, int nq, int nq_pad,
-                     int first_step,
-                     double *st_d, double *st_x, int *st_i, double *st_T, const void *qblk,
-                     size_t q_rows_pad, const void *cblk, size_t c_base, int nc, int n,
-                     const double *meta, double *qthr, int filt, const int *qperm, void *stream);
 /* knn_order.hip: a query order for the GEMM-mode merge (queries grouped by
  * the clusters their list heads connect) */
 size_t knn_order_tmp_bytes(int nq);

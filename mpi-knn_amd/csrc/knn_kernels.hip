@@ -2805,22 +2805,6 @@ extern "C" int knn_launch_dist_split_n(int dtype, int kp, int k, const void *qbl
 #undef CALL
 }
 
-extern "C" int knn_launch_merge(int dtype, int kp, int k, const double *part_d, const int *part_i,
-                                const double *part_T, int nsplit, int lpq, int kl, int nq, int nq_pad,
-                                int first_step, double *st_d, double *st_x, int *st_i,
-                                double *st_T, const void *qblk, size_t q_rows_pad,
-                                const void *cblk, size_t c_base, int nc, int n,
-                                const double *meta, double *qthr, int filt, const int *qperm, void *stream)
-{
-    knn_merge_blocks_t mb{};
-    mb.nblk = 1;
-    mb.ptr[0] = cblk;
-    mb.base[0] = (int64_t)c_base;
-    mb.nc[0] = nc;
-    return knn_launch_merge_n(dtype, kp, k, part_d, part_i, part_T, nsplit, lpq, kl, nq, nq_pad, first_step, st_d,
-                              st_x, st_i, st_T, qblk, q_rows_pad, &mb, n, meta, qthr, filt, qperm, stream);
-}
-
 extern "C" int knn_launch_merge_n(int dtype, int kp, int k, const double *part_d, const int *part_i,
                                   const double *part_T, int nsplit, int lpq, int kl, int nq, int nq_pad,
                                   int first_step, double *st_d, double *st_x, int *st_i, double *st_T,
