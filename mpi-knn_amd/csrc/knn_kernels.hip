@@ -1381,28 +1381,41 @@ __global__ __launch_bounds__(256) void k_merge(
 }
 
 // ---------------------------------------------------------------------------
-// k_merge_rank: the INT-mode merge of int8 lane lists (k_dist_topk_i8: exact
-// integer d^2 < 2^31; zeros never admitted, or -- keep-zero -- admitted as
-// the results they are: nothing here tells them apart) by ranking instead of argmin
-// rounds.  One wave per query.  The shared bound qthr[q] is an upper bound on
-// the query's (k+1)-th smallest d^2 over all rows (k + 1 distinct rows lie at
-// or below it), so no entry above it can be among the k + 1 smallest; the
-// (k+1)-th smallest key among the lists' first entries and the state is a
-// second such bound, usually far tighter.  Every list entry and state entry
-// at or below both is compacted into LDS as a u64 key (d^2 << 32 | idx: u64
-// order is the reference's (d, idx) order; keys are distinct),
-// each candidate's rank is the number of smaller keys, and rank r < k + 1
-// goes to state slot r.  The rank of a candidate costs C compares a lane
-// (C candidates, ~31..60 at the end of a search);
-// k_merge's k + 1 dependent wave-argmin rounds cost ~2k cycles each in
-// latency (rocprofv3: 33 us for 7500 queries, 0.19 ms for 60000).
-// State, T, Td and the publication as k_merge's INT mode (the (k+1)-th of
-// the merged entries is published into qthr).
+// The rank merge (k_merge_rank, k_merge_rank16): the INT-mode merge of int8
+// lane lists (k_dist_topk_i8: exact integer d^2 < 2^31; zeros never admitted,
+// or -- keep-zero -- admitted as the results they are: nothing here tells
+// them apart) by ranking instead of k_merge's argmin rounds (k + 1 dependent
+// wave-argmins of ~2k cycles each: 33 us for 7500 queries, 0.19 ms for 60000,
+// rocprofv3).  G lanes serve a query; a lane holds one list, and -- after the
+// first step of a ring -- one entry of the query's state.
+//
+// Bounds.  The shared bound qthr[q] is an upper bound on the query's (k+1)-th
+// smallest d^2 over all rows (k + 1 distinct rows lie at or below it), so no
+// entry above it can be among the k + 1 smallest.  The (k+1)-th smallest key
+// among the lists' first HD entries and the state is a second such bound (a
+// subset's (k+1)-th is never below the whole set's), usually far tighter: the
+// shared bound alone admitted ~100-170 entries a query at P = 1 (7 splits x
+// 2 lists x 12), and the rank loop's broadcast LDS reads grow with C^2 / 64
+// (89 us a merge of 60000 queries, nearly all of it those reads; round 6).
+//
+// Ranks.  Every list and state entry at or below both bounds is compacted
+// into the group's LDS buffer as a u64 key (d^2 << 32 | idx: u64 order is the
+// reference's (d, idx) order; keys are distinct).  A candidate's
+// rank is the number of smaller keys: C compares a candidate (~31..60 at the
+// end of a search), 64 / G candidates a lane a round.
+//
+// Outcome.  Not the search's last merge (fin == 0): rank r < k + 1 goes to
+// state slot r, T and Td are kept, and the rank-k key is published into qthr,
+// as k_merge's INT mode does.  The last merge (fin != 0, knn_ctx_end) does
+// k_finalize's INT-mode work in the same pass instead: rank r < k is record
+// r, slots past the candidates are {inf, 0, 0}, and the query is certified
+// (tau_k < T) or put on the rescan list with the bounds its rescan (fbound)
+// and int8 re-search (qthr) start from.  With fewer than k + 1 candidates
+// under the bounds those come from a fallback pass over every entry of the
+// lists and the state -- with +inf instead they scanned cold (2.8 ms of
+// k_rescan_step for two MNIST queries).
 // ---------------------------------------------------------------------------
 typedef unsigned long long knn_u64x2 __attribute__((ext_vector_type(2)));
-// fin != 0 (the search's last merge, knn_ctx_end): k_finalize's INT-mode
-// work in the same pass -- certify tau_k < T, emit the k records or put the
-// query on the rescan list -- instead of writing the state.
 struct knn_fin_args {
     knn_neighbour_t *out;
     int *fail_count, *fail_list, *mode_out;
@@ -1411,6 +1424,335 @@ struct knn_fin_args {
     double lim;   // 2^51 / 4n, knn_mode_lim
     int n, force_fail;
 };
+// list entries as 32-bit d^2 (exact integers < 2^31; +inf -> RANK_DINF, above
+// every bound): half the registers of doubles, 5 -> 6 waves a SIMD
+constexpr unsigned RANK_DINF = 0xffffffffu;
+constexpr unsigned long long RANK_NOKEY = ~0ull;   // above every key
+
+__device__ __forceinline__ unsigned long long rank_key(unsigned d, int id)
+{
+    return ((unsigned long long)d << 32) | (unsigned)id;
+}
+__device__ __forceinline__ double rank_key_d2(unsigned long long key) { return (double)(unsigned)(key >> 32); }
+
+// list l of a query: split l / lpq, list l % lpq of that split
+__device__ __forceinline__ size_t rank_list_base(int l, int lpq, int q, int nq_pad, int kl)
+{
+    const int s = lpq == 2 ? l >> 1 : lpq == 4 ? l >> 2 : l / lpq, g = l - s * lpq;
+    return (((size_t)s * nq_pad + q) * lpq + g) * kl;
+}
+
+// List l of query q (l < nl; other lanes hold none) and the number of its
+// entries at or below Bu -- a prefix: the list is sorted, +inf past its end.
+// Its first 4 entries, then the rest in one round if the 4th is still at or
+// below the bound (two dependent rounds at most: the merge is latency-bound);
+// full: all at once.
+template <int KL>
+__device__ __forceinline__ int rank_load_lists(const double *__restrict__ part_d, const int *__restrict__ part_i,
+                                               int l, int nl, int lpq, int q, int nq_pad, unsigned Bu, bool full,
+                                               unsigned (&d)[KL], int (&id)[KL])
+{
+#pragma unroll
+    for (int e = 0; e < KL; e++) {
+        d[e] = RANK_DINF;
+        id[e] = 0;
+    }
+    int c = 0;
+    if (l < nl) {
+        constexpr int H = KL < 4 ? KL : 4;
+        const size_t base = rank_list_base(l, lpq, q, nq_pad, KL);
+        auto load = [&](int e) {
+            const double v = part_d[base + e];
+            d[e] = v < 4294967295.0 ? (unsigned)v : RANK_DINF;
+            id[e] = part_i[base + e];
+        };
+#pragma unroll
+        for (int e = 0; e < H; e++) load(e);
+        if (KL > H && (full || d[H - 1] <= Bu)) {
+#pragma unroll
+            for (int e = H; e < KL; e++) load(e);
+        }
+#pragma unroll
+        for (int e = 0; e < KL; e++) c += d[e] <= Bu ? 1 : 0;
+    }
+    return c;
+}
+
+// the lanes of this lane's group of G
+template <int G>
+__device__ __forceinline__ unsigned long long rank_gmask()
+{
+    if constexpr (G == 64) return ~0ull;
+    else return ((1ull << G) - 1ull) << (threadIdx.x & 63 & ~(G - 1));
+}
+
+// exclusive prefix within the group of the per-lane counts ct < 2^NB, and
+// their sum: bit-sliced through ballots (a whole wave: mbcnt)
+template <int G, int NB>
+__device__ __forceinline__ int rank_prefix(int ct, int &sum)
+{
+    int pre = 0;
+    sum = 0;
+#pragma unroll
+    for (int b = 0; b < NB; b++) {
+        const unsigned long long m = __ballot((ct >> b) & 1) & rank_gmask<G>();
+        if constexpr (G == 64)
+            pre += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) << b;
+        else
+            pre += __popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull)) << b;
+        sum += __popcll(m) << b;
+    }
+    return pre;
+}
+
+// the group's LDS writes are visible to its reads
+__device__ __forceinline__ void rank_lds_sync()
+{
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// One round of ranks: lane gl takes the keys x[t] = buf[b0 + gl + G t] (past
+// C: RANK_NOKEY) and counts the keys of buf[0, C) below each -- broadcast
+// reads, 2 keys each.  skip: leave the slots out that are dead in the whole
+// group this round (it costs a test a slot; C and b0 are group-uniform).
+template <int G>
+__device__ __forceinline__ void rank_count(const LDS_AS unsigned long long *buf, int C, int b0, int gl, bool skip,
+                                           unsigned long long (&x)[64 / G], int (&r)[64 / G])
+{
+    constexpr int NT = 64 / G;
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+        const int my = b0 + gl + G * t;
+        x[t] = my < C ? buf[my] : RANK_NOKEY;
+        r[t] = 0;
+    }
+    const int nt = skip ? (int)((unsigned)(C - b0 + G - 1) / G) : NT;   // live slots a lane
+    int j = 0;
+    for (; j + 4 <= C; j += 4) {
+        const knn_u64x2 u = *(const LDS_AS knn_u64x2 *)(buf + j);
+        const knn_u64x2 w = *(const LDS_AS knn_u64x2 *)(buf + j + 2);
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+            if (NT == 1 || t < nt)
+                r[t] += (u.x < x[t] ? 1 : 0) + (u.y < x[t] ? 1 : 0) + (w.x < x[t] ? 1 : 0) + (w.y < x[t] ? 1 : 0);
+    }
+    for (; j < C; j++) {
+        const unsigned long long u = buf[j];
+#pragma unroll
+        for (int t = 0; t < NT; t++) r[t] += u < x[t] ? 1 : 0;
+    }
+}
+
+// the key of the group's lane with hit set (at most one), if any
+template <int G>
+__device__ __forceinline__ bool rank_pick(bool hit, unsigned long long x, unsigned long long &key)
+{
+    const unsigned long long at = __ballot(hit) & rank_gmask<G>();
+    if (at) key = __shfl(x, __builtin_ctzll(at));
+    return at != 0;
+}
+
+// The keys at ranks k - 1 and k among buf[0, C), as d^2: tau (the k-th kept)
+// and tk1 (the (k+1)-th); left alone where C has no such rank.
+template <int G>
+__device__ __forceinline__ void rank_pick_tau(bool hit0, bool hit1, unsigned long long x, double &tau, double &tk1)
+{
+    unsigned long long key;
+    if (rank_pick<G>(hit0, x, key)) tau = rank_key_d2(key);
+    if (rank_pick<G>(hit1, x, key)) tk1 = rank_key_d2(key);
+}
+
+// The merge of one query by the G lanes gl = 0 .. G - 1 of a wave (qv: the
+// group has a query; lanes of groups without one run along with nothing).
+// buf: the group's LDS, room for every list and state entry.  first_step and
+// fin as compile-time constants (k_merge_rank16) remove the state's code.
+template <typename TE, int KP, int KL, int G>
+__device__ __forceinline__ void rank_merge(
+    LDS_AS unsigned long long *buf, int q, bool qv, int gl, const double *__restrict__ part_d,
+    const int *__restrict__ part_i, const double *__restrict__ part_T, int nsplit, int lpq, int nq_pad,
+    int first_step, double *__restrict__ st_d, double *__restrict__ st_x, int *__restrict__ st_i,
+    double *__restrict__ st_T, int k, unsigned long long *__restrict__ qthr, int fin, const knn_fin_args &fa)
+{
+    constexpr int NT = 64 / G;
+    const int nl = qv ? lpq * nsplit : 0;
+    // any value read is a valid bound (it only falls); floor: d^2 are integers
+    const double qb = __longlong_as_double((long long)qthr[qv ? q : 0]);
+    const double B = qb >= 4294967294.0 ? 4294967294.0 : floor(qb);
+    const unsigned Bu = (unsigned)B;
+    // T: the smallest rejection bound of the merged lanes (and the state, on
+    // the group's last lane); read with the lists (one round of loads)
+    double T = KNN_INF, Td = KNN_INF;
+    if (qv && gl < nsplit) T = part_T[(size_t)gl * nq_pad + q];
+    if (!first_step && gl == G - 1) {
+        T = fmin(T, st_T[2 * (size_t)q]);
+        Td = st_T[2 * (size_t)q + 1];
+    }
+    const int mode = fin ? knn_mode_lim<TE>(fa.meta, fa.n, fa.lim) : KNN_MODE_INT;
+    unsigned d[KL];
+    int id[KL];
+    int c = rank_load_lists<KL>(part_d, part_i, gl, nl, lpq, q, nq_pad, Bu, false, d, id);
+    // the lane's state entry, if any (d^2 < 2^31 or +inf), and whether it
+    // lies at or below the bounds
+    unsigned long long skey = RANK_NOKEY;
+    if (!first_step && gl < KP) {
+        const double sdv = st_d[(size_t)q * KP + gl];
+        const int siv = st_i[(size_t)q * KP + gl];
+        if (siv >= 0 && sdv < 4294967295.0) skey = rank_key((unsigned)sdv, siv);
+    }
+    int cs = (skey != RANK_NOKEY && (unsigned)(skey >> 32) <= Bu) ? 1 : 0;
+
+    // the tighter bound: rank k among the lists' first HD entries and the
+    // state.  Groups of one wave differ in CH > k: the writes are predicated
+    // and the barriers unconditional.
+    unsigned long long lim = RANK_NOKEY;
+    {
+        constexpr int HD = KL < 4 ? KL : 4;
+        const int hh = c < HD ? c : HD;
+        int CH;
+        const int preh = rank_prefix<G, 3>(hh + cs, CH);
+        const bool tight = CH > k;
+#pragma unroll
+        for (int e = 0; e < HD; e++)
+            if (tight && e < hh) buf[preh + e] = rank_key(d[e], id[e]);
+        if (tight && cs) buf[preh + hh] = skey;
+        rank_lds_sync();
+        if (tight) {
+            for (int b0 = 0; b0 < CH; b0 += 64) {
+                unsigned long long x[NT];
+                int r[NT];
+                rank_count<G>(buf, CH, b0, gl, false, x, r);   // (nearly every slot is live)
+#pragma unroll
+                for (int t = 0; t < NT; t++) rank_pick<G>(b0 + gl + G * t < CH && r[t] == k, x[t], lim);
+            }
+            // keep the entries at or below it (the lists are sorted by d, so
+            // a prefix up to ties: counted and written entry by entry)
+            int c2 = 0;
+#pragma unroll
+            for (int e = 0; e < KL; e++) c2 += (e < c && rank_key(d[e], id[e]) <= lim) ? 1 : 0;
+            c = c2;
+            if (skey > lim) cs = 0;
+        }
+        __builtin_amdgcn_wave_barrier();   // (the subset's slots are overwritten below)
+    }
+    // compaction: the group's entries at or below both bounds
+    int C;
+    {
+        int w = rank_prefix<G, 5>(c + cs, C);   // (c + cs <= KL + 1 < 32)
+#pragma unroll
+        for (int e = 0; e < KL; e++) {
+            const unsigned long long key = rank_key(d[e], id[e]);
+            if (d[e] <= Bu && key <= lim) buf[w++] = key;
+        }
+        if (cs) buf[w] = skey;
+    }
+    rank_lds_sync();
+
+    const int kk = k + 1 < KP ? k + 1 : KP;   // entries the state keeps
+    for (int off = G / 2; off > 0; off >>= 1) {
+        T = fmin(T, __shfl_xor(T, off));
+        Td = fmin(Td, __shfl_xor(Td, off));
+    }
+    // fin: the records are written as the ranks come out; the query is
+    // certified (or put on the rescan list, whose pass rewrites them) after
+    if (fin) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *fa.mode_out = mode;
+        for (int p = gl; p < k; p += G)
+            if (qv && p >= C) {   // slots past the candidates
+                knn_neighbour_t rec;
+                rec.distance = KNN_INF;
+                rec.idx = 0;
+                rec.label = 0;
+                fa.out[(size_t)q * k + p] = rec;
+            }
+    }
+    double tau = KNN_INF, tk1 = KNN_INF;
+    for (int b0 = 0; b0 < C; b0 += 64) {   // (group-uniform trip count)
+        unsigned long long x[NT];
+        int r[NT];
+        rank_count<G>(buf, C, b0, gl, true, x, r);
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            const bool live = b0 + gl + G * t < C;
+            const double dv = rank_key_d2(x[t]);
+            if (live && fin) {
+                if (r[t] < k) {
+                    knn_neighbour_t rec;
+                    rec.distance = sqrt(dv);
+                    rec.idx = (int)(unsigned)x[t] + 1;
+                    rec.label = 0;
+                    fa.out[(size_t)q * k + r[t]] = rec;
+                }
+            } else if (live) {
+                if (r[t] < kk) {
+                    st_d[(size_t)q * KP + r[t]] = dv;
+                    st_x[(size_t)q * KP + r[t]] = dv;
+                    st_i[(size_t)q * KP + r[t]] = (int)(unsigned)x[t];
+                }
+                if (r[t] == k) {   // the (k+1)-th: a bound on the query's (k+1)-th over all rows
+                    double u = dv;
+                    if constexpr (sizeof(TE) == 4) u = (double)__double2float_ru(u);
+                    atomicMin(qthr + q, (unsigned long long)__double_as_longlong(u));
+                }
+            }
+            if (fin) rank_pick_tau<G>(live && r[t] == k - 1, live && r[t] == k, x[t], tau, tk1);
+        }
+    }
+    if (fin) {
+        // k_finalize, INT mode: zeros were never admitted, so the rank-(k-1)
+        // candidate is tau; a candidate a lane turned away has d^2 >= T, and
+        // with d^2 == T it may precede the k-th by index: certify tau < T
+        const bool intm = mode == KNN_MODE_INT && !fa.force_fail;
+        const bool ok = intm && (T == KNN_INF || (C >= k && tau < T));
+        if (qv && !ok && intm && C < k + 1) {
+            // the fallback: the k-th and (k+1)-th over every entry -- still
+            // bounds on the query's k-th / (k+1)-th over all rows
+            const int c2 = rank_load_lists<KL>(part_d, part_i, gl, nl, lpq, q, nq_pad, RANK_DINF - 1, true, d, id);
+            const int cs2 = skey != RANK_NOKEY ? 1 : 0;
+            int C2;
+            const int pre2 = rank_prefix<G, 5>(c2 + cs2, C2);
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int e = 0; e < KL; e++)
+                if (e < c2) buf[pre2 + e] = rank_key(d[e], id[e]);
+            if (cs2) buf[pre2 + c2] = skey;
+            rank_lds_sync();
+            for (int b0 = 0; b0 < C2; b0 += 64) {
+                unsigned long long x[NT];
+                int r[NT];
+                rank_count<G>(buf, C2, b0, gl, true, x, r);
+#pragma unroll
+                for (int t = 0; t < NT; t++) {
+                    const bool live = b0 + gl + G * t < C2;
+                    rank_pick_tau<G>(live && r[t] == k - 1, live && r[t] == k, x[t], tau, tk1);
+                }
+            }
+        }
+        if (qv && !ok && gl == 0) {
+            fa.fail_list[atomicAdd(fa.fail_count, 1)] = q;
+            fa.fbound[q] = intm ? sqrt(tau) : KNN_INF;
+            // k + 1 distinct rows lie at or below the (k+1)-th kept key: a
+            // valid bound for the int8 re-search to start from (knn_engine.c
+            // research8; INT mode only, the search is over)
+            if (intm)
+                qthr[q] = (unsigned long long)__double_as_longlong(sizeof(TE) == 4 ? (double)__double2float_ru(tk1) : tk1);
+        }
+        return;
+    }
+    if (gl < KP && gl >= (C < kk ? C : kk)) {
+        st_d[(size_t)q * KP + gl] = KNN_INF;
+        st_x[(size_t)q * KP + gl] = KNN_INF;
+        st_i[(size_t)q * KP + gl] = -1;
+    }
+    if (gl == 0) {
+        st_T[2 * (size_t)q] = T;
+        st_T[2 * (size_t)q + 1] = Td;
+    }
+}
+
+// k_merge_rank: one wave a query, 4 queries a workgroup; any merge of a
+// search (a state is read after the first step and written unless fin).
+// Dynamic LDS: cap keys a wave (every list and state entry).
 template <typename TE, int KP, int KL>
 __global__ __launch_bounds__(256) void k_merge_rank(
     const double *__restrict__ part_d, const int *__restrict__ part_i, const double *__restrict__ part_T,
@@ -1422,281 +1764,16 @@ __global__ __launch_bounds__(256) void k_merge_rank(
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = blockIdx.x * 4 + wave;
     if (q >= nq) return;   // wave-uniform, and no workgroup barrier below
-    LDS_AS unsigned long long *buf = (LDS_AS unsigned long long *)mr_buf + (size_t)wave * cap;
-    const int nl = lpq * nsplit;
-    // any value read is a valid bound (it only falls); floor: d^2 are integers
-    const double qb = __longlong_as_double((long long)qthr[q]);
-    const double B = qb >= 4294967294.0 ? 4294967294.0 : floor(qb);
-    const unsigned Bu = (unsigned)B;
-    // T: the smallest rejection bound of the merged lanes (and the state);
-    // read with the lists (one round of loads), reduced below
-    double T = KNN_INF, Td = KNN_INF;
-    if (lane < nsplit) T = part_T[(size_t)lane * nq_pad + q];
-    if (!first_step && lane == 63) {
-        T = fmin(T, st_T[2 * (size_t)q]);
-        Td = st_T[2 * (size_t)q + 1];
-    }
-    const int mode = fin ? knn_mode_lim<TE>(fa.meta, fa.n, fa.lim) : KNN_MODE_INT;
-    // list entries as 32-bit d^2 (exact integers < 2^31; +inf -> 0xffffffff,
-    // above every bound): half the registers of doubles, 5 -> 6 waves a SIMD
-    constexpr unsigned DINF = 0xffffffffu;
-    unsigned d[KL];
-    int id[KL];
-#pragma unroll
-    for (int e = 0; e < KL; e++) {
-        d[e] = DINF;
-        id[e] = 0;
-    }
-    int c = 0;
-    if (lane < nl) {
-        const int s = lpq == 2 ? lane >> 1 : lpq == 4 ? lane >> 2 : lane / lpq, g = lane - s * lpq;
-        const size_t base = (((size_t)s * nq_pad + q) * lpq + g) * KL;
-        // the list is sorted: its first 4 entries, then the rest in one
-        // round if the 4th is still at or below the bound (two dependent
-        // rounds at most: the merge is latency-bound, one wave a query)
-#pragma unroll
-        for (int e = 0; e < 4 && e < KL; e++) {
-            const double v = part_d[base + e];
-            d[e] = v < 4294967295.0 ? (unsigned)v : DINF;
-            id[e] = part_i[base + e];
-        }
-        if (KL > 4 && d[3] <= Bu) {
-#pragma unroll
-            for (int e = 4; e < KL; e++) {
-                const double v = part_d[base + e];
-                d[e] = v < 4294967295.0 ? (unsigned)v : DINF;
-                id[e] = part_i[base + e];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < KL; e++) c += d[e] <= Bu ? 1 : 0;   // a prefix (+inf past the end)
-    }
-    double sdv = KNN_INF;
-    int siv = -1, cs = 0;
-    if (!first_step && lane < KP) {
-        sdv = st_d[(size_t)q * KP + lane];
-        siv = st_i[(size_t)q * KP + lane];
-        cs = (siv >= 0 && sdv <= B) ? 1 : 0;
-    }
-    // A tighter bound first: the (k+1)-th smallest key among the first HD
-    // entries of every list and the state entries.  It is at or above the
-    // (k+1)-th smallest key of all the entries (a subset's (k+1)-th is never
-    // below the whole set's), so the entries at or below it still hold the
-    // k + 1 smallest.  The shared bound B alone admitted ~100-170 entries a
-    // query at P = 1 (7 splits x 2 lists x 12), and the rank loop's
-    // broadcast LDS reads grow with C^2 / 64: 89 us a merge of 60000
-    // queries, nearly all of it those reads (rocprofv3, round 6).
-    unsigned long long lim = ~0ull;
-#ifndef KNN_MR_NOTIGHT
-    {
-        constexpr int HD = KL < 4 ? KL : 4;
-        const int hh = c < HD ? c : HD;    // lists are sorted: a prefix
-        const int chh = hh + cs;
-        int preh = 0, CH = 0;
-#pragma unroll
-        for (int b = 0; b < 5; b++) {
-            const unsigned long long m = __ballot((chh >> b) & 1);
-            preh += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) << b;
-            CH += __popcll(m) << b;
-        }
-        if (CH > k) {
-#pragma unroll
-            for (int e = 0; e < HD; e++)
-                if (e < hh) buf[preh + e] = ((unsigned long long)d[e] << 32) | (unsigned)id[e];
-            if (cs) buf[preh + hh] = ((unsigned long long)(unsigned)sdv << 32) | (unsigned)siv;
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            unsigned long long bk = ~0ull;
-            for (int b0 = 0; b0 < CH; b0 += 64) {
-                const int my = b0 + lane;
-                const unsigned long long x = my < CH ? buf[my] : ~0ull;
-                int r = 0, j = 0;
-                for (; j + 4 <= CH; j += 4) {
-                    const knn_u64x2 u = *(const LDS_AS knn_u64x2 *)(buf + j);
-                    const knn_u64x2 w = *(const LDS_AS knn_u64x2 *)(buf + j + 2);
-                    r += (u.x < x ? 1 : 0) + (u.y < x ? 1 : 0) + (w.x < x ? 1 : 0) + (w.y < x ? 1 : 0);
-                }
-                for (; j < CH; j++) r += buf[j] < x ? 1 : 0;
-                const unsigned long long at = __ballot(my < CH && r == k);
-                if (at) bk = __shfl(x, __builtin_ctzll(at));
-            }
-            // keep the entries at or below it (the lists are sorted by d, so
-            // a prefix up to ties; counted and written entry by entry below)
-            lim = bk;
-            int c2 = 0;
-#pragma unroll
-            for (int e = 0; e < KL; e++)
-                c2 += (e < c && (((unsigned long long)d[e] << 32) | (unsigned)id[e]) <= bk) ? 1 : 0;
-            c = c2;
-            if (cs && (((unsigned long long)(unsigned)sdv << 32) | (unsigned)siv) > bk) cs = 0;
-            __builtin_amdgcn_wave_barrier();   // (the subset's slots are overwritten below)
-        }
-    }
-#endif
-    // exclusive prefix of the per-lane counts (<= KL + 1 < 32): bit-sliced
-    // through mbcnt
-    const int ct = c + cs;
-    int pre = 0, C = 0;
-#pragma unroll
-    for (int b = 0; b < 5; b++) {
-        const unsigned long long m = __ballot((ct >> b) & 1);
-        pre += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) << b;
-        C += __popcll(m) << b;
-    }
-    {
-        int w = pre;
-#pragma unroll
-        for (int e = 0; e < KL; e++) {
-            const unsigned long long key = ((unsigned long long)d[e] << 32) | (unsigned)id[e];
-            if (d[e] <= Bu && key <= lim) buf[w++] = key;
-        }
-    }
-    if (cs) buf[pre + c] = ((unsigned long long)(unsigned)sdv << 32) | (unsigned)siv;
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-
-    const int kk = k + 1 < KP ? k + 1 : KP;   // entries the state keeps
-    for (int off = 32; off > 0; off >>= 1) {
-        T = fmin(T, __shfl_xor(T, off));
-        Td = fmin(Td, __shfl_xor(Td, off));
-    }
-    // fin: the records are written as the ranks come out; the query is
-    // certified (or put on the rescan list, whose pass rewrites them) after
-    const bool emit = fin != 0;
-    if (fin) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) *fa.mode_out = mode;
-        // slots past the candidates: {inf, 0, 0}
-        if (lane < k && lane >= C) {
-            knn_neighbour_t rec;
-            rec.distance = KNN_INF;
-            rec.idx = 0;
-            rec.label = 0;
-            fa.out[(size_t)q * k + lane] = rec;
-        }
-    }
-    double tau = KNN_INF;   // fin: the k-th kept d^2
-    double tk1 = KNN_INF;   // fin: the (k+1)-th, the seed of an uncertified query's re-search
-    for (int b0 = 0; b0 < C; b0 += 64) {
-        const int my = b0 + lane;
-        const unsigned long long x = my < C ? buf[my] : ~0ull;
-        int r = 0, j = 0;
-        for (; j + 4 <= C; j += 4) {   // broadcast reads, 2 keys each
-            const knn_u64x2 a = *(const LDS_AS knn_u64x2 *)(buf + j);
-            const knn_u64x2 b = *(const LDS_AS knn_u64x2 *)(buf + j + 2);
-            r += (a.x < x ? 1 : 0) + (a.y < x ? 1 : 0) + (b.x < x ? 1 : 0) + (b.y < x ? 1 : 0);
-        }
-        for (; j < C; j++) r += buf[j] < x ? 1 : 0;
-        if (my < C) {
-            const double dv = (double)(unsigned)(x >> 32);
-            if (emit) {
-                if (r < k) {
-                    knn_neighbour_t rec;
-                    rec.distance = sqrt(dv);
-                    rec.idx = (int)(unsigned)x + 1;
-                    rec.label = 0;
-                    fa.out[(size_t)q * k + r] = rec;
-                }
-            } else if (r < kk) {
-                st_d[(size_t)q * KP + r] = dv;
-                st_x[(size_t)q * KP + r] = dv;
-                st_i[(size_t)q * KP + r] = (int)(unsigned)x;
-            }
-            if (r == k && !emit) {   // the (k+1)-th: a bound on the query's (k+1)-th over all rows
-                double u = dv;
-                if constexpr (sizeof(TE) == 4) u = (double)__double2float_ru(u);
-                atomicMin(qthr + q, (unsigned long long)__double_as_longlong(u));
-            }
-        }
-        if (emit) {
-            const unsigned long long at = __ballot(my < C && r == k - 1);
-            if (at) tau = (double)(unsigned)(__shfl(x, __builtin_ctzll(at)) >> 32);
-            const unsigned long long a1 = __ballot(my < C && r == k);
-            if (a1) tk1 = (double)(unsigned)(__shfl(x, __builtin_ctzll(a1)) >> 32);
-        }
-    }
-    if (emit) {
-        // k_finalize, INT mode: zeros were never admitted, so the rank-(k-1)
-        // candidate is tau; a candidate a lane turned away has d^2 >= T, and
-        // with d^2 == T it may precede the k-th by index: certify tau < T
-        const bool ok = mode == KNN_MODE_INT && !fa.force_fail && (T == KNN_INF || (C >= k && tau < T));
-        if (!ok && C < k + 1 && mode == KNN_MODE_INT && !fa.force_fail) {
-            // fewer than k + 1 entries under the shared bound: the k-th and
-            // (k+1)-th over every entry of the lists and the state -- still
-            // bounds on the query's k-th / (k+1)-th over all rows, which the
-            // rescan (fbound) and the int8 re-search (qthr) start from; with
-            // +inf instead they scanned cold (2.8 ms of k_rescan_step for two
-            // MNIST queries)
-            int c2 = 0;
-            if (lane < nl) {
-                const int s = lpq == 2 ? lane >> 1 : lpq == 4 ? lane >> 2 : lane / lpq, g = lane - s * lpq;
-                const size_t base = (((size_t)s * nq_pad + q) * lpq + g) * KL;
-#pragma unroll
-                for (int e = 0; e < KL; e++) {
-                    const double v = part_d[base + e];
-                    d[e] = v < 4294967295.0 ? (unsigned)v : DINF;
-                    id[e] = part_i[base + e];
-                    c2 += d[e] != DINF ? 1 : 0;   // a prefix
-                }
-            }
-            const int cs2 = (!first_step && lane < KP && siv >= 0 && sdv < KNN_INF) ? 1 : 0;
-            const int ct2 = c2 + cs2;
-            int pre2 = 0, C2 = 0;
-#pragma unroll
-            for (int b = 0; b < 5; b++) {
-                const unsigned long long m = __ballot((ct2 >> b) & 1);
-                pre2 += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) << b;
-                C2 += __popcll(m) << b;
-            }
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int e = 0; e < KL; e++)
-                if (e < c2) buf[pre2 + e] = ((unsigned long long)d[e] << 32) | (unsigned)id[e];
-            if (cs2) buf[pre2 + c2] = ((unsigned long long)(unsigned)sdv << 32) | (unsigned)siv;
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            for (int b0 = 0; b0 < C2; b0 += 64) {
-                const int my = b0 + lane;
-                const unsigned long long x = my < C2 ? buf[my] : ~0ull;
-                int r = 0;
-                for (int j = 0; j < C2; j++) r += buf[j] < x ? 1 : 0;
-                const unsigned long long a0 = __ballot(my < C2 && r == k - 1);
-                if (a0) tau = (double)(unsigned)(__shfl(x, __builtin_ctzll(a0)) >> 32);
-                const unsigned long long a1 = __ballot(my < C2 && r == k);
-                if (a1) tk1 = (double)(unsigned)(__shfl(x, __builtin_ctzll(a1)) >> 32);
-            }
-        }
-        if (!ok && lane == 0) {
-            fa.fail_list[atomicAdd(fa.fail_count, 1)] = q;
-            fa.fbound[q] = (fa.force_fail || mode != KNN_MODE_INT) ? KNN_INF : sqrt(tau);
-            // k + 1 distinct rows lie at or below the (k+1)-th kept key: a
-            // valid bound for the int8 re-search to start from (knn_engine.c
-            // research8; INT mode only, the search is over)
-            if (mode == KNN_MODE_INT && !fa.force_fail)
-                qthr[q] = (unsigned long long)__double_as_longlong(sizeof(TE) == 4 ? (double)__double2float_ru(tk1) : tk1);
-        }
-        return;
-    }
-    if (lane < KP && lane >= (C < kk ? C : kk)) {
-        st_d[(size_t)q * KP + lane] = KNN_INF;
-        st_x[(size_t)q * KP + lane] = KNN_INF;
-        st_i[(size_t)q * KP + lane] = -1;
-    }
-    if (lane == 0) {
-        st_T[2 * (size_t)q] = T;
-        st_T[2 * (size_t)q + 1] = Td;
-    }
+    rank_merge<TE, KP, KL, 64>((LDS_AS unsigned long long *)mr_buf + (size_t)wave * cap, q, true, lane, part_d, part_i,
+                               part_T, nsplit, lpq, nq_pad, first_step, st_d, st_x, st_i, st_T, k, qthr, fin, fa);
 }
 
-// ---------------------------------------------------------------------------
-// k_merge_rank16: k_merge_rank's fin pass without a state (the search's only
-// merge: a P = 1 search) when a query has at most 16 lists -- 16 lanes a
-// query, 4 queries a wave.  Same bounds, keys, ranks, records, certificate
-// and fallback as k_merge_rank (fin, first_step); a lane ranks the group's
-// candidates gl, gl + 16, ... against all of them.  k_merge_rank ran one
-// wave a query with 14 of 64 lanes holding lists: 651 VALU instructions a
-// query, most of them per-query work (loads, conversions, compaction, the
-// records' sqrt) done once a wave (SQ counters, round 6).
-// ---------------------------------------------------------------------------
+// k_merge_rank16: 16 lanes a query, 4 queries a wave, 16 a workgroup; the
+// search's only merge (a P = 1 search: no state, fin) when a query has at
+// most 16 lists.  k_merge_rank ran one wave a query with 14 of 64 lanes
+// holding lists: 651 VALU instructions a query, most of them per-query work
+// (loads, conversions, compaction, the records' sqrt) done once a wave (SQ
+// counters, round 6).  Static LDS: CAPG keys a group.
 template <typename TE, int KL>
 __global__ __launch_bounds__(256) void k_merge_rank16(
     const double *__restrict__ part_d, const int *__restrict__ part_i, const double *__restrict__ part_T,
@@ -1704,225 +1781,12 @@ __global__ __launch_bounds__(256) void k_merge_rank16(
 {
     constexpr int CAPG = 16 * KL + 4;   // a group's keys (+ pad: groups 32 bytes apart mod 256)
     __shared__ __attribute__((aligned(16))) unsigned long long r16_buf[16 * CAPG];
-    constexpr unsigned DINF = 0xffffffffu;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 4, gl = lane & 15;
-    const int q = blockIdx.x * 16 + wave * 4 + grp;
+    const int grp = threadIdx.x >> 4, gl = threadIdx.x & 15;
+    const int q = blockIdx.x * 16 + grp;
     const bool qv = q < nq;
     if (__ballot(qv) == 0ull) return;   // wave-uniform; no workgroup barrier below
-    LDS_AS unsigned long long *buf = (LDS_AS unsigned long long *)r16_buf + (size_t)(wave * 4 + grp) * CAPG;
-    const unsigned long long gmask = 0xffffull << (16 * grp);
-    const unsigned long long ltmask = (1ull << lane) - 1ull;
-    const int nl = qv ? lpq * nsplit : 0;
-    const int qq = qv ? q : 0;
-    const double qb = __longlong_as_double((long long)qthr[qq]);
-    const double B = qb >= 4294967294.0 ? 4294967294.0 : floor(qb);
-    const unsigned Bu = (unsigned)B;
-    double T = KNN_INF;
-    if (qv && gl < nsplit) T = part_T[(size_t)gl * nq_pad + q];
-    const int mode = knn_mode_lim<TE>(fa.meta, fa.n, fa.lim);
-
-    unsigned d[KL];
-    int id[KL];
-#pragma unroll
-    for (int e = 0; e < KL; e++) {
-        d[e] = DINF;
-        id[e] = 0;
-    }
-    int c = 0;
-    if (gl < nl) {
-        const int sp = lpq == 2 ? gl >> 1 : lpq == 4 ? gl >> 2 : gl / lpq, g = gl - sp * lpq;
-        const size_t base = (((size_t)sp * nq_pad + q) * lpq + g) * KL;
-#pragma unroll
-        for (int e = 0; e < 4 && e < KL; e++) {
-            const double v = part_d[base + e];
-            d[e] = v < 4294967295.0 ? (unsigned)v : DINF;
-            id[e] = part_i[base + e];
-        }
-        if (KL > 4 && d[3] <= Bu) {
-#pragma unroll
-            for (int e = 4; e < KL; e++) {
-                const double v = part_d[base + e];
-                d[e] = v < 4294967295.0 ? (unsigned)v : DINF;
-                id[e] = part_i[base + e];
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < KL; e++) c += d[e] <= Bu ? 1 : 0;   // a prefix
-    }
-    for (int off = 8; off > 0; off >>= 1) T = fmin(T, __shfl_xor(T, off));   // within the group
-
-    // the tighter bound: the (k+1)-th smallest key among the lists' first
-    // HD entries (k_merge_rank)
-    unsigned long long lim = ~0ull;
-    {
-        constexpr int HD = KL < 4 ? KL : 4;
-        const int hh = c < HD ? c : HD;
-        int preh = 0, CH = 0;
-#pragma unroll
-        for (int b = 0; b < 3; b++) {
-            const unsigned long long m = __ballot((hh >> b) & 1) & gmask;
-            preh += __popcll(m & ltmask) << b;
-            CH += __popcll(m) << b;
-        }
-#pragma unroll
-        for (int e = 0; e < HD; e++)
-            if (CH > k && e < hh) buf[preh + e] = ((unsigned long long)d[e] << 32) | (unsigned)id[e];
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (CH > k) {   // (group-uniform)
-            unsigned long long bk = ~0ull;
-            for (int b0 = 0; b0 < CH; b0 += 64) {
-                unsigned long long x[4];
-                int r[4];
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const int my = b0 + gl + 16 * t;
-                    x[t] = my < CH ? buf[my] : ~0ull;
-                    r[t] = 0;
-                }
-                int j = 0;
-                for (; j + 4 <= CH; j += 4) {
-                    const knn_u64x2 u = *(const LDS_AS knn_u64x2 *)(buf + j);
-                    const knn_u64x2 w = *(const LDS_AS knn_u64x2 *)(buf + j + 2);
-#pragma unroll
-                    for (int t = 0; t < 4; t++)
-                        r[t] += (u.x < x[t] ? 1 : 0) + (u.y < x[t] ? 1 : 0) + (w.x < x[t] ? 1 : 0) + (w.y < x[t] ? 1 : 0);
-                }
-                for (; j < CH; j++) {
-                    const unsigned long long u = buf[j];
-#pragma unroll
-                    for (int t = 0; t < 4; t++) r[t] += u < x[t] ? 1 : 0;
-                }
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const unsigned long long at = __ballot(b0 + gl + 16 * t < CH && r[t] == k) & gmask;
-                    if (at) bk = __shfl(x[t], __builtin_ctzll(at));
-                }
-            }
-            lim = bk;
-            int c2 = 0;
-#pragma unroll
-            for (int e = 0; e < KL; e++)
-                c2 += (e < c && (((unsigned long long)d[e] << 32) | (unsigned)id[e]) <= bk) ? 1 : 0;
-            c = c2;
-        }
-        __builtin_amdgcn_wave_barrier();   // (the subset's slots are overwritten below)
-    }
-    // compaction: the group's entries at or below both bounds
-    int pre = 0, C = 0;
-#pragma unroll
-    for (int b = 0; b < 5; b++) {
-        const unsigned long long m = __ballot((c >> b) & 1) & gmask;
-        pre += __popcll(m & ltmask) << b;
-        C += __popcll(m) << b;
-    }
-    {
-        int w = pre;
-#pragma unroll
-        for (int e = 0; e < KL; e++) {
-            const unsigned long long key = ((unsigned long long)d[e] << 32) | (unsigned)id[e];
-            if (d[e] <= Bu && key <= lim) buf[w++] = key;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-
-    if (blockIdx.x == 0 && threadIdx.x == 0) *fa.mode_out = mode;
-    // slots past the candidates: {inf, 0, 0}
-    for (int p = gl; p < k; p += 16)
-        if (qv && p >= C) {
-            knn_neighbour_t rec;
-            rec.distance = KNN_INF;
-            rec.idx = 0;
-            rec.label = 0;
-            fa.out[(size_t)q * k + p] = rec;
-        }
-    double tau = KNN_INF, tk1 = KNN_INF;
-    for (int b0 = 0; b0 < C; b0 += 64) {   // (group-uniform trip count)
-        unsigned long long x[4];
-        int r[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int my = b0 + gl + 16 * t;
-            x[t] = my < C ? buf[my] : ~0ull;
-            r[t] = 0;
-        }
-        const int nt = (C - b0 + 15) >> 4;   // live slots a lane this round (group-uniform)
-        int j = 0;
-        for (; j + 4 <= C; j += 4) {
-            const knn_u64x2 u = *(const LDS_AS knn_u64x2 *)(buf + j);
-            const knn_u64x2 w = *(const LDS_AS knn_u64x2 *)(buf + j + 2);
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-                if (t < nt)
-                    r[t] += (u.x < x[t] ? 1 : 0) + (u.y < x[t] ? 1 : 0) + (w.x < x[t] ? 1 : 0) + (w.y < x[t] ? 1 : 0);
-        }
-        for (; j < C; j++) {
-            const unsigned long long u = buf[j];
-#pragma unroll
-            for (int t = 0; t < 4; t++) r[t] += u < x[t] ? 1 : 0;
-        }
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const bool live = b0 + gl + 16 * t < C;
-            if (live && r[t] < k) {
-                knn_neighbour_t rec;
-                rec.distance = sqrt((double)(unsigned)(x[t] >> 32));
-                rec.idx = (int)(unsigned)x[t] + 1;
-                rec.label = 0;
-                fa.out[(size_t)q * k + r[t]] = rec;
-            }
-            const unsigned long long a0 = __ballot(live && r[t] == k - 1) & gmask;
-            if (a0) tau = (double)(unsigned)(__shfl(x[t], __builtin_ctzll(a0)) >> 32);
-            const unsigned long long a1 = __ballot(live && r[t] == k) & gmask;
-            if (a1) tk1 = (double)(unsigned)(__shfl(x[t], __builtin_ctzll(a1)) >> 32);
-        }
-    }
-    const bool ok = mode == KNN_MODE_INT && !fa.force_fail && (T == KNN_INF || (C >= k && tau < T));
-    if (qv && !ok && C < k + 1 && mode == KNN_MODE_INT && !fa.force_fail) {
-        // fewer than k + 1 entries under the bounds: the k-th and (k+1)-th
-        // over every entry of the lists (k_merge_rank's fallback)
-        int c2 = 0;
-        if (gl < nl) {
-            const int sp = lpq == 2 ? gl >> 1 : lpq == 4 ? gl >> 2 : gl / lpq, g = gl - sp * lpq;
-            const size_t base = (((size_t)sp * nq_pad + q) * lpq + g) * KL;
-#pragma unroll
-            for (int e = 0; e < KL; e++) {
-                const double v = part_d[base + e];
-                d[e] = v < 4294967295.0 ? (unsigned)v : DINF;
-                id[e] = part_i[base + e];
-                c2 += d[e] != DINF ? 1 : 0;   // a prefix
-            }
-        }
-        int pre2 = 0, C2 = 0;
-#pragma unroll
-        for (int b = 0; b < 5; b++) {
-            const unsigned long long m = __ballot((c2 >> b) & 1) & gmask;
-            pre2 += __popcll(m & ltmask) << b;
-            C2 += __popcll(m) << b;
-        }
-#pragma unroll
-        for (int e = 0; e < KL; e++)
-            if (e < c2) buf[pre2 + e] = ((unsigned long long)d[e] << 32) | (unsigned)id[e];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        for (int my0 = 0; my0 < C2; my0 += 16) {
-            const int my = my0 + gl;
-            const unsigned long long x = my < C2 ? buf[my] : ~0ull;
-            int r = 0;
-            for (int j = 0; j < C2; j++) r += buf[j] < x ? 1 : 0;
-            const unsigned long long a0 = __ballot(my < C2 && r == k - 1) & gmask;
-            if (a0) tau = (double)(unsigned)(__shfl(x, __builtin_ctzll(a0)) >> 32);
-            const unsigned long long a1 = __ballot(my < C2 && r == k) & gmask;
-            if (a1) tk1 = (double)(unsigned)(__shfl(x, __builtin_ctzll(a1)) >> 32);
-        }
-    }
-    if (qv && !ok && gl == 0) {
-        fa.fail_list[atomicAdd(fa.fail_count, 1)] = q;
-        fa.fbound[q] = (fa.force_fail || mode != KNN_MODE_INT) ? KNN_INF : sqrt(tau);
-        if (mode == KNN_MODE_INT && !fa.force_fail)
-            qthr[q] = (unsigned long long)__double_as_longlong(sizeof(TE) == 4 ? (double)__double2float_ru(tk1) : tk1);
-    }
+    rank_merge<TE, 0, KL, 16>((LDS_AS unsigned long long *)r16_buf + (size_t)grp * CAPG, q, qv, gl, part_d, part_i,
+                              part_T, nsplit, lpq, nq_pad, 1, nullptr, nullptr, nullptr, nullptr, k, qthr, 1, fa);
 }
 
 // ---------------------------------------------------------------------------
@@ -2848,6 +2712,23 @@ extern "C" int knn_launch_merge_n(int dtype, int kp, int k, const double *part_d
 #undef CALL
 }
 
+// f(element, KP, KL) with the rank kernels' template arguments as values:
+// double or float, KNN_KP_M or KNN_KP, KNN_I8_KL_S or KNN_I8_KL
+template <typename F>
+static void rank_dispatch(bool f64, bool kp_m, bool kl_s, F f)
+{
+    auto with_kl = [&](auto te, auto kp) {
+        if (kl_s) f(te, kp, std::integral_constant<int, KNN_I8_KL_S>());
+        else f(te, kp, std::integral_constant<int, KNN_I8_KL>());
+    };
+    auto with_kp = [&](auto te) {
+        if (kp_m) with_kl(te, std::integral_constant<int, KNN_KP_M>());
+        else with_kl(te, std::integral_constant<int, KNN_KP>());
+    };
+    if (f64) with_kp(double());
+    else with_kp(float());
+}
+
 extern "C" int knn_launch_merge_rank(int dtype, int kp, int kl, int k, const double *part_d, const int *part_i,
                                      const double *part_T, int nsplit, int lpq, int nq, int nq_pad,
                                      int first_step, double *st_d, double *st_x, int *st_i, double *st_T,
@@ -2869,40 +2750,26 @@ extern "C" int knn_launch_merge_rank(int dtype, int kp, int kl, int k, const dou
     if (lpq < 1 || nsplit < 1 || lpq * nsplit > 64 || k <= 0 || k > kp || kp > 64 || nsplit > 64 ||
         (kl != KNN_I8_KL_S && kl != KNN_I8_KL))
         return KNN_ERR_INVALID;
-#ifndef KNN_NO_RANK16
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long *qt = (unsigned long long *)qthr;
     if (fin && first_step && lpq * nsplit <= 16) {
-        // the search's only merge (P = 1): 16 lanes a query
-        const dim3 g16((unsigned)((nq + 15) / 16));
-        hipStream_t s16 = (hipStream_t)stream;
-#define RANK16(T, KL)                                                                              \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge_rank16<T, KL>), g16, dim3(256), 0, s16, part_d, part_i, \
-                           part_T, nsplit, lpq, nq, nq_pad, k, (unsigned long long *)qthr, fa)
-        if (dtype == KNN_F64 && kl == KNN_I8_KL_S) RANK16(double, KNN_I8_KL_S);
-        else if (dtype == KNN_F64) RANK16(double, KNN_I8_KL);
-        else if (kl == KNN_I8_KL_S) RANK16(float, KNN_I8_KL_S);
-        else RANK16(float, KNN_I8_KL);
-#undef RANK16
+        // the search's only merge (P = 1): 16 lanes a query (no state: any kp)
+        const dim3 grid((unsigned)((nq + 15) / 16));
+        rank_dispatch(dtype == KNN_F64, false, kl == KNN_I8_KL_S, [&](auto te, auto, auto klc) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge_rank16<decltype(te), decltype(klc)::value>), grid, dim3(256),
+                               0, s, part_d, part_i, part_T, nsplit, lpq, nq, nq_pad, k, qt, fa);
+        });
         return hip_status();
     }
-#endif
+    if ((dtype != KNN_F64 && dtype != KNN_F32) || (kp != KNN_KP && kp != KNN_KP_M)) return KNN_ERR_INVALID;
     const int cap = (lpq * nsplit * kl + kp + 1) & ~1;   // every candidate; 16-byte rows
     const size_t lds = 4 * (size_t)cap * sizeof(unsigned long long);
     const dim3 grid((unsigned)((nq + 3) / 4));
-    hipStream_t s = (hipStream_t)stream;
-#define RANK(T, KP, KL)                                                                            \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge_rank<T, KP, KL>), grid, dim3(256), lds, s, part_d, part_i, \
-                       part_T, nsplit, lpq, nq, nq_pad, first_step, st_d, st_x, st_i, st_T, k,       \
-                       (unsigned long long *)qthr, cap, fin, fa)
-    if (dtype == KNN_F64 && kp == KNN_KP && kl == KNN_I8_KL_S) RANK(double, KNN_KP, KNN_I8_KL_S);
-    else if (dtype == KNN_F64 && kp == KNN_KP) RANK(double, KNN_KP, KNN_I8_KL);
-    else if (dtype == KNN_F64 && kp == KNN_KP_M && kl == KNN_I8_KL_S) RANK(double, KNN_KP_M, KNN_I8_KL_S);
-    else if (dtype == KNN_F64 && kp == KNN_KP_M) RANK(double, KNN_KP_M, KNN_I8_KL);
-    else if (dtype == KNN_F32 && kp == KNN_KP && kl == KNN_I8_KL_S) RANK(float, KNN_KP, KNN_I8_KL_S);
-    else if (dtype == KNN_F32 && kp == KNN_KP) RANK(float, KNN_KP, KNN_I8_KL);
-    else if (dtype == KNN_F32 && kp == KNN_KP_M && kl == KNN_I8_KL_S) RANK(float, KNN_KP_M, KNN_I8_KL_S);
-    else if (dtype == KNN_F32 && kp == KNN_KP_M) RANK(float, KNN_KP_M, KNN_I8_KL);
-    else return KNN_ERR_INVALID;
-#undef RANK
+    rank_dispatch(dtype == KNN_F64, kp == KNN_KP_M, kl == KNN_I8_KL_S, [&](auto te, auto kpc, auto klc) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge_rank<decltype(te), decltype(kpc)::value, decltype(klc)::value>),
+                           grid, dim3(256), lds, s, part_d, part_i, part_T, nsplit, lpq, nq, nq_pad, first_step,
+                           st_d, st_x, st_i, st_T, k, qt, cap, fin, fa);
+    });
     return hip_status();
 }
 
