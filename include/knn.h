@@ -57,10 +57,12 @@
  *   KNN_XCD_ORDER=1 / 0   distance launches in the XCD-grouped / the
  *                         split-major workgroup order (unset: XCD-grouped
  *                         for split-filter launches of <= 2 splits)
- *   KNN_QUERY_BLOCK=rows  knn_query folds the corpus in blocks of this many
- *                         rows instead of the capacity it chooses
- *   KNN_QUERY_TILE=rows   knn_query searches the queries in tiles of this many
- *                         rows instead of all at once (up to 2^18)
+ *   KNN_QUERY_BLOCK=rows  knn_query and knn_index_create fold / pack the corpus
+ *                         in blocks of this many rows instead of the capacity
+ *                         they choose
+ *   KNN_QUERY_TILE=rows   knn_query and knn_index_query search the queries in
+ *                         tiles of this many rows instead of all at once (up
+ *                         to 2^18)
  *   KNN_MAT / KNN_MPI_COMPAT  the CLIs: .mat path, bug-compatible mode
  *   (mpiknn/ring.py: KNN_NO_S8=1 packs element blocks, not the byte block
  *   of knn_block_pack_s8)
@@ -102,7 +104,10 @@ enum knn_status {
 };
 
 enum knn_layout { KNN_COLMAJOR = 0, KNN_ROWMAJOR = 1 };
-enum knn_dtype  { KNN_F64 = 0, KNN_F32 = 1 };
+/* KNN_U8: unsigned 8-bit elements.  A SOURCE type only (src_dtype of
+ * knn_block_pack_dt / knn_block_pack_s8, and of the knn_index_* calls): no
+ * block, context or search has it as its dtype. */
+enum knn_dtype  { KNN_F64 = 0, KNN_F32 = 1, KNN_U8 = 2 };
 enum knn_vote   { KNN_VOTE_SERIAL = 0, KNN_VOTE_MPI = 1, KNN_VOTE_MAJORITY = 2 };
 
 /* Largest k served: KNN_F64 32 (the reference fixes NN = 30, serial:8 /
@@ -201,7 +206,66 @@ KNN_API int knn_search_mpi_compat(const double *X, size_t m, size_t n, int layou
 KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, size_t n, int layout,
                       const double *labels, int k, int dtype, int flags, knn_neighbour_t *out);
 
-/* Search wall time of the last knn_search() / knn_query() on this thread, seconds: the
+/* ---------------------------------------------------------------------- *
+ * Resident corpus index -- knn_query split where a server needs it split:
+ * the corpus is uploaded, packed and reduced ONCE (knn_index_create) and
+ * stays on the device; each knn_index_query then costs its own queries only
+ * (blk:217-242 with the received blocks already in place).
+ *
+ * knn_index_create: X is m x n in `layout`, of src_dtype KNN_F64, KNN_F32 or
+ * KNN_U8, uploaded in that type (no widening on the host; with
+ * KNN_INDEX_DEVICE_SRC X is a device pointer on device 0 and is read in
+ * place).  The index holds the element blocks of `dtype` (KNN_F64 / KNN_F32,
+ * as knn_search; capacity as knn_query chooses it, KNN_QUERY_BLOCK overrides),
+ * the byte blocks too when the corpus's own reduced meta passes
+ * knn_s8_spec_ok, the host copy of that meta and a copy of labels (nullable,
+ * m doubles).  The uploaded source is freed before the call returns: the
+ * caller may free or overwrite X.
+ *
+ * knn_index_query: knn_query's sequence for one batch against the resident
+ * blocks -- pack the query tiles (Q: mq x n in `layout`, of src_dtype, its
+ * own; KNN_QUERY_TILE and the 2^18 limit as in knn_query), MAX-reduce their
+ * meta with the stored corpus meta, take the byte path when the index has
+ * byte blocks and the reduced meta passes knn_s8_spec_ok (else the element
+ * path), then per tile begin, fold, end, int8 re-search, exact rescan.  out:
+ * mq*k records, exactly those of knn_query(X, Q, ...) on the same values on
+ * every path; queries take the ids m.. as there; .label from the index's
+ * labels (0 without).  flags: KNN_QUERY_KEEP_ZERO as in knn_query;
+ * KNN_INDEX_DEVICE_SRC: Q is a device pointer; KNN_INDEX_DEVICE_OUT: out is
+ * a device pointer, written by the search itself (.label stays 0:
+ * knn_classify_device fills it).  The context and the query-tile buffers are
+ * kept between calls and recreated only when k changes or a batch needs more
+ * tile capacity than is allocated (capacity grows geometrically from 128
+ * rows); no result depends on the calls before it.
+ * knn_last_search_seconds() reports the call's device span, query pack
+ * through the last tile's records -- no corpus work, because none is done.
+ *
+ * knn_index_info (every output nullable): the shape, the number of resident
+ * corpus blocks, the device bytes the index holds (element blocks, byte
+ * blocks, tile buffers, records, and the context's buffers as an estimate
+ * restated from their sizes) and knn_ctx_contraction_bits of
+ * the last query (8, 16, 32 or 64; 0 before the first).
+ *
+ * KNN_ERR_INVALID: NULL index, X, Q or out, zero m, mq or n, k <= 0, a bad
+ * layout, unknown flag bits, m + mq > INT32_MAX; KNN_ERR_UNSUPPORTED: an
+ * unknown src_dtype, dtype not KNN_F64 / KNN_F32, k above the dtype's limit
+ * -- all before any device call.  An index is used from one host thread at a
+ * time.  (Integer corpora inside an 8-bit window but outside [0, 255] are not
+ * knn_s8_spec_ok: the engine converts their element blocks to byte blocks
+ * inside each search, as in knn_query -- exact, but per call.)
+ * ---------------------------------------------------------------------- */
+typedef struct knn_index knn_index_t;
+#define KNN_INDEX_DEVICE_SRC 2   /* X / Q is a device pointer on the index's device        */
+#define KNN_INDEX_DEVICE_OUT 4   /* out is a device pointer (knn_index_query only)         */
+KNN_API int knn_index_create(knn_index_t **index, const void *X, size_t m, size_t n, int layout,
+                             int src_dtype, const double *labels, int dtype, int flags);
+KNN_API int knn_index_query(knn_index_t *index, const void *Q, size_t mq, int layout, int src_dtype,
+                            int k, int flags, knn_neighbour_t *out);
+KNN_API int knn_index_info(const knn_index_t *index, size_t *m, size_t *n, int *nblocks,
+                           size_t *device_bytes, int *last_bits);
+KNN_API int knn_index_destroy(knn_index_t *index);
+
+/* Search wall time of the last knn_search() / knn_query() / knn_index_query() on this thread, seconds: the
  * span the reference times (serial:70-98, blk:120-250) -- device compute
  * only, excluding load, H2D, D2H and vote. */
 KNN_API double knn_last_search_seconds(void);
@@ -310,7 +374,8 @@ KNN_API int knn_split_pack(void *d_dst, const void *d_block, size_t cap, size_t 
 KNN_API int knn_block_pack(void *d_block, size_t cap, size_t rows, size_t n, const double *d_src,
                    size_t ld, int layout, void *stream);
 /* Pack into a block of element type dtype from a source of src_dtype
- * (fp64 or fp32 device array, same layouts). */
+ * (fp64, fp32 or KNN_U8 device array, same layouts).  For the same values the
+ * block from a KNN_U8 source is byte for byte the block from the fp64 one. */
 KNN_API int knn_block_pack_dt(void *d_block, int dtype, size_t cap, size_t rows, size_t n,
                       const void *d_src, int src_dtype, size_t ld, int layout, void *stream);
 
@@ -348,7 +413,10 @@ KNN_API int knn_ctx_begin_meta(knn_ctx_t *ctx, const void *d_qblock, size_t q_ca
  * it (no element block, no conversion; a ring moves it as the shadow block),
  * otherwise pack the element block (knn_block_pack_dt) and knn_ctx_begin_meta.
  * One read of the source, 1 byte written an element (replaces the pack of
- * blk:100-109 plus the element -> byte conversion). */
+ * blk:100-109 plus the element -> byte conversion).  src_dtype KNN_U8: the
+ * bytes are x ^ 0x80, norms and meta in integer arithmetic -- byte for byte
+ * the block packed from the fp64 array of the same values (1 byte read, 1
+ * written an element). */
 KNN_API size_t knn_s8_block_bytes(size_t cap, size_t n);
 KNN_API size_t knn_s8_block_meta_offset(size_t cap, size_t n);
 KNN_API int knn_block_pack_s8(void *d_sblock, int dtype, size_t cap, size_t rows, size_t n, const void *d_src,

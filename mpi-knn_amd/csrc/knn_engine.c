@@ -5,8 +5,8 @@
  *   knn_block_pack  -> k_pack_col / k_pack_row (blk:100-109 packing)
  *   knn_ctx_step    -> k_dist_topk + k_merge (one ring step, blk:217-242)
  *   knn_ctx_end     -> k_finalize            (+ rescan pass when needed)
- * and implements the one-call knn_search() and knn_query() of include/knn.h
- * on top.
+ * and implements the one-call knn_search() of include/knn.h on top
+ * (knn_query() and the resident index: knn_index.c).
  */
 #include "knn_internal.h"
 
@@ -34,6 +34,7 @@ struct knn_ctx {
     int device;
     int dtype;          /* element type of the packed blocks (KNN_F64 / KNN_F32) */
     size_t nq, nq_pad, n, block_cap;
+    size_t nq_cap;      /* the nq_pad the per-query buffers were allocated for (knn_ctx_set_rows) */
     int k;
     int kp, kl;         /* state capacity / per-lane list length serving k */
     int xord;           /* workgroup order: 0 split-major, 1 XCD-grouped, -1 by the launch (xord_for) */
@@ -185,6 +186,8 @@ double knn_last_search_seconds(void) { return g_last_search_s; }
 void knn_set_last_search_seconds(double s) { g_last_search_s = s; }
 
 static int dtype_ok(int dtype) { return dtype == KNN_F64 || dtype == KNN_F32; }
+/* a pack source: an element type, or unsigned bytes (KNN_U8, source only) */
+static int src_dtype_ok(int dtype) { return dtype_ok(dtype) || dtype == KNN_U8; }
 
 size_t knn_block_meta_offset_dt(size_t cap, size_t n, int dtype)
 {
@@ -283,7 +286,7 @@ int knn_block_pack_dt(void *d_block, int dtype, size_t cap, size_t rows, size_t 
                       const void *d_src, int src_dtype, size_t ld, int layout, void *stream)
 {
     if (!d_block || !d_src || rows == 0 || n == 0 || rows > cap || cap > 0x7fffffffULL ||
-        n > 0x7fffffffULL || !dtype_ok(dtype) || !dtype_ok(src_dtype))
+        n > 0x7fffffffULL || !dtype_ok(dtype) || !src_dtype_ok(src_dtype))
         return KNN_ERR_INVALID;
     if (layout == KNN_COLMAJOR ? ld < rows : (layout == KNN_ROWMAJOR ? ld < n : 1))
         return KNN_ERR_INVALID;
@@ -297,7 +300,7 @@ int knn_block_pack_s8(void *d_sblock, int dtype, size_t cap, size_t rows, size_t
                       int src_dtype, size_t ld, int layout, void *stream)
 {
     if (!d_sblock || !d_src || rows == 0 || n == 0 || rows > cap || cap > 0x7fffffffULL || n > KNN_I8_MAX_N ||
-        !dtype_ok(dtype) || !dtype_ok(src_dtype))
+        !dtype_ok(dtype) || !src_dtype_ok(src_dtype))
         return KNN_ERR_INVALID;
     if (layout == KNN_COLMAJOR ? ld < rows : (layout == KNN_ROWMAJOR ? ld < n : 1)) return KNN_ERR_INVALID;
     return knn_launch_pack_s8(d_sblock, dtype, cap, rows, n, d_src, src_dtype, ld, layout, stream);
@@ -473,6 +476,19 @@ int knn_ctx_profile_merge(knn_ctx_t *c, double *merge_kernel_ms, int *merges, do
     return KNN_OK;
 }
 
+/* KNN_OK when `device` is a gfx950 of this node (*cus: its compute units) */
+int knn_device_probe(int device, int *cus)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
+        return KNN_ERR_NODEVICE;
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return KNN_ERR_NODEVICE;
+    if (cus) *cus = prop.multiProcessorCount;
+    return KNN_OK;
+}
+
 int knn_ctx_create_dt(knn_ctx_t **out, int device, size_t nq, size_t n, size_t block_cap, int k,
                       int dtype)
 {
@@ -480,12 +496,8 @@ int knn_ctx_create_dt(knn_ctx_t **out, int device, size_t nq, size_t n, size_t b
         k > (dtype == KNN_F32 ? KNN_MAX_K_F32 : KNN_MAX_K) || nq > 0x7fffffffULL ||
         block_cap > 0x7fffffffULL)
         return KNN_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
-        return KNN_ERR_NODEVICE;
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return KNN_ERR_NODEVICE;
+    int cus = 0;
+    RCHK(knn_device_probe(device, &cus));
     HIPCHK(hipSetDevice(device));
 
     knn_ctx_t *c = (knn_ctx_t *)calloc(1, sizeof(*c));
@@ -494,6 +506,7 @@ int knn_ctx_create_dt(knn_ctx_t **out, int device, size_t nq, size_t n, size_t b
     c->dtype = dtype;
     c->nq = nq;
     c->nq_pad = knn_round_up(nq, KNN_TQ);
+    c->nq_cap = c->nq_pad;
     c->n = n;
     c->block_cap = block_cap;
     c->k = k;
@@ -511,7 +524,7 @@ int knn_ctx_create_dt(knn_ctx_t **out, int device, size_t nq, size_t n, size_t b
         const char *xe = getenv("KNN_XCD_ORDER");
         c->xord = xe && xe[0] == '1' ? 1 : (xe && xe[0] == '0' ? 0 : -1);
     }
-    c->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    c->cus = cus > 0 ? cus : 256;
 
     const size_t np = c->nq_pad;
     int ok = 1;
@@ -565,6 +578,49 @@ int knn_ctx_destroy(knn_ctx_t *c)
     ctx_free_buffers(c);
     free(c);
     return KNN_OK;
+}
+
+/* The context's next searches take `rows` queries, within the capacity it
+ * was created with (a query tile of knn_index.c; research8_run does the same
+ * for its sub-context).  The split model depends on the query count, so its
+ * cache starts over when that changes. */
+int knn_ctx_set_rows(knn_ctx_t *c, size_t rows)
+{
+    if (!c || rows == 0 || knn_round_up(rows, KNN_TQ) > c->nq_cap) return KNN_ERR_INVALID;
+    if (rows != c->nq) memset(c->split_cache, 0, sizeof(c->split_cache));
+    c->nq = rows;
+    c->nq_pad = knn_round_up(rows, KNN_TQ);
+    return KNN_OK;
+}
+
+/* Device bytes the context holds: its per-query state, the conversion
+ * buffers, partial lists, rescan lists and query order it has grown so far,
+ * and its re-search sub-context.  A restatement of the allocation sizes in
+ * this file, not a counter kept at every hipMalloc: an estimate for
+ * knn_index_info, to be kept in step with them by hand. */
+size_t knn_ctx_device_bytes(const knn_ctx_t *c)
+{
+    if (!c) return 0;
+    const size_t np = c->nq_cap;
+    size_t b = np * (sizeof(double) + 4 * sizeof(unsigned long long) + 2 * sizeof(double) + sizeof(int) +
+                     sizeof(double)) +
+               np * c->kp * (2 * sizeof(double) + sizeof(int)) + 2 * sizeof(int);
+    b += c->qsh_bytes + c->qs8_bytes + c->qsp_bytes;
+    for (int s = 0; s < KNN_PSETS; s++) {
+        if (c->csh[s]) b += c->csh_bytes;
+        if (c->cs8[s]) b += knn_s8_bytes(c->block_cap, c->n);
+        if (c->csp[s]) b += c->csp_bytes;
+        b += c->cspm_bytes[s];
+    }
+    for (int pr = 0; pr < KNN_PSETS / 2; pr++)
+        b += (size_t)c->pp_cap[pr] * (c->pp_per[pr] * (sizeof(double) + sizeof(int)) + np * sizeof(double));
+    b += c->rs_cap * c->kp * (sizeof(double) + sizeof(int));
+    b += c->ord_cap * 4 * sizeof(int) + (c->ord_cap ? c->ord_tmp_bytes : 0);
+    if (c->fail_list2) b += np * sizeof(int);
+    if (c->sub)
+        b += knn_ctx_device_bytes(c->sub) + knn_s8_bytes(c->sub_cap, c->n) +
+             c->sub_cap * ((size_t)c->k * sizeof(knn_neighbour_t) + 1);
+    return b;
 }
 
 int knn_ctx_contraction_bits(const knn_ctx_t *c)
@@ -1040,7 +1096,11 @@ static int ensure_part_buffers(knn_ctx_t *c, int nsplit, int set, int off)
         const int cap = need > 2 * nsplit ? need : 2 * nsplit;
         if (hipMalloc((void **)&c->pp_d[pr], (size_t)cap * per * sizeof(double)) != hipSuccess ||
             hipMalloc((void **)&c->pp_i[pr], (size_t)cap * per * sizeof(int)) != hipSuccess ||
-            hipMalloc((void **)&c->pp_T[pr], (size_t)cap * c->nq_pad * sizeof(double)) != hipSuccess)
+            /* (the bounds by the context's capacity, not this search's rows: `per` can
+             * come out equal for two row counts under different list shapes -- 384
+             * rows of 4 x 16 lists, 1024 rows of 2 x 12 -- and then nothing is
+             * reallocated between them, knn_ctx_set_rows) */
+            hipMalloc((void **)&c->pp_T[pr], (size_t)cap * c->nq_cap * sizeof(double)) != hipSuccess)
             return KNN_ERR_NOMEM;
         c->pp_cap[pr] = cap;
     }
@@ -1643,7 +1703,7 @@ static int research8_run(knn_ctx_t *c, int nblk, const void *const *blk, const s
         if (hipMalloc(&c->sub_q8, knn_s8_bytes(cap, c->n)) != hipSuccess ||
             hipMalloc((void **)&c->sub_out, cap * (size_t)c->k * sizeof(knn_neighbour_t)) != hipSuccess ||
             hipMalloc((void **)&c->sub_flag, cap) != hipSuccess ||
-            (!c->fail_list2 && hipMalloc((void **)&c->fail_list2, c->nq_pad * sizeof(int)) != hipSuccess)) {
+            (!c->fail_list2 && hipMalloc((void **)&c->fail_list2, c->nq_cap * sizeof(int)) != hipSuccess)) {
             research8_free(c);   /* no half-built sub-context survives */
             return KNN_ERR_NOMEM;
         }
@@ -1920,193 +1980,6 @@ int knn_search_packed(knn_ctx_t *c, const void *d_block, size_t m, knn_neighbour
         RCHK(knn_ctx_rescan_end(c, d_out, stream));
     }
     return KNN_OK;
-}
-
-/* knn_query (include/knn.h): out-of-sample queries on one GPU.  The corpus is
- * packed into resident blocks of one capacity (KNN_QUERY_BLOCK=rows overrides
- * the choice), the queries into tiles of at most KNN_QUERY_TILE_MAX rows
- * (KNN_QUERY_TILE=rows overrides that, for tests) with
- * ids m.. (past every corpus id, so no row is ever "the query itself"), and
- * each tile runs the ring rank's sequence against foreign blocks
- * (blk:217-242): begin on the MAX-reduced meta of every block and tile, the
- * fold of every corpus block, end, the int8 re-search where it applies, then
- * the exact rescan over every block.  The records of every tile stay on the
- * device until the last tile is done: the timed span holds no copy to the
- * host. */
-#define KNN_QUERY_BYTES_MAX ((size_t)1 << 30)   /* element bytes of one block / tile */
-#define KNN_QUERY_TILE_MAX ((size_t)1 << 18)
-
-static int query_tile(knn_ctx_t *ctx, size_t nblk, void *const *cblk, void *const *cs8,
-                      const size_t *cnc, const size_t *cbase, const void *qblk, const void *qs8, size_t tcap,
-                      size_t rows, size_t q_base, const double *d_meta, const double *h_meta,
-                      knn_neighbour_t *d_out)
-{
-    /* the tile's rows within the context's capacity (as research8_run) */
-    ctx->nq = rows;
-    ctx->nq_pad = knn_round_up(rows, KNN_TQ);
-    size_t unresolved = 0;
-    if (qs8) {
-        RCHK(knn_ctx_begin_s8(ctx, qs8, tcap, q_base, d_meta, h_meta, NULL));
-        RCHK(knn_ctx_step_shadow_n(ctx, (int)nblk, (const void *const *)cs8, cnc, cbase, NULL));
-    } else {
-        RCHK(knn_ctx_begin_meta(ctx, qblk, tcap, q_base, d_meta, h_meta, NULL));
-        RCHK(knn_ctx_step_n(ctx, (int)nblk, (const void *const *)cblk, cnc, cbase, NULL));
-    }
-    RCHK(knn_ctx_end(ctx, d_out, &unresolved, NULL));
-    if (unresolved && qs8) {
-        /* the re-search takes every block at once: together they are the corpus */
-        RCHK(knn_ctx_attach_qblock(ctx, qblk, tcap));
-        RCHK(knn_ctx_research_blocks(ctx, (int)nblk, (const void *const *)cs8, cnc, cbase, d_out, &unresolved, NULL));
-    }
-    if (unresolved) {
-        for (size_t b = 0; b < nblk; b++) RCHK(knn_ctx_rescan_step(ctx, cblk[b], cnc[b], cbase[b], NULL));
-        RCHK(knn_ctx_rescan_end(ctx, d_out, NULL));
-    }
-    return KNN_OK;
-}
-
-int knn_query(const double *X, size_t m, const double *Q, size_t mq, size_t n, int layout, const double *labels,
-              int k, int dtype, int flags, knn_neighbour_t *out)
-{
-    if (!X || !Q || !out || m == 0 || mq == 0 || n == 0 || k <= 0) return KNN_ERR_INVALID;
-    if (!dtype_ok(dtype)) return KNN_ERR_UNSUPPORTED;
-    if (k > (dtype == KNN_F32 ? KNN_MAX_K_F32 : KNN_MAX_K)) return KNN_ERR_UNSUPPORTED;
-    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
-    if (flags & ~KNN_QUERY_KEEP_ZERO) return KNN_ERR_INVALID;
-    if (m > 0x7fffffffULL || mq > 0x7fffffffULL || m + mq > 0x7fffffffULL || n > 0x7fffffffULL)
-        return KNN_ERR_INVALID;
-
-    /* block and tile capacities: at most KNN_QUERY_BYTES_MAX of elements each */
-    const size_t row_bytes = knn_n_pad_dt(n, dtype) * knn_esize(dtype);
-    size_t fit = KNN_QUERY_BYTES_MAX / row_bytes;
-    if (fit < 1024) fit = 1024;
-    size_t cap = m < fit ? m : fit;
-    {
-        const char *e = getenv("KNN_QUERY_BLOCK");
-        if (e && atol(e) > 0) cap = (size_t)atol(e) < m ? (size_t)atol(e) : m;
-    }
-    size_t tcap = mq < fit ? mq : fit;
-    if (tcap > KNN_QUERY_TILE_MAX) tcap = KNN_QUERY_TILE_MAX;
-    {
-        const char *e = getenv("KNN_QUERY_TILE");
-        if (e && atol(e) > 0) tcap = (size_t)atol(e) < mq ? (size_t)atol(e) : mq;
-    }
-    const size_t nblk = (m + cap - 1) / cap, ntile = (mq + tcap - 1) / tcap;   /* (both <= INT32_MAX) */
-
-    knn_ctx_t *ctx = NULL;
-    int rc = knn_ctx_create_dt(&ctx, 0, tcap, n, cap, k, dtype);
-    if (rc) return rc;
-    knn_ctx_set_keep_zero(ctx, (flags & KNN_QUERY_KEEP_ZERO) != 0);
-
-    double *d_X = NULL, *d_Q = NULL, *d_meta = NULL;
-    knn_neighbour_t *d_out = NULL;
-    hipEvent_t e0 = NULL, e1 = NULL;
-    /* [corpus blocks][query tiles]: element blocks, byte blocks (int8 path) */
-    const size_t nall = nblk + ntile;
-    void **blk = (void **)calloc(2 * nall, sizeof(void *));
-    size_t *cnc = (size_t *)calloc(2 * nblk, sizeof(size_t));
-    double *hm = (double *)calloc(nall * KNN_META_DOUBLES, sizeof(double));
-    if (!blk || !cnc || !hm) {
-        rc = KNN_ERR_NOMEM;
-        goto done;
-    }
-    void **s8 = blk + nall;
-    size_t *cbase = cnc + nblk;
-    if (hipMalloc((void **)&d_X, m * n * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&d_Q, mq * n * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&d_meta, KNN_META_DOUBLES * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&d_out, mq * (size_t)k * sizeof(knn_neighbour_t)) != hipSuccess) {
-        rc = KNN_ERR_NOMEM;
-        goto done;
-    }
-    for (size_t b = 0; b < nall; b++)
-        if (hipMalloc(&blk[b], knn_block_bytes_dt(b < nblk ? cap : tcap, n, dtype)) != hipSuccess) {
-            rc = KNN_ERR_NOMEM;
-            goto done;
-        }
-    if (hipMemcpy(d_X, X, m * n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_Q, Q, mq * n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        rc = KNN_ERR_HIP;
-        goto done;
-    }
-    hipEventRecord(e0, NULL);
-    /* pack every block and tile, then MAX-reduce their meta on the host */
-    for (size_t b = 0; b < nall && !rc; b++) {
-        const int corpus = b < nblk;
-        const size_t bc = corpus ? cap : tcap, r0 = corpus ? b * cap : (b - nblk) * tcap;
-        const size_t tot = corpus ? m : mq, rows = tot - r0 < bc ? tot - r0 : bc;
-        const double *src = (corpus ? d_X : d_Q) + (layout == KNN_COLMAJOR ? r0 : r0 * n);
-        if (corpus) {
-            cnc[b] = rows;
-            cbase[b] = r0;
-        }
-        rc = knn_block_pack_dt(blk[b], dtype, bc, rows, n, src, KNN_F64, layout == KNN_COLMAJOR ? tot : n, layout,
-                               NULL);
-        if (!rc && hipMemcpyAsync(hm + b * KNN_META_DOUBLES,
-                                  (const char *)blk[b] + knn_block_meta_offset_dt(bc, n, dtype),
-                                  KNN_META_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, NULL) != hipSuccess)
-            rc = KNN_ERR_HIP;
-    }
-    if (!rc && hipStreamSynchronize(NULL) != hipSuccess) rc = KNN_ERR_HIP;
-    if (rc) goto done;
-    double red[KNN_META_DOUBLES];
-    for (int j = 0; j < KNN_META_DOUBLES; j++) {
-        red[j] = hm[j];
-        for (size_t b = 1; b < nall; b++)
-            if (hm[b * KNN_META_DOUBLES + j] > red[j]) red[j] = hm[b * KNN_META_DOUBLES + j];
-    }
-    if (hipMemcpy(d_meta, red, sizeof(red), hipMemcpyHostToDevice) != hipSuccess) {
-        rc = KNN_ERR_HIP;
-        goto done;
-    }
-    /* 8-bit data: the byte blocks straight from the source (knn_block_pack_s8);
-     * they stay resident for the re-search */
-    const int use_s8 = knn_s8_spec_ok(red, n, dtype);
-    for (size_t b = 0; b < nall && use_s8 && !rc; b++) {
-        const int corpus = b < nblk;
-        const size_t bc = corpus ? cap : tcap, r0 = corpus ? b * cap : (b - nblk) * tcap;
-        const size_t tot = corpus ? m : mq, rows = tot - r0 < bc ? tot - r0 : bc;
-        const double *src = (corpus ? d_X : d_Q) + (layout == KNN_COLMAJOR ? r0 : r0 * n);
-        if (hipMalloc(&s8[b], knn_s8_bytes(bc, n)) != hipSuccess) {
-            rc = KNN_ERR_NOMEM;
-            break;
-        }
-        rc = knn_block_pack_s8(s8[b], dtype, bc, rows, n, src, KNN_F64, layout == KNN_COLMAJOR ? tot : n, layout,
-                               NULL);
-    }
-    for (size_t t = 0; t < ntile && !rc; t++) {
-        const size_t r0 = t * tcap, rows = mq - r0 < tcap ? mq - r0 : tcap;
-        rc = query_tile(ctx, nblk, blk, use_s8 ? s8 : NULL, cnc, cbase, blk[nblk + t],
-                        use_s8 ? s8[nblk + t] : NULL, tcap, rows, m + r0, d_meta, red, d_out + r0 * (size_t)k);
-    }
-    if (!rc) {
-        float ms = 0.f;
-        hipEventRecord(e1, NULL);
-        if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
-            rc = KNN_ERR_HIP;
-        g_last_search_s = ms * 1e-3;
-    }
-    if (!rc && hipMemcpy(out, d_out, mq * (size_t)k * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = KNN_ERR_HIP;
-done:
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (blk)
-        for (size_t b = 0; b < 2 * nall; b++) hipFree(blk[b]);
-    hipFree(d_X);
-    hipFree(d_Q);
-    hipFree(d_meta);
-    hipFree(d_out);
-    free(blk);
-    free(cnc);
-    free(hm);
-    knn_ctx_destroy(ctx);
-    if (!rc && labels) {
-        for (size_t i = 0; i < mq * (size_t)k; i++)
-            out[i].label = out[i].idx > 0 ? (int32_t)labels[out[i].idx - 1] : 0;
-    }
-    return rc;
 }
 
 /* Multi-GPU one-call path lives in knn_ring.c. */

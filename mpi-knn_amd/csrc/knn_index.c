@@ -1,0 +1,528 @@
+/*
+ * knn_index.c -- out-of-sample queries (include/knn.h): the resident corpus
+ * index knn_index_* and the one-call knn_query() on top of it.
+ *
+ * One implementation of the sequence serves both.  build_pack / build_finish
+ * pack the corpus from a device source into resident blocks of one capacity
+ * (KNN_QUERY_BLOCK=rows overrides the choice): element blocks, their meta
+ * MAX-reduced on the host, and byte blocks when that meta passes
+ * knn_s8_spec_ok.  run_pack / run_finish pack a batch of queries into tiles of at most
+ * KNN_QUERY_TILE_MAX rows (KNN_QUERY_TILE=rows overrides that, for tests)
+ * with ids m.. (past every corpus id, so no row is ever "the query itself"),
+ * MAX-reduces their meta with the corpus's, and runs the ring rank's sequence
+ * against foreign blocks per tile (blk:217-242): begin, the fold of every
+ * corpus block, end, the int8 re-search where it applies, then the exact
+ * rescan over every block.  The records of every tile stay on the device
+ * until the last tile is done: a timed span holds no copy to the host.
+ */
+#include "knn_internal.h"
+
+#include <hip/hip_runtime_api.h>
+#include <stdlib.h>
+#include <string.h>
+
+#define RCHK(x)                  \
+    do {                         \
+        int rc_ = (x);           \
+        if (rc_) return rc_;     \
+    } while (0)
+
+#define KNN_QUERY_BYTES_MAX ((size_t)1 << 30)   /* element bytes of one block / tile */
+#define KNN_QUERY_TILE_MAX ((size_t)1 << 18)
+#define KNN_INDEX_TILE_MIN 128                  /* tile capacity grows from here, doubling */
+
+struct knn_index {
+    int dtype;
+    size_t m, n;
+    /* the corpus: nblk blocks of capacity cap; s8[] only when have_s8 */
+    size_t cap, nblk;
+    void **blk, **s8;
+    size_t *cnc, *cbase;
+    int have_s8;
+    double cmeta[KNN_META_DOUBLES];   /* host copy of the corpus's reduced meta */
+    double *chm;                      /* the blocks' meta as read back (8 doubles a block) */
+    double *labels;
+    /* kept between queries: the context (for k, tile_cap query rows), ntile
+     * tile buffers of capacity tile_cap (byte forms allocated on first use),
+     * the records of a host-out call, the reduced meta, the span's events */
+    knn_ctx_t *ctx;
+    int k;
+    size_t tile_cap, ntile;
+    void **tblk, **ts8;
+    double *thm;                      /* the tiles' meta as read back */
+    knn_neighbour_t *d_out;
+    size_t out_recs;
+    double *d_meta, *red;             /* the reduced meta of the batch: device, and its pinned host copy */
+    hipEvent_t e0, e1;
+    int last_bits;
+};
+
+static int dtype_ok(int dtype) { return dtype == KNN_F64 || dtype == KNN_F32; }
+
+static size_t fit_rows(size_t n, int dtype)
+{
+    /* block and tile capacities: at most KNN_QUERY_BYTES_MAX of elements each */
+    const size_t row_bytes = knn_n_pad_dt(n, dtype) * knn_esize(dtype);
+    const size_t fit = KNN_QUERY_BYTES_MAX / row_bytes;
+    return fit < 1024 ? 1024 : fit;
+}
+
+static size_t env_rows(const char *name, size_t dflt, size_t limit)
+{
+    const char *e = getenv(name);
+    if (e && atol(e) > 0) return (size_t)atol(e) < limit ? (size_t)atol(e) : limit;
+    return dflt;
+}
+
+static void free_query_state(knn_index_t *ix)
+{
+    for (size_t t = 0; t < ix->ntile; t++) {
+        hipFree(ix->tblk[t]);
+        hipFree(ix->ts8[t]);
+    }
+    free(ix->tblk);
+    free(ix->ts8);
+    free(ix->thm);
+    ix->tblk = ix->ts8 = NULL;
+    ix->thm = NULL;
+    ix->ntile = 0;
+    knn_ctx_destroy(ix->ctx);
+    ix->ctx = NULL;
+}
+
+static void index_free(knn_index_t *ix)
+{
+    if (!ix) return;
+    free_query_state(ix);
+    for (size_t b = 0; b < ix->nblk; b++) {
+        if (ix->blk) hipFree(ix->blk[b]);
+        if (ix->s8) hipFree(ix->s8[b]);
+    }
+    hipFree(ix->d_out);
+    hipFree(ix->d_meta);
+    if (ix->red) hipHostFree(ix->red);
+    if (ix->e0) hipEventDestroy(ix->e0);
+    if (ix->e1) hipEventDestroy(ix->e1);
+    free(ix->blk);
+    free(ix->s8);
+    free(ix->cnc);
+    free(ix->chm);
+    free(ix->labels);
+    free(ix);
+}
+
+/* the host side of an index over an m x n corpus on device 0 (the first
+ * device call of every entry point: KNN_ERR_NODEVICE without a gfx950) */
+static int index_alloc(knn_index_t **out, size_t m, size_t n, int dtype)
+{
+    RCHK(knn_device_probe(0, NULL));
+    if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
+    knn_index_t *ix = (knn_index_t *)calloc(1, sizeof(*ix));
+    if (!ix) return KNN_ERR_NOMEM;
+    ix->dtype = dtype;
+    ix->m = m;
+    ix->n = n;
+    const size_t fit = fit_rows(n, dtype);
+    ix->cap = env_rows("KNN_QUERY_BLOCK", m < fit ? m : fit, m);
+    ix->nblk = (m + ix->cap - 1) / ix->cap;   /* (<= INT32_MAX) */
+    ix->blk = (void **)calloc(ix->nblk, sizeof(void *));
+    ix->s8 = (void **)calloc(ix->nblk, sizeof(void *));
+    ix->cnc = (size_t *)calloc(2 * ix->nblk, sizeof(size_t));
+    ix->chm = (double *)calloc(ix->nblk * KNN_META_DOUBLES, sizeof(double));
+    if (!ix->blk || !ix->s8 || !ix->cnc || !ix->chm) {
+        index_free(ix);
+        return KNN_ERR_NOMEM;
+    }
+    ix->cbase = ix->cnc + ix->nblk;
+    if (hipMalloc((void **)&ix->d_meta, KNN_META_DOUBLES * sizeof(double)) != hipSuccess ||
+        hipHostMalloc((void **)&ix->red, KNN_META_DOUBLES * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+        index_free(ix);
+        return KNN_ERR_NOMEM;
+    }
+    if (hipEventCreate(&ix->e0) != hipSuccess || hipEventCreate(&ix->e1) != hipSuccess) {
+        index_free(ix);
+        return KNN_ERR_HIP;
+    }
+    *out = ix;
+    return KNN_OK;
+}
+
+/* Pack rows r0.. of a `tot`-row device source into nb buffers of capacity bc
+ * (buffer b: rows r0 = b * step ..), element blocks (s8 = 0; their meta
+ * words gathered behind each pack into hm, 8 doubles a buffer) or byte
+ * blocks (s8 = 1).  All on the NULL stream, no wait. */
+static int pack_rows(void *const *buf, size_t nb, size_t bc, size_t step, const void *d_src, size_t tot, size_t n,
+                     int layout, int src_dtype, int dtype, int s8, double *hm)
+{
+    const size_t es = knn_src_esize(src_dtype);
+    for (size_t b = 0; b < nb; b++) {
+        const size_t r0 = b * step, rows = tot - r0 < step ? tot - r0 : step;
+        const char *src = (const char *)d_src + (layout == KNN_COLMAJOR ? r0 : r0 * n) * es;
+        const size_t ld = layout == KNN_COLMAJOR ? tot : n;
+        if (s8) {
+            RCHK(knn_block_pack_s8(buf[b], dtype, bc, rows, n, src, src_dtype, ld, layout, NULL));
+            continue;
+        }
+        RCHK(knn_block_pack_dt(buf[b], dtype, bc, rows, n, src, src_dtype, ld, layout, NULL));
+        if (hipMemcpyAsync(hm + b * KNN_META_DOUBLES, (const char *)buf[b] + knn_block_meta_offset_dt(bc, n, dtype),
+                           KNN_META_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, NULL) != hipSuccess)
+            return KNN_ERR_HIP;
+    }
+    return KNN_OK;
+}
+
+/* red = max(red, every buffer's meta) word by word */
+static void meta_max(double *red, const double *hm, size_t nb)
+{
+    for (size_t b = 0; b < nb; b++)
+        for (int j = 0; j < KNN_META_DOUBLES; j++)
+            if (hm[b * KNN_META_DOUBLES + j] > red[j]) red[j] = hm[b * KNN_META_DOUBLES + j];
+}
+
+/* the element blocks' memory (knn_query: ahead of its span) */
+static int index_alloc_blocks(knn_index_t *ix)
+{
+    for (size_t b = 0; b < ix->nblk; b++) {
+        ix->cbase[b] = b * ix->cap;
+        ix->cnc[b] = ix->m - ix->cbase[b] < ix->cap ? ix->m - ix->cbase[b] : ix->cap;
+        if (!ix->blk[b] && hipMalloc(&ix->blk[b], knn_block_bytes_dt(ix->cap, ix->n, ix->dtype)) != hipSuccess)
+            return KNN_ERR_NOMEM;
+    }
+    return KNN_OK;
+}
+
+/* The resident corpus blocks from the device source d_X, in two parts around
+ * one wait for the NULL stream (knn_query shares that wait with its queries'
+ * part): the element packs and their meta on their way to the host ... */
+static int build_pack(knn_index_t *ix, const void *d_X, int layout, int src_dtype)
+{
+    RCHK(index_alloc_blocks(ix));
+    return pack_rows(ix->blk, ix->nblk, ix->cap, ix->cap, d_X, ix->m, ix->n, layout, src_dtype, ix->dtype, 0, ix->chm);
+}
+
+/* ... and, the meta arrived: its reduction, and for 8-bit data the byte blocks
+ * straight from the source (knn_block_pack_s8), resident for every search and
+ * re-search */
+static int build_finish(knn_index_t *ix, const void *d_X, int layout, int src_dtype, const double *batch_hm,
+                        size_t batch_n)
+{
+    memset(ix->cmeta, 0, sizeof(ix->cmeta));   /* (every meta word is >= 0) */
+    meta_max(ix->cmeta, ix->chm, ix->nblk);
+    /* knn_query knows its only batch already (batch_hm: its tiles' meta): no
+     * byte blocks for a corpus whose queries will not take the byte path */
+    double joint[KNN_META_DOUBLES];
+    memcpy(joint, ix->cmeta, sizeof(joint));
+    if (batch_hm) meta_max(joint, batch_hm, batch_n);
+    ix->have_s8 = knn_s8_spec_ok(joint, ix->n, ix->dtype);
+    if (!ix->have_s8) return KNN_OK;
+    for (size_t b = 0; b < ix->nblk; b++)
+        if (hipMalloc(&ix->s8[b], knn_s8_bytes(ix->cap, ix->n)) != hipSuccess) return KNN_ERR_NOMEM;
+    return pack_rows(ix->s8, ix->nblk, ix->cap, ix->cap, d_X, ix->m, ix->n, layout, src_dtype, ix->dtype, 1, NULL);
+}
+
+/* a batch of mq queries: tiles of *tcap rows, *ntile of them */
+static void tile_shape(const knn_index_t *ix, size_t mq, size_t *tcap, size_t *ntile)
+{
+    const size_t fit = fit_rows(ix->n, ix->dtype);
+    size_t t = mq < fit ? mq : fit;
+    if (t > KNN_QUERY_TILE_MAX) t = KNN_QUERY_TILE_MAX;
+    *tcap = env_rows("KNN_QUERY_TILE", t, mq);
+    *ntile = (mq + *tcap - 1) / *tcap;
+}
+
+/* The context and the tile buffers for a batch of mq queries at k.  grow: the
+ * tile capacity doubles from KNN_INDEX_TILE_MIN rows, so that a stream of
+ * varying batch sizes does not reallocate every call (knn_query, one batch:
+ * the capacity it needs). */
+static int index_reserve(knn_index_t *ix, size_t mq, int k, int grow)
+{
+    size_t tcap, ntile;
+    tile_shape(ix, mq, &tcap, &ntile);
+    if (ix->ctx && (k != ix->k || tcap > ix->tile_cap)) free_query_state(ix);
+    if (!ix->ctx) {
+        size_t cap = grow ? (ix->tile_cap ? ix->tile_cap : KNN_INDEX_TILE_MIN) : tcap;
+        while (cap < tcap) cap *= 2;
+        RCHK(knn_ctx_create_dt(&ix->ctx, 0, cap, ix->n, ix->cap, k, ix->dtype));
+        ix->tile_cap = cap;
+        ix->k = k;
+    }
+    if (ntile > ix->ntile) {
+        void **a = (void **)calloc(ntile, sizeof(void *)), **b = (void **)calloc(ntile, sizeof(void *));
+        double *hm = (double *)calloc(ntile * KNN_META_DOUBLES, sizeof(double));
+        if (!a || !b || !hm) {
+            free(a);
+            free(b);
+            free(hm);
+            return KNN_ERR_NOMEM;
+        }
+        free(ix->thm);
+        ix->thm = hm;
+        if (ix->ntile) {
+            memcpy(a, ix->tblk, ix->ntile * sizeof(void *));
+            memcpy(b, ix->ts8, ix->ntile * sizeof(void *));
+        }
+        free(ix->tblk);
+        free(ix->ts8);
+        ix->tblk = a;
+        ix->ts8 = b;
+        ix->ntile = ntile;
+    }
+    for (size_t t = 0; t < ntile; t++)
+        if (!ix->tblk[t] && hipMalloc(&ix->tblk[t], knn_block_bytes_dt(ix->tile_cap, ix->n, ix->dtype)) != hipSuccess)
+            return KNN_ERR_NOMEM;
+    return KNN_OK;
+}
+
+static int query_tile(knn_ctx_t *ctx, size_t nblk, void *const *cblk, void *const *cs8,
+                      const size_t *cnc, const size_t *cbase, const void *qblk, const void *qs8, size_t tcap,
+                      size_t rows, size_t q_base, const double *d_meta, const double *h_meta,
+                      knn_neighbour_t *d_out)
+{
+    /* the tile's rows within the context's capacity */
+    RCHK(knn_ctx_set_rows(ctx, rows));
+    size_t unresolved = 0;
+    if (qs8) {
+        RCHK(knn_ctx_begin_s8(ctx, qs8, tcap, q_base, d_meta, h_meta, NULL));
+        RCHK(knn_ctx_step_shadow_n(ctx, (int)nblk, (const void *const *)cs8, cnc, cbase, NULL));
+    } else {
+        RCHK(knn_ctx_begin_meta(ctx, qblk, tcap, q_base, d_meta, h_meta, NULL));
+        RCHK(knn_ctx_step_n(ctx, (int)nblk, (const void *const *)cblk, cnc, cbase, NULL));
+    }
+    RCHK(knn_ctx_end(ctx, d_out, &unresolved, NULL));
+    if (unresolved && qs8) {
+        /* the re-search takes every block at once: together they are the corpus */
+        RCHK(knn_ctx_attach_qblock(ctx, qblk, tcap));
+        RCHK(knn_ctx_research_blocks(ctx, (int)nblk, (const void *const *)cs8, cnc, cbase, d_out, &unresolved, NULL));
+    }
+    if (unresolved) {
+        for (size_t b = 0; b < nblk; b++) RCHK(knn_ctx_rescan_step(ctx, cblk[b], cnc[b], cbase[b], NULL));
+        RCHK(knn_ctx_rescan_end(ctx, d_out, NULL));
+    }
+    return KNN_OK;
+}
+
+/* One batch against the resident blocks, mq queries from the device source
+ * d_Q, in two parts around one wait for the NULL stream: the tiles' element
+ * packs and their meta on their way to the host (the context and the tile
+ * buffers reserved by the caller) ... */
+static int run_pack(knn_index_t *ix, const void *d_Q, size_t mq, int layout, int src_dtype)
+{
+    size_t tcap, ntile;
+    tile_shape(ix, mq, &tcap, &ntile);
+    return pack_rows(ix->tblk, ntile, ix->tile_cap, tcap, d_Q, mq, ix->n, layout, src_dtype, ix->dtype, 0, ix->thm);
+}
+
+/* ... and, the meta arrived: its MAX-reduction with the corpus's, the path
+ * that allows, and the tiles' searches -- their records into d_out (device),
+ * complete on return (knn_ctx_end waits for each tile's). */
+static int run_finish(knn_index_t *ix, const void *d_Q, size_t mq, int layout, int src_dtype, int flags,
+                      knn_neighbour_t *d_out)
+{
+    const size_t n = ix->n;
+    size_t tcap, ntile;
+    tile_shape(ix, mq, &tcap, &ntile);
+    knn_ctx_set_keep_zero(ix->ctx, (flags & KNN_QUERY_KEEP_ZERO) != 0);
+    /* (pinned, and its last reader done with the call before this one: the
+     * copy is enqueued without a wait for the packs in front of it) */
+    double *red = ix->red;
+    memcpy(red, ix->cmeta, KNN_META_DOUBLES * sizeof(double));
+    meta_max(red, ix->thm, ntile);
+    if (hipMemcpyAsync(ix->d_meta, red, KNN_META_DOUBLES * sizeof(double), hipMemcpyHostToDevice, NULL) != hipSuccess)
+        return KNN_ERR_HIP;
+    /* the byte path: the corpus has its byte blocks and the batch is 8-bit too */
+    const int use_s8 = ix->have_s8 && knn_s8_spec_ok(red, n, ix->dtype);
+    if (use_s8) {
+        for (size_t t = 0; t < ntile; t++)
+            if (!ix->ts8[t] && hipMalloc(&ix->ts8[t], knn_s8_bytes(ix->tile_cap, n)) != hipSuccess)
+                return KNN_ERR_NOMEM;
+        RCHK(pack_rows(ix->ts8, ntile, ix->tile_cap, tcap, d_Q, mq, n, layout, src_dtype, ix->dtype, 1, NULL));
+    }
+    for (size_t t = 0; t < ntile; t++) {
+        const size_t r0 = t * tcap, rows = mq - r0 < tcap ? mq - r0 : tcap;
+        RCHK(query_tile(ix->ctx, ix->nblk, ix->blk, use_s8 ? ix->s8 : NULL, ix->cnc, ix->cbase, ix->tblk[t],
+                        use_s8 ? ix->ts8[t] : NULL, ix->tile_cap, rows, ix->m + r0, ix->d_meta, red,
+                        d_out + r0 * (size_t)ix->k));
+    }
+    ix->last_bits = knn_ctx_contraction_bits(ix->ctx);
+    return KNN_OK;
+}
+
+static int stream_wait(void) { return hipStreamSynchronize(NULL) == hipSuccess ? KNN_OK : KNN_ERR_HIP; }
+
+/* the index's own record buffer, for cnt records */
+static int index_out(knn_index_t *ix, size_t cnt)
+{
+    if (cnt <= ix->out_recs) return KNN_OK;
+    hipFree(ix->d_out);
+    ix->d_out = NULL;
+    ix->out_recs = 0;
+    if (hipMalloc((void **)&ix->d_out, cnt * sizeof(knn_neighbour_t)) != hipSuccess) return KNN_ERR_NOMEM;
+    ix->out_recs = cnt;
+    return KNN_OK;
+}
+
+/* a host array on the device (*d: to hipFree) */
+static int upload(void **d, const void *h, size_t bytes)
+{
+    if (hipMalloc(d, bytes) != hipSuccess) return KNN_ERR_NOMEM;
+    return hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+}
+
+/* the span e0 .. e1 (e1 recorded here) into knn_last_search_seconds() */
+static int span_end(knn_index_t *ix)
+{
+    float ms = 0.f;
+    hipEventRecord(ix->e1, NULL);
+    if (hipEventSynchronize(ix->e1) != hipSuccess || hipEventElapsedTime(&ms, ix->e0, ix->e1) != hipSuccess)
+        return KNN_ERR_HIP;
+    knn_set_last_search_seconds(ms * 1e-3);
+    return KNN_OK;
+}
+
+static void fill_labels(knn_neighbour_t *out, size_t cnt, const double *labels)
+{
+    for (size_t i = 0; i < cnt; i++) out[i].label = out[i].idx > 0 ? (int32_t)labels[out[i].idx - 1] : 0;
+}
+
+int knn_index_create(knn_index_t **index, const void *X, size_t m, size_t n, int layout, int src_dtype,
+                     const double *labels, int dtype, int flags)
+{
+    if (!index || !X || m == 0 || n == 0) return KNN_ERR_INVALID;
+    if (!knn_src_esize(src_dtype) || !dtype_ok(dtype)) return KNN_ERR_UNSUPPORTED;
+    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (flags & ~KNN_INDEX_DEVICE_SRC) return KNN_ERR_INVALID;
+    if (m > 0x7fffffffULL || n > 0x7fffffffULL) return KNN_ERR_INVALID;
+    knn_index_t *ix = NULL;
+    RCHK(index_alloc(&ix, m, n, dtype));
+    int rc = KNN_OK;
+    void *d_X = NULL;
+    if (labels) {
+        ix->labels = (double *)malloc(m * sizeof(double));
+        if (ix->labels) memcpy(ix->labels, labels, m * sizeof(double));
+        else rc = KNN_ERR_NOMEM;
+    }
+    if (!rc && !(flags & KNN_INDEX_DEVICE_SRC)) rc = upload(&d_X, X, m * n * knn_src_esize(src_dtype));
+    const void *src = (flags & KNN_INDEX_DEVICE_SRC) ? X : d_X;
+    if (!rc) rc = build_pack(ix, src, layout, src_dtype);
+    if (!rc) rc = stream_wait();
+    if (!rc) rc = build_finish(ix, src, layout, src_dtype, NULL, 0);
+    /* the packs have read the source before the index is handed out */
+    if (!rc) rc = stream_wait();
+    else hipStreamSynchronize(NULL);
+    hipFree(d_X);
+    if (rc) {
+        index_free(ix);
+        return rc;
+    }
+    *index = ix;
+    return KNN_OK;
+}
+
+int knn_index_query(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int flags,
+                    knn_neighbour_t *out)
+{
+    if (!ix || !Q || !out || mq == 0 || k <= 0) return KNN_ERR_INVALID;
+    if (!knn_src_esize(src_dtype)) return KNN_ERR_UNSUPPORTED;
+    if (k > (ix->dtype == KNN_F32 ? KNN_MAX_K_F32 : KNN_MAX_K)) return KNN_ERR_UNSUPPORTED;
+    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (flags & ~(KNN_QUERY_KEEP_ZERO | KNN_INDEX_DEVICE_SRC | KNN_INDEX_DEVICE_OUT)) return KNN_ERR_INVALID;
+    if (mq > 0x7fffffffULL || ix->m + mq > 0x7fffffffULL) return KNN_ERR_INVALID;
+    if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
+    const size_t cnt = mq * (size_t)k;
+    const int dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
+    void *d_Q = NULL;
+    int rc = dev_out ? KNN_OK : index_out(ix, cnt);
+    if (!rc && !(flags & KNN_INDEX_DEVICE_SRC)) rc = upload(&d_Q, Q, mq * ix->n * knn_src_esize(src_dtype));
+    if (!rc) rc = index_reserve(ix, mq, k, 1);
+    if (!rc) {
+        knn_neighbour_t *d_out = dev_out ? out : ix->d_out;
+        const void *src = (flags & KNN_INDEX_DEVICE_SRC) ? Q : d_Q;
+        hipEventRecord(ix->e0, NULL);
+        rc = run_pack(ix, src, mq, layout, src_dtype);
+        if (!rc) rc = stream_wait();
+        if (!rc) rc = run_finish(ix, src, mq, layout, src_dtype, flags, d_out);
+        if (!rc) rc = span_end(ix);
+        if (!rc && !dev_out && hipMemcpy(out, d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = KNN_ERR_HIP;
+    }
+    if (rc) {   /* nothing of a failed call is kept */
+        hipStreamSynchronize(NULL);
+        free_query_state(ix);
+    }
+    hipFree(d_Q);
+    if (!rc && !dev_out && ix->labels) fill_labels(out, cnt, ix->labels);
+    return rc;
+}
+
+int knn_index_info(const knn_index_t *ix, size_t *m, size_t *n, int *nblocks, size_t *device_bytes, int *last_bits)
+{
+    if (!ix) return KNN_ERR_INVALID;
+    if (m) *m = ix->m;
+    if (n) *n = ix->n;
+    if (nblocks) *nblocks = (int)ix->nblk;
+    if (last_bits) *last_bits = ix->last_bits;
+    if (device_bytes) {
+        size_t b = ix->nblk * knn_block_bytes_dt(ix->cap, ix->n, ix->dtype) + KNN_META_DOUBLES * sizeof(double);
+        if (ix->have_s8) b += ix->nblk * knn_s8_bytes(ix->cap, ix->n);
+        for (size_t t = 0; t < ix->ntile; t++) {
+            if (ix->tblk[t]) b += knn_block_bytes_dt(ix->tile_cap, ix->n, ix->dtype);
+            if (ix->ts8[t]) b += knn_s8_bytes(ix->tile_cap, ix->n);
+        }
+        b += ix->out_recs * sizeof(knn_neighbour_t);
+        *device_bytes = b + knn_ctx_device_bytes(ix->ctx);
+    }
+    return KNN_OK;
+}
+
+int knn_index_destroy(knn_index_t *ix)
+{
+    if (!ix) return KNN_ERR_INVALID;
+    hipSetDevice(0);
+    index_free(ix);
+    return KNN_OK;
+}
+
+/* knn_query: an index that lives for one call.  Both uploads come first, so
+ * the span -- corpus pack through the last tile's records -- holds no copy
+ * from or to the host. */
+int knn_query(const double *X, size_t m, const double *Q, size_t mq, size_t n, int layout, const double *labels,
+              int k, int dtype, int flags, knn_neighbour_t *out)
+{
+    if (!X || !Q || !out || m == 0 || mq == 0 || n == 0 || k <= 0) return KNN_ERR_INVALID;
+    if (!dtype_ok(dtype)) return KNN_ERR_UNSUPPORTED;
+    if (k > (dtype == KNN_F32 ? KNN_MAX_K_F32 : KNN_MAX_K)) return KNN_ERR_UNSUPPORTED;
+    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (flags & ~KNN_QUERY_KEEP_ZERO) return KNN_ERR_INVALID;
+    if (m > 0x7fffffffULL || mq > 0x7fffffffULL || m + mq > 0x7fffffffULL || n > 0x7fffffffULL)
+        return KNN_ERR_INVALID;
+    knn_index_t *ix = NULL;
+    RCHK(index_alloc(&ix, m, n, dtype));
+    const size_t cnt = mq * (size_t)k;
+    void *d_X = NULL, *d_Q = NULL;
+    /* every allocation, then the uploads: the span starts behind a copy, with
+     * no fresh memory still to be mapped in front of its first kernel */
+    int rc = index_reserve(ix, mq, k, 0);
+    if (!rc) rc = index_out(ix, cnt);
+    if (!rc) rc = index_alloc_blocks(ix);
+    if (!rc) rc = upload(&d_X, X, m * n * sizeof(double));
+    if (!rc) rc = upload(&d_Q, Q, mq * n * sizeof(double));
+    if (!rc) {
+        /* every block and tile packed, one wait for their meta, then the byte
+         * forms and the searches */
+        hipEventRecord(ix->e0, NULL);
+        rc = build_pack(ix, d_X, layout, KNN_F64);
+        if (!rc) rc = run_pack(ix, d_Q, mq, layout, KNN_F64);
+        if (!rc) rc = stream_wait();
+        if (!rc) rc = build_finish(ix, d_X, layout, KNN_F64, ix->thm, ix->ntile);
+        if (!rc) rc = run_finish(ix, d_Q, mq, layout, KNN_F64, flags, ix->d_out);
+        if (!rc) rc = span_end(ix);
+    }
+    if (!rc && hipMemcpy(out, ix->d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = KNN_ERR_HIP;
+    if (rc) hipStreamSynchronize(NULL);
+    hipFree(d_X);
+    hipFree(d_Q);
+    index_free(ix);
+    if (!rc && labels) fill_labels(out, cnt, labels);
+    return rc;
+}

@@ -259,6 +259,17 @@ int knn_launch_vote(knn_neighbour_t *nb, size_t m, int k, int nclasses, int rule
 int knn_launch_wire(int unpack, void *dst, const void *src, int dtype, size_t cnt, void *stream);
 /* knn_engine.c: the value knn_last_search_seconds() returns (this thread) */
 void knn_set_last_search_seconds(double s);
+/* knn_engine.c, for knn_index.c: KNN_OK when `device` is a gfx950 (*cus,
+ * nullable: its compute units), else KNN_ERR_NODEVICE; the context's next
+ * searches over `rows` queries within its capacity; the device bytes it holds */
+int knn_device_probe(int device, int *cus);
+int knn_ctx_set_rows(knn_ctx_t *ctx, size_t rows);
+size_t knn_ctx_device_bytes(const knn_ctx_t *ctx);
+/* bytes of one element of a pack source (KNN_F64 / KNN_F32 / KNN_U8), 0 = unknown */
+static inline size_t knn_src_esize(int src_dtype)
+{
+    return src_dtype == KNN_F64 ? 8 : src_dtype == KNN_F32 ? 4 : src_dtype == KNN_U8 ? 1 : 0;
+}
 
 #ifdef __cplusplus
 }

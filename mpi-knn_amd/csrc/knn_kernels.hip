@@ -173,7 +173,7 @@ __device__ __forceinline__ double knn_cert_E(int n, double qn, double maxnorm, i
 }
 
 // ---------------------------------------------------------------------------
-// Packing (blk:100-109): src (S = fp64 or fp32; col-major, ld >= rows |
+// Packing (blk:100-109): src (S = fp64, fp32 or unsigned char; col-major, ld >= rows |
 // row-major, ld >= n) -> padded row-major block of T, the squared norms
 // (fp64 accumulate, stored as T) and the meta (max|x|, max norm,
 // non-integer, non-finite, max(x)+, max(-x)+), in ONE pass over the source
@@ -435,6 +435,95 @@ __global__ __launch_bounds__(256) void k_pack8_row(signed char *__restrict__ dst
         else ma.nonfin = 1.0;
     }
     knn_meta_flush(ma, mnorm, meta);
+    if (blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
+}
+
+// row-major KNN_U8 source: the byte image is x ^ 0x80 (x - 128 as int8), so a
+// lane moves one 16-byte group of a row, read as one vector and written as
+// one (2 bytes of traffic an element).  LPR lanes (a power of two >= rs / 16,
+// at most 64) share a row and a wave carries 64 / LPR rows at once: SIFT's
+// 128-byte rows 8 to a wave, MNIST's 800-byte rows one (four such row groups
+// in flight).  Everything is
+// integer arithmetic: sum (x - 128)^2 for the norm words, sum x^2 (< 2^26 at
+// n <= 896) and max x for the meta -- the words the fp64 source gives for the
+// same values, whatever the order of summation (exact integers below 2^53).
+// VEC: the source and ld are multiples of 16 bytes, so every whole group
+// inside n is read as a 16-byte vector; otherwise, in a row's tail group and
+// past n (ld > n), byte by byte.
+typedef unsigned knn_v4u __attribute__((ext_vector_type(4)));
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_pack8_row_u8(signed char *__restrict__ dst, size_t rows, size_t rows_pad,
+                                                      int n, int rs, const unsigned char *__restrict__ src,
+                                                      size_t ld, int lpr)
+{
+    int *norms = (int *)(dst + rows_pad * (size_t)rs);
+    double *meta = (double *)(norms + 2 * rows_pad);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int rpw = 64 / lpr;               // rows a wave
+    const int sub = lane / lpr, g = lane % lpr;
+    const bool has = 16 * g < rs;           // this lane's group lies inside the row
+    unsigned mx = 0u, mnorm = 0u;
+    // U row groups a wave in flight: their vector loads issue before the first
+    // conversion (one load a lane a row left the wave waiting on each row in
+    // turn).  rows_pad is a multiple of 128 and rpw divides 64, so a row group
+    // lies below rows_pad as a whole or not at all (wave-uniform).
+    constexpr int U = 4;
+    for (size_t rb = ((size_t)blockIdx.x * 4 + wave) * U * rpw; rb < rows_pad;
+         rb += (size_t)gridDim.x * 4 * U * rpw) {
+        knn_v4u v[U];
+        bool full[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const size_t r = rb + (size_t)u * rpw + sub;
+            full[u] = VEC && has && r < rows && 16 * g + 16 <= n;
+            v[u] = (knn_v4u){0u, 0u, 0u, 0u};
+            if (full[u]) v[u] = *(const knn_v4u *)(src + r * ld + 16 * g);
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (rb + (size_t)u * rpw >= rows_pad) break;
+            const size_t r = rb + (size_t)u * rpw + sub;
+            // bytes, and 0xff where a byte is data
+            unsigned w[4] = {v[u][0], v[u][1], v[u][2], v[u][3]};
+            const unsigned fm = full[u] ? 0xffffffffu : 0u;
+            unsigned live[4] = {fm, fm, fm, fm};
+            if (!full[u] && has && r < rows) {
+                const unsigned char *x = src + r * ld + 16 * g;
+#pragma unroll
+                for (int e = 0; e < 16; e++)
+                    if (16 * g + e < n) {
+                        w[e >> 2] |= (unsigned)x[e] << (8 * (e & 3));
+                        live[e >> 2] |= 0xffu << (8 * (e & 3));
+                    }
+            }
+            unsigned sx = 0u, si = 0u;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const unsigned b = (w[q] >> (8 * e)) & 0xffu;
+                    const int xi = ((live[q] >> (8 * e)) & 1u) ? (int)b - 128 : 0;
+                    sx += b * b;
+                    si += (unsigned)(xi * xi);
+                    mx = b > mx ? b : mx;
+                }
+                w[q] = (w[q] ^ 0x80808080u) & live[q];
+            }
+            if (has) *(knn_v4u *)(dst + r * (size_t)rs + 16 * g) = (knn_v4u){w[0], w[1], w[2], w[3]};
+            for (int off = lpr >> 1; off > 0; off >>= 1) {
+                sx += (unsigned)__shfl_xor((int)sx, off);
+                si += (unsigned)__shfl_xor((int)si, off);
+            }
+            if (g == 0) {
+                norms[i8_norm_pos((int)r)] = i8_norm_word((int)r, (int)si, rs);
+                norms[rows_pad + i8_norm_pos((int)r)] = i8_init_word((int)si, rs);
+            }
+            mnorm = sx > mnorm ? sx : mnorm;
+        }
+    }
+    knn_meta_acc ma;
+    ma.mabs = ma.mpos = (double)mx;
+    knn_meta_flush(ma, (double)mnorm, meta);
     if (blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
 }
 
@@ -2307,6 +2396,22 @@ static int launch_pack8(signed char *dst, size_t cap, size_t rows, size_t n, con
         // (32-row workgroups, twice as many: 107.5 against 105.7 us for MNIST)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_col<T, S, 64>), dim3((unsigned)((rp + 63) / 64)), dim3(256), 0,
                            s, dst, rows, rp, (int)n, (int)rs, src, ld);
+    } else if constexpr (sizeof(S) == 1) {
+        // KNN_U8: lpr lanes a row (a power of two >= rs / 16), 64 / lpr rows a wave
+        int lpr = 1;
+        while (lpr < 64 && 16 * (size_t)lpr < rs) lpr *= 2;
+        if (16 * (size_t)lpr < rs) return KNN_ERR_INVALID;   // (rs <= 1024: n <= KNN_I8_MAX_N)
+        // waves for one pass at 4 row groups a wave; 2048 workgroups (8 a CU) at most:
+        // every workgroup ends in six atomics on the same meta words
+        const size_t nw = (rp * lpr + 255) / 256;
+        const unsigned nb = (unsigned)((nw + 3) / 4 < 2048 ? (nw + 3) / 4 : 2048);
+        const bool vec = ((uintptr_t)src % 16 == 0) && ld % 16 == 0;
+        if (vec)
+            hipLaunchKernelGGL(k_pack8_row_u8<true>, dim3(nb), dim3(256), 0, s, dst, rows, rp, (int)n, (int)rs, src,
+                               ld, lpr);
+        else
+            hipLaunchKernelGGL(k_pack8_row_u8<false>, dim3(nb), dim3(256), 0, s, dst, rows, rp, (int)n, (int)rs, src,
+                               ld, lpr);
     } else {
         const unsigned nb = (unsigned)((rp + 3) / 4 < 8192 ? (rp + 3) / 4 : 8192);
         const bool vec = ((uintptr_t)src % 16 == 0) && (ld * sizeof(S)) % 16 == 0;
@@ -2329,6 +2434,9 @@ extern "C" int knn_launch_pack_s8(void *dst, int dtype, size_t cap, size_t rows,
     if (dtype == KNN_F64 && src_dtype == KNN_F32) return launch_pack8<double>(d, cap, rows, n, (const float *)src, ld, layout, s);
     if (dtype == KNN_F32 && src_dtype == KNN_F64) return launch_pack8<float>(d, cap, rows, n, (const double *)src, ld, layout, s);
     if (dtype == KNN_F32 && src_dtype == KNN_F32) return launch_pack8<float>(d, cap, rows, n, (const float *)src, ld, layout, s);
+    // (the bytes do not depend on the block's element type: every value is exact in both)
+    if (dtype == KNN_F64 && src_dtype == KNN_U8) return launch_pack8<double>(d, cap, rows, n, (const unsigned char *)src, ld, layout, s);
+    if (dtype == KNN_F32 && src_dtype == KNN_U8) return launch_pack8<float>(d, cap, rows, n, (const unsigned char *)src, ld, layout, s);
     return KNN_ERR_INVALID;
 }
 
@@ -2523,6 +2631,10 @@ extern "C" int knn_launch_pack(void *blk, int dtype, size_t cap, size_t rows, si
         return launch_pack((float *)blk, cap, rows, n, (const double *)src, ld, layout, s);
     if (dtype == KNN_F32 && src_dtype == KNN_F32)
         return launch_pack((float *)blk, cap, rows, n, (const float *)src, ld, layout, s);
+    if (dtype == KNN_F64 && src_dtype == KNN_U8)
+        return launch_pack((double *)blk, cap, rows, n, (const unsigned char *)src, ld, layout, s);
+    if (dtype == KNN_F32 && src_dtype == KNN_U8)
+        return launch_pack((float *)blk, cap, rows, n, (const unsigned char *)src, ld, layout, s);
     return KNN_ERR_INVALID;
 }
 

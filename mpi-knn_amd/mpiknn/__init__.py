@@ -11,6 +11,7 @@ Reference (yiapou13/mpi-knn): serial:L = knn-serial.c,
 blk:L = mpi-knn-parallel_blocking.c, nb:L = mpi-knn-parallel_non_blocking.c.
 """
 import atexit
+import collections
 import ctypes
 import os
 import sys
@@ -27,7 +28,7 @@ NB_DTYPE = np.dtype([("distance", "<f8"), ("idx", "<i4"), ("label", "<i4")])
 
 OK, ERR_INVALID, ERR_NOMEM, ERR_HIP, ERR_IO, ERR_FORMAT, ERR_UNSUPPORTED, ERR_NODEVICE, ERR_RCCL = range(9)
 COLMAJOR, ROWMAJOR = 0, 1
-F64, F32 = 0, 1
+F64, F32, U8 = 0, 1, 2
 VOTE_SERIAL, VOTE_MPI, VOTE_MAJORITY = 0, 1, 2
 MAX_K = 32          # KNN_MAX_K (fp64)
 MAX_K_F32 = 128     # KNN_MAX_K_F32
@@ -50,8 +51,12 @@ API_SYMBOLS = (
     "knn_s8_block_meta_offset", "knn_block_pack_s8", "knn_s8_spec_ok", "knn_ctx_begin_s8",
     "knn_ctx_attach_qblock", "knn_ctx_research_blocks", "knn_ctx_step_n", "knn_ctx_profile_merge",
     "knn_ctx_set_solo", "knn_ctx_search_meta", "knn_query", "knn_classify_query", "knn_ctx_set_keep_zero",
+    "knn_index_create", "knn_index_query", "knn_index_info", "knn_index_destroy",
 )
 DTYPES = {"f64": F64, "f32": F32, F64: F64, F32: F32}
+# a pack / index SOURCE may also be unsigned bytes (KNN_U8: never a block or search dtype)
+SRC_DTYPES = dict(DTYPES)
+SRC_DTYPES.update({"u8": U8, U8: U8})
 
 
 class KnnError(RuntimeError):
@@ -139,6 +144,10 @@ def _load():
         "knn_query": ([p, sz, p, sz, sz, i, p, i, i, i, p], i),
         "knn_classify_query": ([p, sz, i, i, i, p, sz, p, p, psz], i),
         "knn_ctx_set_keep_zero": ([p, i], i),
+        "knn_index_create": ([pp, p, sz, sz, i, i, p, i, i], i),
+        "knn_index_query": ([p, p, sz, i, i, i, i, p], i),
+        "knn_index_info": ([p, psz, psz, ctypes.POINTER(i), psz, ctypes.POINTER(i)], i),
+        "knn_index_destroy": ([p], i),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -346,8 +355,8 @@ def split_pack(d_dst, d_block, cap, n, dtype="f64", scale=1.0, stream=0):
 
 def block_pack(d_block, cap, rows, n, d_src, ld, layout, stream=0, dtype="f64", src_dtype="f64"):
     """knn_block_pack_dt on device pointers (ints).  layout COLMAJOR/ROWMAJOR;
-    dtype = block element type, src_dtype = that of d_src."""
-    _check(lib.knn_block_pack_dt(d_block, DTYPES[dtype], cap, rows, n, d_src, DTYPES[src_dtype],
+    dtype = block element type, src_dtype = that of d_src ("f64", "f32" or "u8")."""
+    _check(lib.knn_block_pack_dt(d_block, DTYPES[dtype], cap, rows, n, d_src, SRC_DTYPES[src_dtype],
                                  ld, layout, stream or None), "knn_block_pack_dt")
 
 
@@ -364,8 +373,9 @@ def s8_block_meta_offset(cap, n):
 
 def block_pack_s8(d_sblock, cap, rows, n, d_src, ld, layout, stream=0, dtype="f64", src_dtype="f64"):
     """knn_block_pack_s8: the speculative byte block (x - 128) + meta straight
-    from the source (valid for the search iff s8_spec_ok(reduced meta))."""
-    _check(lib.knn_block_pack_s8(d_sblock, DTYPES[dtype], cap, rows, n, d_src, DTYPES[src_dtype], ld, layout,
+    from the source (valid for the search iff s8_spec_ok(reduced meta));
+    src_dtype "f64", "f32" or "u8"."""
+    _check(lib.knn_block_pack_s8(d_sblock, DTYPES[dtype], cap, rows, n, d_src, SRC_DTYPES[src_dtype], ld, layout,
                                  stream or None), "knn_block_pack_s8")
 
 
@@ -380,6 +390,122 @@ def _close_all():
     # teardown runs after Python's atexit handlers)
     for c in list(_live_contexts):
         c.close()
+
+
+INDEX_DEVICE_SRC = 2  # KNN_INDEX_DEVICE_SRC
+INDEX_DEVICE_OUT = 4  # KNN_INDEX_DEVICE_OUT
+IndexInfo = collections.namedtuple("IndexInfo", "m n nblocks device_bytes last_bits")
+_NP_SRC = {np.dtype(np.uint8): U8, np.dtype(np.float32): F32, np.dtype(np.float64): F64}
+
+
+def _is_device_tensor(a):
+    return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "data_ptr") and a.is_cuda
+
+
+def _on_index_device(t, what):
+    """the index lives on device 0: a pointer into another device's memory is
+    no argument for it.  Work pending on torch's current stream is waited for
+    (the library reads and writes on the NULL stream)."""
+    import torch
+    if t.device.index != 0:
+        raise ValueError("%s must be on cuda:0 (the index's device), got %s" % (what, t.device))
+    torch.cuda.current_stream(t.device).synchronize()
+
+
+def _index_source(A, layout, what):
+    """(pointer, keep-alive, rows, n, layout code, src dtype, device flag) of a
+    corpus or query array: uint8 / float32 / float64 numpy arrays and torch GPU
+    tensors go in their own type, anything else as float64 on the host."""
+    if _is_device_tensor(A):
+        import torch
+        code = {torch.uint8: U8, torch.float32: F32, torch.float64: F64}.get(A.dtype)
+        if code is None:
+            A = A.to(torch.float64)
+            code = F64
+        if A.dim() != 2:
+            raise ValueError("%s must be 2-D, got %r" % (what, tuple(A.shape)))
+        buf = A.t().contiguous() if layout == "col" else A.contiguous()
+        _on_index_device(buf, what)
+        return (ctypes.c_void_p(buf.data_ptr()), buf, A.shape[0], A.shape[1],
+                COLMAJOR if layout == "col" else ROWMAJOR, code, INDEX_DEVICE_SRC)
+    A = np.asarray(A)
+    if A.dtype not in _NP_SRC:
+        A = A.astype(np.float64)
+    if A.ndim != 2:
+        raise ValueError("%s must be 2-D, got %r" % (what, A.shape))
+    buf = np.asfortranarray(A) if layout == "col" else np.ascontiguousarray(A)
+    return _ptr(buf), buf, A.shape[0], A.shape[1], COLMAJOR if layout == "col" else ROWMAJOR, _NP_SRC[A.dtype], 0
+
+
+class Index:
+    """knn_index_t: a corpus packed once and resident on the device, queried
+    many times (include/knn.h).  X: (m, n) numpy array or torch GPU tensor of
+    uint8, float32 or float64 (other types: float64 on the host); the index
+    keeps nothing of X after the constructor returns."""
+
+    def __init__(self, X, labels=None, layout="row", dtype="f64"):
+        self._h = ctypes.c_void_p()
+        ptr, keep, m, n, lay, src, dev = _index_source(X, layout, "X")
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.float64)
+        if lab is not None and lab.shape[0] != m:
+            raise ValueError("labels must have %d entries, got %d" % (m, lab.shape[0]))
+        _check(lib.knn_index_create(ctypes.byref(self._h), ptr, m, n, lay, src, _ptr(lab), DTYPES[dtype], dev),
+               "knn_index_create")
+        del keep
+        self.m, self.n, self.layout, self.dtype = m, n, layout, dtype
+        _live_contexts.add(self)
+
+    def close(self):
+        if self._h:
+            lib.knn_index_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        if not sys.is_finalizing():
+            self.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def query(self, Q, k=30, keep_zero=True, out=None):
+        """knn_index_query: the k nearest corpus rows of every row of Q
+        ((mq, n), in the index's layout argument; types as X, its own).
+        out: a torch GPU uint8 buffer of mq*k*16 bytes receives the records on
+        the device (labels left 0) and is returned; otherwise a (mq, k)
+        NB_DTYPE array.  Returns (neighbours, device seconds of this call)."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        ptr, keep, mq, n, lay, src, flags = _index_source(Q, self.layout, "Q")
+        if n != self.n:
+            raise ValueError("Q must be (mq, %d), got (%d, %d)" % (self.n, mq, n))
+        if keep_zero:
+            flags |= QUERY_KEEP_ZERO
+        if out is not None:
+            if not _is_device_tensor(out) or not out.is_contiguous() or \
+                    out.numel() * out.element_size() < mq * k * NB_DTYPE.itemsize:
+                raise ValueError("out must be a contiguous torch GPU buffer of >= %d bytes" %
+                                 (mq * k * NB_DTYPE.itemsize))
+            _on_index_device(out, "out")
+            flags |= INDEX_DEVICE_OUT
+            res, optr = out, ctypes.c_void_p(out.data_ptr())
+        else:
+            res = np.zeros((mq, k), dtype=NB_DTYPE)
+            optr = _ptr(res)
+        _check(lib.knn_index_query(self._h, ptr, mq, lay, src, k, flags, optr), "knn_index_query")
+        del keep
+        return res, lib.knn_last_search_seconds()
+
+    def info(self):
+        """knn_index_info: IndexInfo(m, n, nblocks, device_bytes, last_bits)."""
+        m, n, db = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+        nb, bits = ctypes.c_int(), ctypes.c_int()
+        _check(lib.knn_index_info(self._h, ctypes.byref(m), ctypes.byref(n), ctypes.byref(nb), ctypes.byref(db),
+                                  ctypes.byref(bits)), "knn_index_info")
+        return IndexInfo(m.value, n.value, nb.value, db.value, bits.value)
 
 
 class Context:
