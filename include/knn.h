@@ -246,6 +246,33 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * restated from their sizes) and knn_ctx_contraction_bits of
  * the last query (8, 16, 32 or 64; 0 before the first).
  *
+ * knn_index_add: rows that arrive later (blk:100-109's pack, without
+ * repacking what is resident).  X is rows x n in `layout`, of src_dtype, its
+ * own (KNN_INDEX_DEVICE_SRC: a device pointer); the rows take the 1-based ids
+ * m+1 .. m+rows, m grows, and later queries take their ids from the new m.
+ * The source is uploaded in its own type and packed into the last block's free
+ * rows (knn_block_append_dt), then into new blocks of the index's capacity;
+ * the touched blocks' meta is MAX-reduced into the corpus meta; an index with
+ * byte blocks appends the same rows to them straight from the source
+ * (knn_block_append_s8) as long as the corpus meta still passes
+ * knn_s8_spec_ok.  When it no longer does -- a row outside [0, 255] or not an
+ * integer was added -- the byte blocks are freed and never come back: queries
+ * take the element path from then on, exact as ever, and an index created
+ * without byte blocks never gains them.  labels: rows doubles when the index
+ * holds labels, NULL when it holds none.  Every block keeps one capacity.
+ * With KNN_QUERY_BLOCK set it is fixed; otherwise, when the add would leave
+ * more than 8 blocks (one fused byte launch) and the capacity is below
+ * knn_query's choice for n, the index is first re-blocked: the capacity
+ * doubles until at most 8 blocks remain (or that limit is reached), the rows
+ * and norms move device to device, the byte blocks are converted again from
+ * the element blocks, and the kept context and tile buffers are dropped (the
+ * next query recreates them) -- moved bytes stay O(rows added) amortised.
+ * The caller may free or overwrite X when the call returns.  If the call
+ * fails after its argument checks, the index answers queries as before it.
+ * KNN_ERR_INVALID: NULL index or X, rows == 0, a bad layout, unknown flag bits,
+ * m + rows > INT32_MAX, labels where the index has none or none where it has;
+ * KNN_ERR_UNSUPPORTED: an unknown src_dtype -- before any device call.
+ *
  * KNN_ERR_INVALID: NULL index, X, Q or out, zero m, mq or n, k <= 0, a bad
  * layout, unknown flag bits, m + mq > INT32_MAX; KNN_ERR_UNSUPPORTED: an
  * unknown src_dtype, dtype not KNN_F64 / KNN_F32, k above the dtype's limit
@@ -261,6 +288,8 @@ KNN_API int knn_index_create(knn_index_t **index, const void *X, size_t m, size_
                              int src_dtype, const double *labels, int dtype, int flags);
 KNN_API int knn_index_query(knn_index_t *index, const void *Q, size_t mq, int layout, int src_dtype,
                             int k, int flags, knn_neighbour_t *out);
+KNN_API int knn_index_add(knn_index_t *index, const void *X, size_t rows, int layout, int src_dtype,
+                          const double *labels, int flags);
 KNN_API int knn_index_info(const knn_index_t *index, size_t *m, size_t *n, int *nblocks,
                            size_t *device_bytes, int *last_bits);
 KNN_API int knn_index_destroy(knn_index_t *index);
@@ -378,6 +407,18 @@ KNN_API int knn_block_pack(void *d_block, size_t cap, size_t rows, size_t n, con
  * block from a KNN_U8 source is byte for byte the block from the fp64 one. */
 KNN_API int knn_block_pack_dt(void *d_block, int dtype, size_t cap, size_t rows, size_t n,
                       const void *d_src, int src_dtype, size_t ld, int layout, void *stream);
+/* Rows that arrive later: write block rows row0 .. row0+rows-1 of a block
+ * packed before with the same cap, n and dtype, from a rows x n source
+ * (layouts, ld and source types as knn_block_pack_dt) -- the rows, their
+ * norms, and the meta atomicMax'ed into the words already there; nothing else
+ * of the block is touched.  A block packed over its first rows and appended
+ * to in any pieces is byte for byte the block one knn_block_pack_dt of all
+ * the rows writes (a row's norm is summed in the same order wherever the row
+ * lands).  Launches are sized by `rows`, not cap.  KNN_ERR_INVALID: row0 +
+ * rows > cap, rows == 0, a NULL pointer, dtype or src_dtype as
+ * knn_block_pack_dt. */
+KNN_API int knn_block_append_dt(void *d_block, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
+                                const void *d_src, int src_dtype, size_t ld, int layout, void *stream);
 
 typedef struct knn_ctx knn_ctx_t;
 
@@ -421,6 +462,11 @@ KNN_API size_t knn_s8_block_bytes(size_t cap, size_t n);
 KNN_API size_t knn_s8_block_meta_offset(size_t cap, size_t n);
 KNN_API int knn_block_pack_s8(void *d_sblock, int dtype, size_t cap, size_t rows, size_t n, const void *d_src,
                               int src_dtype, size_t ld, int layout, void *stream);
+/* knn_block_append_dt for a byte block packed by knn_block_pack_s8: the byte
+ * rows, both norm words of each row and the meta (word 7 stays 1); the same
+ * byte-for-byte contract against one knn_block_pack_s8 of all the rows. */
+KNN_API int knn_block_append_s8(void *d_sblock, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
+                                const void *d_src, int src_dtype, size_t ld, int layout, void *stream);
 KNN_API int knn_s8_spec_ok(const double *h_meta, size_t n, int dtype);
 /* begin from the query block's speculative byte block (h_meta: the reduced
  * meta, host; KNN_ERR_INVALID unless knn_s8_spec_ok).  The element block is

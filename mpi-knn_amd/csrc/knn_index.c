@@ -14,6 +14,8 @@
  * corpus block, end, the int8 re-search where it applies, then the exact
  * rescan over every block.  The records of every tile stay on the device
  * until the last tile is done: a timed span holds no copy to the host.
+ * knn_index_add repeats build_pack / build_finish for rows that arrive later,
+ * with the packs at a row offset (knn_block_append_dt / _s8, defined here).
  */
 #include "knn_internal.h"
 
@@ -36,12 +38,14 @@ struct knn_index {
     size_t m, n;
     /* the corpus: nblk blocks of capacity cap; s8[] only when have_s8 */
     size_t cap, nblk;
+    size_t nalloc;                    /* entries of the per-block arrays (>= nblk: knn_index_add grows them) */
     void **blk, **s8;
     size_t *cnc, *cbase;
     int have_s8;
     double cmeta[KNN_META_DOUBLES];   /* host copy of the corpus's reduced meta */
     double *chm;                      /* the blocks' meta as read back (8 doubles a block) */
     double *labels;
+    size_t lab_cap;                   /* doubles allocated at labels (>= m) */
     /* kept between queries: the context (for k, tile_cap query rows), ntile
      * tile buffers of capacity tile_cap (byte forms allocated on first use),
      * the records of a host-out call, the reduced meta, the span's events */
@@ -125,6 +129,7 @@ static int index_alloc(knn_index_t **out, size_t m, size_t n, int dtype)
     const size_t fit = fit_rows(n, dtype);
     ix->cap = env_rows("KNN_QUERY_BLOCK", m < fit ? m : fit, m);
     ix->nblk = (m + ix->cap - 1) / ix->cap;   /* (<= INT32_MAX) */
+    ix->nalloc = ix->nblk;
     ix->blk = (void **)calloc(ix->nblk, sizeof(void *));
     ix->s8 = (void **)calloc(ix->nblk, sizeof(void *));
     ix->cnc = (size_t *)calloc(2 * ix->nblk, sizeof(size_t));
@@ -398,6 +403,7 @@ int knn_index_create(knn_index_t **index, const void *X, size_t m, size_t n, int
     void *d_X = NULL;
     if (labels) {
         ix->labels = (double *)malloc(m * sizeof(double));
+        ix->lab_cap = m;
         if (ix->labels) memcpy(ix->labels, labels, m * sizeof(double));
         else rc = KNN_ERR_NOMEM;
     }
@@ -452,6 +458,268 @@ int knn_index_query(knn_index_t *ix, const void *Q, size_t mq, int layout, int s
     hipFree(d_Q);
     if (!rc && !dev_out && ix->labels) fill_labels(out, cnt, ix->labels);
     return rc;
+}
+
+/* ------------------------------------------------------------------ add */
+
+/* Rows that arrive later: block rows row0 .. of a block packed before
+ * (include/knn.h).  The entry points live here, beside their first user, and
+ * not with knn_block_pack_* in knn_engine.c: that file is also built on its
+ * own against stub launchers (tests/engine_trace). */
+int knn_block_append_dt(void *d_block, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
+                        const void *d_src, int src_dtype, size_t ld, int layout, void *stream)
+{
+    if (!d_block || !d_src || rows == 0 || n == 0 || cap > 0x7fffffffULL || row0 > cap || rows > cap - row0 ||
+        n > 0x7fffffffULL || !dtype_ok(dtype) || !knn_src_esize(src_dtype))
+        return KNN_ERR_INVALID;
+    if (layout == KNN_COLMAJOR ? ld < rows : (layout == KNN_ROWMAJOR ? ld < n : 1)) return KNN_ERR_INVALID;
+    return knn_launch_append(d_block, dtype, cap, row0, rows, n, d_src, src_dtype, ld, layout, stream);
+}
+
+int knn_block_append_s8(void *d_sblock, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
+                        const void *d_src, int src_dtype, size_t ld, int layout, void *stream)
+{
+    if (!d_sblock || !d_src || rows == 0 || n == 0 || cap > 0x7fffffffULL || row0 > cap || rows > cap - row0 ||
+        n > KNN_I8_MAX_N || !dtype_ok(dtype) || !knn_src_esize(src_dtype))
+        return KNN_ERR_INVALID;
+    if (layout == KNN_COLMAJOR ? ld < rows : (layout == KNN_ROWMAJOR ? ld < n : 1)) return KNN_ERR_INVALID;
+    return knn_launch_append_s8(d_sblock, dtype, cap, row0, rows, n, d_src, src_dtype, ld, layout, stream);
+}
+
+
+/* the per-block arrays for at least nb blocks, their nblk entries kept */
+static int index_grow_arrays(knn_index_t *ix, size_t nb)
+{
+    if (nb <= ix->nalloc) return KNN_OK;
+    const size_t na = 2 * ix->nalloc > nb ? 2 * ix->nalloc : nb;
+    void **blk = (void **)calloc(na, sizeof(void *)), **s8 = (void **)calloc(na, sizeof(void *));
+    size_t *cnc = (size_t *)calloc(2 * na, sizeof(size_t));
+    double *chm = (double *)calloc(na * KNN_META_DOUBLES, sizeof(double));
+    if (!blk || !s8 || !cnc || !chm) {
+        free(blk);
+        free(s8);
+        free(cnc);
+        free(chm);
+        return KNN_ERR_NOMEM;
+    }
+    memcpy(blk, ix->blk, ix->nblk * sizeof(void *));
+    memcpy(s8, ix->s8, ix->nblk * sizeof(void *));
+    memcpy(cnc, ix->cnc, ix->nblk * sizeof(size_t));
+    memcpy(cnc + na, ix->cbase, ix->nblk * sizeof(size_t));
+    memcpy(chm, ix->chm, ix->nblk * KNN_META_DOUBLES * sizeof(double));
+    free(ix->blk);
+    free(ix->s8);
+    free(ix->cnc);
+    free(ix->chm);
+    ix->blk = blk;
+    ix->s8 = s8;
+    ix->cnc = cnc;
+    ix->cbase = cnc + na;
+    ix->chm = chm;
+    ix->nalloc = na;
+    return KNN_OK;
+}
+
+/* The corpus in blocks of capacity ncap (> cap): element rows and norms move
+ * device to device, a new block's meta is the max of the blocks merged into
+ * it, and the byte blocks are converted again from the new element blocks
+ * (knn_launch_shadow8 with the corpus meta: for knn_s8_spec_ok data the image
+ * the source pack writes on every corpus row; rows past a block's nc are not
+ * searched).  No search reads a corpus byte block's trailing meta (begin_s8
+ * and step_shadow_n take the reduced meta as arguments), but a later
+ * knn_block_append_s8 takes its atomicMax into it: it is written.  Old and new
+ * blocks are resident together until the last copy is done.  All or nothing. */
+static int index_reblock(knn_index_t *ix, size_t ncap)
+{
+    const size_t n = ix->n, es = knn_esize(ix->dtype), np = knn_n_pad_dt(n, ix->dtype);
+    const size_t nb = (ix->m + ncap - 1) / ncap;
+    const size_t orp = knn_rows_pad(ix->cap), nrp = knn_rows_pad(ncap);
+    void **blk = (void **)calloc(nb, sizeof(void *)), **s8 = (void **)calloc(nb, sizeof(void *));
+    size_t *cnc = (size_t *)calloc(2 * nb, sizeof(size_t));
+    double *chm = (double *)calloc(nb * KNN_META_DOUBLES, sizeof(double));
+    int rc = blk && s8 && cnc && chm ? KNN_OK : KNN_ERR_NOMEM;
+    for (size_t b = 0; b < nb && !rc; b++) {
+        const size_t bytes = knn_block_bytes_dt(ncap, n, ix->dtype);
+        if (hipMalloc(&blk[b], bytes) != hipSuccess) rc = KNN_ERR_NOMEM;
+        else if (hipMemsetAsync(blk[b], 0, bytes, NULL) != hipSuccess) rc = KNN_ERR_HIP;
+        if (!rc && ix->have_s8 && hipMalloc(&s8[b], knn_s8_bytes(ncap, n)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    }
+    /* runs of rows that lie in one old and one new block */
+    for (size_t g = 0; g < ix->m && !rc;) {
+        const size_t ob = g / ix->cap, oo = g % ix->cap, b = g / ncap, no = g % ncap;
+        const size_t len = ix->cnc[ob] - oo < ncap - no ? ix->cnc[ob] - oo : ncap - no;
+        const char *src = (const char *)ix->blk[ob];
+        char *dst = (char *)blk[b];
+        if (hipMemcpyAsync(dst + no * np * es, src + oo * np * es, len * np * es, hipMemcpyDeviceToDevice, NULL) !=
+                hipSuccess ||
+            hipMemcpyAsync(dst + (nrp * np + no) * es, src + (orp * np + oo) * es, len * es, hipMemcpyDeviceToDevice,
+                           NULL) != hipSuccess)
+            rc = KNN_ERR_HIP;
+        meta_max(chm + b * KNN_META_DOUBLES, ix->chm + ob * KNN_META_DOUBLES, 1);
+        g += len;
+    }
+    if (!rc && ix->have_s8) {
+        memcpy(ix->red, ix->cmeta, KNN_META_DOUBLES * sizeof(double));
+        if (hipMemcpyAsync(ix->d_meta, ix->red, KNN_META_DOUBLES * sizeof(double), hipMemcpyHostToDevice, NULL) !=
+            hipSuccess)
+            rc = KNN_ERR_HIP;
+    }
+    for (size_t b = 0; b < nb && !rc; b++) {
+        double hm[KNN_META_DOUBLES];
+        memcpy(hm, chm + b * KNN_META_DOUBLES, sizeof(hm));
+        hm[KNN_META_S8] = 0.0;   /* (an element block's word 7) */
+        if (hipMemcpy((char *)blk[b] + knn_block_meta_offset_dt(ncap, n, ix->dtype), hm, sizeof(hm),
+                      hipMemcpyHostToDevice) != hipSuccess)
+            rc = KNN_ERR_HIP;
+        if (rc || !ix->have_s8) continue;
+        rc = knn_launch_shadow8(s8[b], blk[b], ix->dtype, nrp, n, ix->d_meta, NULL);
+        hm[KNN_META_S8] = 1.0;
+        if (!rc && hipMemcpy((char *)s8[b] + knn_s8_meta_offset(ncap, n), hm, sizeof(hm), hipMemcpyHostToDevice) !=
+                       hipSuccess)
+            rc = KNN_ERR_HIP;
+    }
+    if (!rc) rc = stream_wait();
+    else hipStreamSynchronize(NULL);
+    if (rc) {
+        for (size_t b = 0; b < nb; b++) {
+            if (blk) hipFree(blk[b]);
+            if (s8) hipFree(s8[b]);
+        }
+        free(blk);
+        free(s8);
+        free(cnc);
+        free(chm);
+        return rc;
+    }
+    /* the context was made for the old capacity */
+    free_query_state(ix);
+    for (size_t b = 0; b < ix->nblk; b++) {
+        hipFree(ix->blk[b]);
+        hipFree(ix->s8[b]);
+    }
+    free(ix->blk);
+    free(ix->s8);
+    free(ix->cnc);
+    free(ix->chm);
+    ix->blk = blk;
+    ix->s8 = s8;
+    ix->cnc = cnc;
+    ix->cbase = cnc + nb;
+    ix->chm = chm;
+    ix->cap = ncap;
+    ix->nblk = ix->nalloc = nb;
+    for (size_t b = 0; b < nb; b++) {
+        ix->cbase[b] = b * ncap;
+        ix->cnc[b] = ix->m - ix->cbase[b] < ncap ? ix->m - ix->cbase[b] : ncap;
+    }
+    return KNN_OK;
+}
+
+/* `rows` new rows (global rows m ..) from the device source d_X into buf[]:
+ * the last block's free rows by an append, then fresh blocks of the index's
+ * capacity by a pack; element blocks (s8 = 0: the touched blocks' meta on its
+ * way to chm) or byte blocks.  NULL stream, no wait. */
+static int add_rows(knn_index_t *ix, void **buf, const void *d_X, size_t rows, int layout, int src_dtype, int s8)
+{
+    const size_t es = knn_src_esize(src_dtype), n = ix->n, cap = ix->cap;
+    const size_t ld = layout == KNN_COLMAJOR ? rows : n;
+    for (size_t r = 0; r < rows;) {
+        const size_t g = ix->m + r, b = g / cap, off = g % cap;
+        const size_t len = cap - off < rows - r ? cap - off : rows - r;
+        const char *src = (const char *)d_X + (layout == KNN_COLMAJOR ? r : r * n) * es;
+        if (b < ix->nblk) {
+            RCHK(s8 ? knn_block_append_s8(buf[b], ix->dtype, cap, off, len, n, src, src_dtype, ld, layout, NULL)
+                    : knn_block_append_dt(buf[b], ix->dtype, cap, off, len, n, src, src_dtype, ld, layout, NULL));
+        } else {
+            const size_t bytes = s8 ? knn_s8_bytes(cap, n) : knn_block_bytes_dt(cap, n, ix->dtype);
+            if (!buf[b] && hipMalloc(&buf[b], bytes) != hipSuccess) return KNN_ERR_NOMEM;
+            RCHK(s8 ? knn_block_pack_s8(buf[b], ix->dtype, cap, len, n, src, src_dtype, ld, layout, NULL)
+                    : knn_block_pack_dt(buf[b], ix->dtype, cap, len, n, src, src_dtype, ld, layout, NULL));
+        }
+        if (!s8 && hipMemcpyAsync(ix->chm + b * KNN_META_DOUBLES,
+                                  (const char *)buf[b] + knn_block_meta_offset_dt(cap, n, ix->dtype),
+                                  KNN_META_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, NULL) != hipSuccess)
+            return KNN_ERR_HIP;
+        r += len;
+    }
+    return KNN_OK;
+}
+
+int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int src_dtype, const double *labels,
+                  int flags)
+{
+    if (!ix || !X || rows == 0) return KNN_ERR_INVALID;
+    if (!knn_src_esize(src_dtype)) return KNN_ERR_UNSUPPORTED;
+    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (flags & ~KNN_INDEX_DEVICE_SRC) return KNN_ERR_INVALID;
+    if (rows > 0x7fffffffULL || ix->m + rows > 0x7fffffffULL) return KNN_ERR_INVALID;
+    if ((ix->labels != NULL) != (labels != NULL)) return KNN_ERR_INVALID;
+    if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
+    const size_t m1 = ix->m + rows;
+    /* one capacity for every block: fixed under KNN_QUERY_BLOCK; else doubled
+     * while the add would leave more than one fused byte launch of blocks */
+    const size_t fit = fit_rows(ix->n, ix->dtype);
+    if (!env_rows("KNN_QUERY_BLOCK", 0, (size_t)-1) && (m1 + ix->cap - 1) / ix->cap > KNN_I8_MAXBLK && ix->cap < fit) {
+        size_t ncap = ix->cap;
+        while ((m1 + ncap - 1) / ncap > KNN_I8_MAXBLK && ncap < fit) ncap = 2 * ncap < fit ? 2 * ncap : fit;
+        RCHK(index_reblock(ix, ncap));
+    }
+    const size_t nb0 = ix->nblk, nb1 = (m1 + ix->cap - 1) / ix->cap;
+    RCHK(index_grow_arrays(ix, nb1));
+    if (labels && m1 > ix->lab_cap) {
+        const size_t lc = 2 * ix->lab_cap > m1 ? 2 * ix->lab_cap : m1;
+        double *l = (double *)realloc(ix->labels, lc * sizeof(double));
+        if (!l) return KNN_ERR_NOMEM;
+        ix->labels = l;
+        ix->lab_cap = lc;
+    }
+    void *d_X = NULL;
+    int rc = KNN_OK;
+    if (!(flags & KNN_INDEX_DEVICE_SRC)) rc = upload(&d_X, X, rows * ix->n * knn_src_esize(src_dtype));
+    const void *src = (flags & KNN_INDEX_DEVICE_SRC) ? X : d_X;
+    /* build_pack / build_finish's two parts for the new rows: the element
+     * rows and the touched blocks' meta, one wait, the corpus meta, the byte
+     * rows while it still allows them */
+    if (!rc) rc = add_rows(ix, ix->blk, src, rows, layout, src_dtype, 0);
+    if (!rc) rc = stream_wait();
+    double cmeta[KNN_META_DOUBLES];
+    memcpy(cmeta, ix->cmeta, sizeof(cmeta));
+    int keep_s8 = 0;
+    if (!rc) {
+        meta_max(cmeta, ix->chm + ix->m / ix->cap * KNN_META_DOUBLES, nb1 - ix->m / ix->cap);
+        keep_s8 = ix->have_s8 && knn_s8_spec_ok(cmeta, ix->n, ix->dtype);
+        if (keep_s8) rc = add_rows(ix, ix->s8, src, rows, layout, src_dtype, 1);
+    }
+    /* the packs have read the source before the call returns */
+    if (!rc) rc = stream_wait();
+    else hipStreamSynchronize(NULL);
+    hipFree(d_X);
+    if (rc) {
+        /* rows written past a block's nc are never read, and its meta only grew */
+        for (size_t b = nb0; b < nb1; b++) {
+            hipFree(ix->blk[b]);
+            hipFree(ix->s8[b]);
+            ix->blk[b] = ix->s8[b] = NULL;
+        }
+        return rc;
+    }
+    if (ix->have_s8 && !keep_s8) {
+        /* a value outside the byte image arrived: the element path from now on */
+        for (size_t b = 0; b < nb0; b++) {
+            hipFree(ix->s8[b]);
+            ix->s8[b] = NULL;
+        }
+        ix->have_s8 = 0;
+    }
+    if (labels) memcpy(ix->labels + ix->m, labels, rows * sizeof(double));
+    memcpy(ix->cmeta, cmeta, sizeof(cmeta));
+    ix->nblk = nb1;
+    ix->m = m1;
+    for (size_t b = 0; b < nb1; b++) {
+        ix->cbase[b] = b * ix->cap;
+        ix->cnc[b] = m1 - ix->cbase[b] < ix->cap ? m1 - ix->cbase[b] : ix->cap;
+    }
+    return KNN_OK;
 }
 
 int knn_index_info(const knn_index_t *ix, size_t *m, size_t *n, int *nblocks, size_t *device_bytes, int *last_bits)

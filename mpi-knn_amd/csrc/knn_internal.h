@@ -205,6 +205,13 @@ int knn_launch_resolve8(unsigned char *flag, const int *list, int cnt, const int
 /* speculative byte block straight from the source (knn_block_pack_s8) */
 int knn_launch_pack_s8(void *dst, int dtype, size_t cap, size_t rows, size_t n, const void *src, int src_dtype,
                        size_t ld, int layout, void *stream);
+/* rows row0 .. row0 + rows - 1 of a block / byte block packed before, from a
+ * rows x n source (knn_block_append_dt / knn_block_append_s8): no meta memset,
+ * grids over `rows` */
+int knn_launch_append(void *blk, int dtype, size_t cap, size_t row0, size_t rows, size_t n, const void *src,
+                      int src_dtype, size_t ld, int layout, void *stream);
+int knn_launch_append_s8(void *dst, int dtype, size_t cap, size_t row0, size_t rows, size_t n, const void *src,
+                         int src_dtype, size_t ld, int layout, void *stream);
 /* INT-mode merge of int8 lane lists (kl = KNN_I8_KL_S / KNN_I8_KL, kp <= 64)
  * by ranking the candidates at or below the shared bound (k_merge_rank) */
 int knn_launch_merge_rank(int dtype, int kp, int kl, int k, const double *part_d, const int *part_i,

@@ -181,12 +181,24 @@ __device__ __forceinline__ double knn_cert_E(int n, double qn, double maxnorm, i
 // is reduced, then one atomicMax per word (non-negative doubles order like
 // their bits; the caller zeroes the meta).
 // ---------------------------------------------------------------------------
-struct knn_meta_acc {
+// (SEL, the append kernels' form: the two flags as selects.  The branches
+// below end in a store through a selected address, which keeps the struct in
+// scratch, 24 bytes a lane; the pack kernels keep the code they always had.)
+template <bool SEL>
+struct knn_meta_acc_t {
     double mabs = 0.0, nonint = 0.0, nonfin = 0.0, mpos = 0.0, mneg = 0.0;
     __device__ __forceinline__ void add(double v, double &s)
     {
         s = fma(v, v, s);
-        if (!__builtin_isfinite(v)) nonfin = 1.0;
+        if constexpr (SEL) {
+            const bool fin = __builtin_isfinite(v);
+            const double a = fabs(v);
+            nonfin = fin ? nonfin : 1.0;
+            mabs = fin && a > mabs ? a : mabs;
+            mpos = fin && v > mpos ? v : mpos;
+            mneg = fin && -v > mneg ? -v : mneg;
+            nonint = fin && v != rint(v) ? 1.0 : nonint;
+        } else if (!__builtin_isfinite(v)) nonfin = 1.0;
         else {
             const double a = fabs(v);
             mabs = a > mabs ? a : mabs;
@@ -196,10 +208,11 @@ struct knn_meta_acc {
         }
     }
 };
+typedef knn_meta_acc_t<false> knn_meta_acc;
 
 // workgroup reduction of the 6 meta words (64 W threads) + atomicMax
-template <int W>
-__device__ __forceinline__ void knn_meta_flush_w(const knn_meta_acc &a, double mnorm, double *meta)
+template <int W, typename A>
+__device__ __forceinline__ void knn_meta_flush_w(const A &a, double mnorm, double *meta)
 {
     __shared__ double red[W][6];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -220,7 +233,8 @@ __device__ __forceinline__ void knn_meta_flush_w(const knn_meta_acc &a, double m
         atomicMax((unsigned long long *)&meta[threadIdx.x], (unsigned long long)__double_as_longlong(v));
     }
 }
-__device__ __forceinline__ void knn_meta_flush(const knn_meta_acc &a, double mnorm, double *meta)
+template <typename A>
+__device__ __forceinline__ void knn_meta_flush(const A &a, double mnorm, double *meta)
 {
     knn_meta_flush_w<4>(a, mnorm, meta);
 }
@@ -230,18 +244,27 @@ __device__ __forceinline__ void knn_meta_flush(const knn_meta_acc &a, double mno
 // column, 512 B; writes: 64 consecutive features of a row).  Thread (ty,
 // tx) accumulates row tx's squared terms over columns = ty mod 4; the four
 // partials are summed at the end (a fixed order).
-template <typename T, typename S>
-__global__ __launch_bounds__(256) void k_pack_col(T *__restrict__ blk, size_t rows, size_t rows_pad,
-                                                  int n, int n_pad, const S *__restrict__ src, size_t ld)
+//
+// APPEND (knn_block_append_dt / _s8, every pack kernel below): the source's
+// rows 0 .. rows-1 land at block rows row0 .. of a block packed before.  Only
+// those rows, their norms and the meta are written (the grid covers `rows`,
+// not rows_pad: padding rows are the first pack's), and the meta is
+// atomicMax'ed into the words already there.  A row is summed by the same
+// lanes in the same order wherever it lands, so pack + appends write the
+// bytes one pack of all the rows writes.
+template <typename T, typename S, bool APPEND>
+__global__ __launch_bounds__(256) void k_pack_col(T *__restrict__ blk, size_t rows, size_t rows_pad, int n,
+                                                  int n_pad, const S *__restrict__ src, size_t ld, size_t row0)
 {
     __shared__ T tile[64][65];
     __shared__ double part[4][64];
     T *norms = blk + rows_pad * (size_t)n_pad;
     double *meta = (double *)(norms + rows_pad);
+    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;   // rows written; the first one's block row
     const size_t i0 = (size_t)blockIdx.x * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const size_t i = i0 + tx;
-    knn_meta_acc ma;
+    knn_meta_acc_t<APPEND> ma;
     double s = 0.0;
     for (int j0 = 0; j0 < n_pad; j0 += 64) {
 #pragma unroll 4
@@ -255,15 +278,15 @@ __global__ __launch_bounds__(256) void k_pack_col(T *__restrict__ blk, size_t ro
         const int j = j0 + tx;
 #pragma unroll 4
         for (int ii = ty; ii < 64; ii += 4)
-            if (i0 + ii < rows_pad && j < n_pad) blk[(i0 + ii) * n_pad + j] = tile[tx][ii];
+            if (i0 + ii < lim && j < n_pad) blk[(d0 + i0 + ii) * n_pad + j] = tile[tx][ii];
         __syncthreads();
     }
     part[ty][tx] = s;
     __syncthreads();
     double mnorm = 0.0;
-    if (ty == 0 && i < rows_pad) {
+    if (ty == 0 && i < lim) {
         const double nr = (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
-        norms[i] = (T)nr;
+        norms[d0 + i] = (T)nr;
         if (nr == nr) mnorm = nr;
         else ma.nonfin = 1.0;
     }
@@ -303,11 +326,12 @@ __device__ __forceinline__ int knn_spec8(T v)
 // that; rejected data is packed again from elements).
 // (Issuing the next tile's loads before converting this one -- 32 in
 // flight at RW = 64 -- measured slower: 106 -> 130 us for MNIST, rocprofv3.)
-template <typename T, typename S, int RW>
+template <typename T, typename S, int RW, bool APPEND>
 __global__ __launch_bounds__(256) void k_pack8_col(signed char *__restrict__ dst, size_t rows, size_t rows_pad,
-                                                   int n, int rs, const S *__restrict__ src, size_t ld)
+                                                   int n, int rs, const S *__restrict__ src, size_t ld, size_t row0)
 {
     constexpr int CG = 256 / RW;      // column groups
+    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
     constexpr int NE = 64 / CG;       // loads a thread a tile
     __shared__ unsigned char tb[64][RW + 4];   // [column of the tile][row]
     __shared__ double part[CG][RW];
@@ -319,7 +343,7 @@ __global__ __launch_bounds__(256) void k_pack8_col(signed char *__restrict__ dst
     const size_t i = i0 + tx;
     const bool live = i < rows;
     const S *xp = src + (live ? i : 0);
-    knn_meta_acc ma;
+    knn_meta_acc_t<APPEND> ma;
     double s = 0.0;
     unsigned si = 0u;
     for (int j0 = 0; j0 < rs; j0 += 64) {
@@ -340,13 +364,13 @@ __global__ __launch_bounds__(256) void k_pack8_col(signed char *__restrict__ dst
         __syncthreads();
         // row r = t / 4: 16 bytes at column 16 (t % 4) of the tile
         const int r = threadIdx.x >> 2, c0 = 16 * (threadIdx.x & 3);
-        if (r < RW && i0 + r < rows_pad && j0 + c0 < rs) {
+        if (r < RW && i0 + r < lim && j0 + c0 < rs) {
             unsigned w4[4];
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 w4[q] = (unsigned)tb[c0 + 4 * q][r] | ((unsigned)tb[c0 + 4 * q + 1][r] << 8) |
                         ((unsigned)tb[c0 + 4 * q + 2][r] << 16) | ((unsigned)tb[c0 + 4 * q + 3][r] << 24);
-            *(knn_v4i *)(dst + (i0 + r) * (size_t)rs + j0 + c0) = (knn_v4i){(int)w4[0], (int)w4[1], (int)w4[2], (int)w4[3]};
+            *(knn_v4i *)(dst + (d0 + i0 + r) * (size_t)rs + j0 + c0) = (knn_v4i){(int)w4[0], (int)w4[1], (int)w4[2], (int)w4[3]};
         }
         __syncthreads();
     }
@@ -354,7 +378,7 @@ __global__ __launch_bounds__(256) void k_pack8_col(signed char *__restrict__ dst
     ipart[ty][tx] = si;
     __syncthreads();
     double mnorm = 0.0;
-    if (ty == 0 && i < rows_pad) {
+    if (ty == 0 && i < lim) {
         double nr = 0.0;
         unsigned ni = 0u;
         if constexpr (CG == 4) {
@@ -367,31 +391,32 @@ __global__ __launch_bounds__(256) void k_pack8_col(signed char *__restrict__ dst
                 ni += ipart[q][tx];
             }
         }
-        norms[i8_norm_pos((int)i)] = i8_norm_word((int)i, (int)ni, rs);
-        norms[rows_pad + i8_norm_pos((int)i)] = i8_init_word((int)ni, rs);
+        norms[i8_norm_pos((int)(d0 + i))] = i8_norm_word((int)(d0 + i), (int)ni, rs);
+        norms[rows_pad + i8_norm_pos((int)(d0 + i))] = i8_init_word((int)ni, rs);
         if (nr == nr) mnorm = nr;
         else ma.nonfin = 1.0;
     }
     knn_meta_flush(ma, mnorm, meta);
-    if (blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
+    if (!APPEND && blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;   // (an append finds it set)
 }
 
 // row-major source: one wave per row, lane l converts the 8-element groups
 // l, l + 64, ... (one 8-byte store each); VEC: 16-byte-aligned rows, whole
 // groups read as 16-byte vectors (sift: 0.68 ms for 512 MB with scalar loads)
-template <typename T, typename S, bool VEC>
+template <typename T, typename S, bool VEC, bool APPEND>
 __global__ __launch_bounds__(256) void k_pack8_row(signed char *__restrict__ dst, size_t rows, size_t rows_pad,
-                                                   int n, int rs, const S *__restrict__ src, size_t ld)
+                                                   int n, int rs, const S *__restrict__ src, size_t ld, size_t row0)
 {
     typedef typename std::conditional<sizeof(S) == 8, dbl2, flt4>::type svec_t;
+    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
     constexpr int SV = 16 / (int)sizeof(S);
     int *norms = (int *)(dst + rows_pad * (size_t)rs);
     double *meta = (double *)(norms + 2 * rows_pad);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int ng = rs / 8;
-    knn_meta_acc ma;
+    knn_meta_acc_t<APPEND> ma;
     double mnorm = 0.0;
-    for (size_t r = (size_t)blockIdx.x * 4 + wave; r < rows_pad; r += (size_t)gridDim.x * 4) {
+    for (size_t r = (size_t)blockIdx.x * 4 + wave; r < lim; r += (size_t)gridDim.x * 4) {
         double s = 0.0;
         unsigned si = 0u;
         const S *x = src + r * ld;
@@ -421,21 +446,21 @@ __global__ __launch_bounds__(256) void k_pack8_row(signed char *__restrict__ dst
                 else hi |= ((unsigned)xi & 0xffu) << (8 * (e - 4));
             }
             typedef unsigned u2 __attribute__((ext_vector_type(2)));
-            *(u2 *)(dst + r * (size_t)rs + 8 * g) = (u2){lo, hi};
+            *(u2 *)(dst + (d0 + r) * (size_t)rs + 8 * g) = (u2){lo, hi};
         }
         for (int off = 32; off > 0; off >>= 1) {
             s += __shfl_xor(s, off);
             si += (unsigned)__shfl_xor((int)si, off);
         }
         if (lane == 0) {
-            norms[i8_norm_pos((int)r)] = i8_norm_word((int)r, (int)si, rs);
-            norms[rows_pad + i8_norm_pos((int)r)] = i8_init_word((int)si, rs);
+            norms[i8_norm_pos((int)(d0 + r))] = i8_norm_word((int)(d0 + r), (int)si, rs);
+            norms[rows_pad + i8_norm_pos((int)(d0 + r))] = i8_init_word((int)si, rs);
         }
         if (s == s) mnorm = s > mnorm ? s : mnorm;
         else ma.nonfin = 1.0;
     }
     knn_meta_flush(ma, mnorm, meta);
-    if (blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
+    if (!APPEND && blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
 }
 
 // row-major KNN_U8 source: the byte image is x ^ 0x80 (x - 128 as int8), so a
@@ -451,11 +476,14 @@ __global__ __launch_bounds__(256) void k_pack8_row(signed char *__restrict__ dst
 // inside n is read as a 16-byte vector; otherwise, in a row's tail group and
 // past n (ld > n), byte by byte.
 typedef unsigned knn_v4u __attribute__((ext_vector_type(4)));
-template <bool VEC>
+// APPEND: row groups are cut at `rows`, which a group may straddle: the rows
+// past it are neither stored nor given norm words.
+template <bool VEC, bool APPEND>
 __global__ __launch_bounds__(256) void k_pack8_row_u8(signed char *__restrict__ dst, size_t rows, size_t rows_pad,
                                                       int n, int rs, const unsigned char *__restrict__ src,
-                                                      size_t ld, int lpr)
+                                                      size_t ld, int lpr, size_t row0)
 {
+    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
     int *norms = (int *)(dst + rows_pad * (size_t)rs);
     double *meta = (double *)(norms + 2 * rows_pad);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -468,7 +496,7 @@ __global__ __launch_bounds__(256) void k_pack8_row_u8(signed char *__restrict__ 
     // turn).  rows_pad is a multiple of 128 and rpw divides 64, so a row group
     // lies below rows_pad as a whole or not at all (wave-uniform).
     constexpr int U = 4;
-    for (size_t rb = ((size_t)blockIdx.x * 4 + wave) * U * rpw; rb < rows_pad;
+    for (size_t rb = ((size_t)blockIdx.x * 4 + wave) * U * rpw; rb < lim;
          rb += (size_t)gridDim.x * 4 * U * rpw) {
         knn_v4u v[U];
         bool full[U];
@@ -481,8 +509,9 @@ __global__ __launch_bounds__(256) void k_pack8_row_u8(signed char *__restrict__ 
         }
 #pragma unroll
         for (int u = 0; u < U; u++) {
-            if (rb + (size_t)u * rpw >= rows_pad) break;
+            if (rb + (size_t)u * rpw >= lim) break;
             const size_t r = rb + (size_t)u * rpw + sub;
+            const bool wr = !APPEND || r < rows;
             // bytes, and 0xff where a byte is data
             unsigned w[4] = {v[u][0], v[u][1], v[u][2], v[u][3]};
             const unsigned fm = full[u] ? 0xffffffffu : 0u;
@@ -509,45 +538,46 @@ __global__ __launch_bounds__(256) void k_pack8_row_u8(signed char *__restrict__ 
                 }
                 w[q] = (w[q] ^ 0x80808080u) & live[q];
             }
-            if (has) *(knn_v4u *)(dst + r * (size_t)rs + 16 * g) = (knn_v4u){w[0], w[1], w[2], w[3]};
+            if (has && wr) *(knn_v4u *)(dst + (d0 + r) * (size_t)rs + 16 * g) = (knn_v4u){w[0], w[1], w[2], w[3]};
             for (int off = lpr >> 1; off > 0; off >>= 1) {
                 sx += (unsigned)__shfl_xor((int)sx, off);
                 si += (unsigned)__shfl_xor((int)si, off);
             }
-            if (g == 0) {
-                norms[i8_norm_pos((int)r)] = i8_norm_word((int)r, (int)si, rs);
-                norms[rows_pad + i8_norm_pos((int)r)] = i8_init_word((int)si, rs);
+            if (g == 0 && wr) {
+                norms[i8_norm_pos((int)(d0 + r))] = i8_norm_word((int)(d0 + r), (int)si, rs);
+                norms[rows_pad + i8_norm_pos((int)(d0 + r))] = i8_init_word((int)si, rs);
             }
             mnorm = sx > mnorm ? sx : mnorm;
         }
     }
-    knn_meta_acc ma;
+    knn_meta_acc_t<APPEND> ma;
     ma.mabs = ma.mpos = (double)mx;
     knn_meta_flush(ma, (double)mnorm, meta);
-    if (blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
+    if (!APPEND && blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
 }
 
 // Row-major source: one wave per row (lane-strided features, butterfly sum).
-template <typename T, typename S>
-__global__ __launch_bounds__(256) void k_pack_row(T *__restrict__ blk, size_t rows, size_t rows_pad,
-                                                  int n, int n_pad, const S *__restrict__ src, size_t ld)
+template <typename T, typename S, bool APPEND>
+__global__ __launch_bounds__(256) void k_pack_row(T *__restrict__ blk, size_t rows, size_t rows_pad, int n,
+                                                  int n_pad, const S *__restrict__ src, size_t ld, size_t row0)
 {
     T *norms = blk + rows_pad * (size_t)n_pad;
     double *meta = (double *)(norms + rows_pad);
+    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    knn_meta_acc ma;
+    knn_meta_acc_t<APPEND> ma;
     double mnorm = 0.0;
-    for (size_t i = (size_t)blockIdx.x * 4 + wave; i < rows_pad; i += (size_t)gridDim.x * 4) {
+    for (size_t i = (size_t)blockIdx.x * 4 + wave; i < lim; i += (size_t)gridDim.x * 4) {
         double s = 0.0;
         const S *x = src + i * ld;
-        T *o = blk + i * (size_t)n_pad;
+        T *o = blk + (d0 + i) * (size_t)n_pad;
         for (int j = lane; j < n_pad; j += 64) {
             const T v = (i < rows && j < n) ? (T)x[j] : (T)0;
             o[j] = v;
             ma.add((double)v, s);
         }
         for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) norms[i] = (T)s;
+        if (lane == 0) norms[d0 + i] = (T)s;
         if (s == s) mnorm = s > mnorm ? s : mnorm;
         else ma.nonfin = 1.0;
     }
@@ -2365,37 +2395,86 @@ __global__ void k_rescan_end(const int *__restrict__ fail_list, int nfail, int K
 // ---------------------------------------------------------------------------
 static int hip_status(void) { return hipGetLastError() == hipSuccess ? KNN_OK : KNN_ERR_HIP; }
 
+// append: rows row0 .. of a block packed before (knn_block_append_dt / _s8) --
+// no meta memset (the meta is max(old, new rows)), grids over `rows`
 template <typename T, typename S>
 static int launch_pack(T *blk, size_t cap, size_t rows, size_t n, const S *src, size_t ld,
-                       int layout, hipStream_t s)
+                       int layout, hipStream_t s, bool append = false, size_t row0 = 0)
 {
     constexpr int dt = sizeof(T) == 8 ? KNN_F64 : KNN_F32;
     const size_t rp = knn_rows_pad(cap), np = knn_n_pad_dt(n, dt);
+    if (append) {
+        if (layout == KNN_COLMAJOR) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_col<T, S, true>), dim3((unsigned)((rows + 63) / 64)), dim3(256), 0,
+                               s, blk, rows, rp, (int)n, (int)np, src, ld, row0);
+        } else {
+            const unsigned nb = (unsigned)((rows + 3) / 4 < 8192 ? (rows + 3) / 4 : 8192);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_row<T, S, true>), dim3(nb), dim3(256), 0, s, blk, rows, rp, (int)n,
+                               (int)np, src, ld, row0);
+        }
+        return hip_status();
+    }
     double *meta = (double *)(blk + rp * np + rp);
     if (hipMemsetAsync(meta, 0, KNN_META_DOUBLES * sizeof(double), s) != hipSuccess)
         return KNN_ERR_HIP;
     if (layout == KNN_COLMAJOR) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_col<T, S>), dim3((unsigned)((rp + 63) / 64)), dim3(256), 0, s,
-                           blk, rows, rp, (int)n, (int)np, src, ld);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_col<T, S, false>), dim3((unsigned)((rp + 63) / 64)), dim3(256), 0, s,
+                           blk, rows, rp, (int)n, (int)np, src, ld, (size_t)0);
     } else {
         const unsigned nb = (unsigned)((rp + 3) / 4 < 8192 ? (rp + 3) / 4 : 8192);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_row<T, S>), dim3(nb), dim3(256), 0, s, blk, rows, rp,
-                           (int)n, (int)np, src, ld);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_row<T, S, false>), dim3(nb), dim3(256), 0, s, blk, rows, rp,
+                           (int)n, (int)np, src, ld, (size_t)0);
+    }
+    return hip_status();
+}
+
+// the byte forms of an append: the same kernels' APPEND instantiations, grids over `rows`
+template <typename T, typename S>
+static int launch_append8(signed char *dst, size_t rp, size_t rs, size_t rows, size_t n, const S *src, size_t ld,
+                          int layout, hipStream_t s, size_t row0)
+{
+    if (layout == KNN_COLMAJOR) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_col<T, S, 64, true>), dim3((unsigned)((rows + 63) / 64)), dim3(256), 0,
+                           s, dst, rows, rp, (int)n, (int)rs, src, ld, row0);
+    } else if constexpr (sizeof(S) == 1) {
+        int lpr = 1;
+        while (lpr < 64 && 16 * (size_t)lpr < rs) lpr *= 2;
+        if (16 * (size_t)lpr < rs) return KNN_ERR_INVALID;
+        const size_t nw = (rows * lpr + 255) / 256;
+        const unsigned nb = (unsigned)((nw + 3) / 4 < 2048 ? (nw + 3) / 4 : 2048);
+        // (a source that starts at row0 * n of a larger array is rarely 16-byte aligned)
+        const bool vec = ((uintptr_t)src % 16 == 0) && ld % 16 == 0;
+        if (vec)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row_u8<true, true>), dim3(nb), dim3(256), 0, s, dst, rows, rp, (int)n, (int)rs, src,
+                               ld, lpr, row0);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row_u8<false, true>), dim3(nb), dim3(256), 0, s, dst, rows, rp, (int)n, (int)rs, src,
+                               ld, lpr, row0);
+    } else {
+        const unsigned nb = (unsigned)((rows + 3) / 4 < 8192 ? (rows + 3) / 4 : 8192);
+        const bool vec = ((uintptr_t)src % 16 == 0) && (ld * sizeof(S)) % 16 == 0;
+        if (vec)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, true, true>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
+                               (int)n, (int)rs, src, ld, row0);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, false, true>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
+                               (int)n, (int)rs, src, ld, row0);
     }
     return hip_status();
 }
 
 template <typename T, typename S>
 static int launch_pack8(signed char *dst, size_t cap, size_t rows, size_t n, const S *src, size_t ld, int layout,
-                        hipStream_t s)
+                        hipStream_t s, bool append = false, size_t row0 = 0)
 {
     const size_t rp = knn_rows_pad(cap), rs = knn_s8_rs(n);
+    if (append) return launch_append8<T, S>(dst, rp, rs, rows, n, src, ld, layout, s, row0);
     double *meta = (double *)(dst + knn_s8_meta_offset(cap, n));
     if (hipMemsetAsync(meta, 0, KNN_META_DOUBLES * sizeof(double), s) != hipSuccess) return KNN_ERR_HIP;
     if (layout == KNN_COLMAJOR) {
         // (32-row workgroups, twice as many: 107.5 against 105.7 us for MNIST)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_col<T, S, 64>), dim3((unsigned)((rp + 63) / 64)), dim3(256), 0,
-                           s, dst, rows, rp, (int)n, (int)rs, src, ld);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_col<T, S, 64, false>), dim3((unsigned)((rp + 63) / 64)), dim3(256), 0,
+                           s, dst, rows, rp, (int)n, (int)rs, src, ld, (size_t)0);
     } else if constexpr (sizeof(S) == 1) {
         // KNN_U8: lpr lanes a row (a power of two >= rs / 16), 64 / lpr rows a wave
         int lpr = 1;
@@ -2407,37 +2486,47 @@ static int launch_pack8(signed char *dst, size_t cap, size_t rows, size_t n, con
         const unsigned nb = (unsigned)((nw + 3) / 4 < 2048 ? (nw + 3) / 4 : 2048);
         const bool vec = ((uintptr_t)src % 16 == 0) && ld % 16 == 0;
         if (vec)
-            hipLaunchKernelGGL(k_pack8_row_u8<true>, dim3(nb), dim3(256), 0, s, dst, rows, rp, (int)n, (int)rs, src,
-                               ld, lpr);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row_u8<true, false>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
+                               (int)n, (int)rs, src, ld, lpr, (size_t)0);
         else
-            hipLaunchKernelGGL(k_pack8_row_u8<false>, dim3(nb), dim3(256), 0, s, dst, rows, rp, (int)n, (int)rs, src,
-                               ld, lpr);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row_u8<false, false>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
+                               (int)n, (int)rs, src, ld, lpr, (size_t)0);
     } else {
         const unsigned nb = (unsigned)((rp + 3) / 4 < 8192 ? (rp + 3) / 4 : 8192);
         const bool vec = ((uintptr_t)src % 16 == 0) && (ld * sizeof(S)) % 16 == 0;
         if (vec)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, true>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
-                               (int)n, (int)rs, src, ld);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, true, false>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
+                               (int)n, (int)rs, src, ld, (size_t)0);
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, false>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
-                               (int)n, (int)rs, src, ld);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, false, false>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
+                               (int)n, (int)rs, src, ld, (size_t)0);
     }
     return hip_status();
 }
 
-extern "C" int knn_launch_pack_s8(void *dst, int dtype, size_t cap, size_t rows, size_t n, const void *src,
-                                  int src_dtype, size_t ld, int layout, void *stream)
+static int pack_s8_any(void *dst, int dtype, size_t cap, size_t rows, size_t n, const void *src, int src_dtype,
+                       size_t ld, int layout, void *stream, bool ap, size_t row0)
 {
     hipStream_t s = (hipStream_t)stream;
     signed char *d = (signed char *)dst;
-    if (dtype == KNN_F64 && src_dtype == KNN_F64) return launch_pack8<double>(d, cap, rows, n, (const double *)src, ld, layout, s);
-    if (dtype == KNN_F64 && src_dtype == KNN_F32) return launch_pack8<double>(d, cap, rows, n, (const float *)src, ld, layout, s);
-    if (dtype == KNN_F32 && src_dtype == KNN_F64) return launch_pack8<float>(d, cap, rows, n, (const double *)src, ld, layout, s);
-    if (dtype == KNN_F32 && src_dtype == KNN_F32) return launch_pack8<float>(d, cap, rows, n, (const float *)src, ld, layout, s);
+    if (dtype == KNN_F64 && src_dtype == KNN_F64) return launch_pack8<double>(d, cap, rows, n, (const double *)src, ld, layout, s, ap, row0);
+    if (dtype == KNN_F64 && src_dtype == KNN_F32) return launch_pack8<double>(d, cap, rows, n, (const float *)src, ld, layout, s, ap, row0);
+    if (dtype == KNN_F32 && src_dtype == KNN_F64) return launch_pack8<float>(d, cap, rows, n, (const double *)src, ld, layout, s, ap, row0);
+    if (dtype == KNN_F32 && src_dtype == KNN_F32) return launch_pack8<float>(d, cap, rows, n, (const float *)src, ld, layout, s, ap, row0);
     // (the bytes do not depend on the block's element type: every value is exact in both)
-    if (dtype == KNN_F64 && src_dtype == KNN_U8) return launch_pack8<double>(d, cap, rows, n, (const unsigned char *)src, ld, layout, s);
-    if (dtype == KNN_F32 && src_dtype == KNN_U8) return launch_pack8<float>(d, cap, rows, n, (const unsigned char *)src, ld, layout, s);
+    if (dtype == KNN_F64 && src_dtype == KNN_U8) return launch_pack8<double>(d, cap, rows, n, (const unsigned char *)src, ld, layout, s, ap, row0);
+    if (dtype == KNN_F32 && src_dtype == KNN_U8) return launch_pack8<float>(d, cap, rows, n, (const unsigned char *)src, ld, layout, s, ap, row0);
     return KNN_ERR_INVALID;
+}
+extern "C" int knn_launch_pack_s8(void *dst, int dtype, size_t cap, size_t rows, size_t n, const void *src,
+                                  int src_dtype, size_t ld, int layout, void *stream)
+{
+    return pack_s8_any(dst, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, false, 0);
+}
+extern "C" int knn_launch_append_s8(void *dst, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
+                                    const void *src, int src_dtype, size_t ld, int layout, void *stream)
+{
+    return pack_s8_any(dst, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, true, row0);
 }
 
 // Ring wire form of a packed block (knn_wire_pack / knn_wire_unpack): the
@@ -2619,23 +2708,33 @@ extern "C" int knn_launch_wire(int unpack, void *dst, const void *src, int dtype
     return hip_status();
 }
 
-extern "C" int knn_launch_pack(void *blk, int dtype, size_t cap, size_t rows, size_t n,
-                               const void *src, int src_dtype, size_t ld, int layout, void *stream)
+static int pack_any(void *blk, int dtype, size_t cap, size_t rows, size_t n, const void *src, int src_dtype,
+                    size_t ld, int layout, void *stream, bool ap, size_t row0)
 {
     hipStream_t s = (hipStream_t)stream;
     if (dtype == KNN_F64 && src_dtype == KNN_F64)
-        return launch_pack((double *)blk, cap, rows, n, (const double *)src, ld, layout, s);
+        return launch_pack((double *)blk, cap, rows, n, (const double *)src, ld, layout, s, ap, row0);
     if (dtype == KNN_F64 && src_dtype == KNN_F32)
-        return launch_pack((double *)blk, cap, rows, n, (const float *)src, ld, layout, s);
+        return launch_pack((double *)blk, cap, rows, n, (const float *)src, ld, layout, s, ap, row0);
     if (dtype == KNN_F32 && src_dtype == KNN_F64)
-        return launch_pack((float *)blk, cap, rows, n, (const double *)src, ld, layout, s);
+        return launch_pack((float *)blk, cap, rows, n, (const double *)src, ld, layout, s, ap, row0);
     if (dtype == KNN_F32 && src_dtype == KNN_F32)
-        return launch_pack((float *)blk, cap, rows, n, (const float *)src, ld, layout, s);
+        return launch_pack((float *)blk, cap, rows, n, (const float *)src, ld, layout, s, ap, row0);
     if (dtype == KNN_F64 && src_dtype == KNN_U8)
-        return launch_pack((double *)blk, cap, rows, n, (const unsigned char *)src, ld, layout, s);
+        return launch_pack((double *)blk, cap, rows, n, (const unsigned char *)src, ld, layout, s, ap, row0);
     if (dtype == KNN_F32 && src_dtype == KNN_U8)
-        return launch_pack((float *)blk, cap, rows, n, (const unsigned char *)src, ld, layout, s);
+        return launch_pack((float *)blk, cap, rows, n, (const unsigned char *)src, ld, layout, s, ap, row0);
     return KNN_ERR_INVALID;
+}
+extern "C" int knn_launch_pack(void *blk, int dtype, size_t cap, size_t rows, size_t n,
+                               const void *src, int src_dtype, size_t ld, int layout, void *stream)
+{
+    return pack_any(blk, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, false, 0);
+}
+extern "C" int knn_launch_append(void *blk, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
+                                 const void *src, int src_dtype, size_t ld, int layout, void *stream)
+{
+    return pack_any(blk, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, true, row0);
 }
 
 template <typename T, int KL, int KP>

@@ -52,6 +52,7 @@ API_SYMBOLS = (
     "knn_ctx_attach_qblock", "knn_ctx_research_blocks", "knn_ctx_step_n", "knn_ctx_profile_merge",
     "knn_ctx_set_solo", "knn_ctx_search_meta", "knn_query", "knn_classify_query", "knn_ctx_set_keep_zero",
     "knn_index_create", "knn_index_query", "knn_index_info", "knn_index_destroy",
+    "knn_index_add", "knn_block_append_dt", "knn_block_append_s8",
 )
 DTYPES = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 # a pack / index SOURCE may also be unsigned bytes (KNN_U8: never a block or search dtype)
@@ -148,6 +149,9 @@ def _load():
         "knn_index_query": ([p, p, sz, i, i, i, i, p], i),
         "knn_index_info": ([p, psz, psz, ctypes.POINTER(i), psz, ctypes.POINTER(i)], i),
         "knn_index_destroy": ([p], i),
+        "knn_index_add": ([p, p, sz, i, i, p, i], i),
+        "knn_block_append_dt": ([p, i, sz, sz, sz, sz, p, i, sz, i, p], i),
+        "knn_block_append_s8": ([p, i, sz, sz, sz, sz, p, i, sz, i, p], i),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -360,6 +364,13 @@ def block_pack(d_block, cap, rows, n, d_src, ld, layout, stream=0, dtype="f64", 
                                  ld, layout, stream or None), "knn_block_pack_dt")
 
 
+def block_append(d_block, cap, row0, rows, n, d_src, ld, layout, stream=0, dtype="f64", src_dtype="f64"):
+    """knn_block_append_dt: rows row0 .. row0+rows-1 of a block packed before,
+    from a rows x n device source (arguments as block_pack)."""
+    _check(lib.knn_block_append_dt(d_block, DTYPES[dtype], cap, row0, rows, n, d_src, SRC_DTYPES[src_dtype],
+                                   ld, layout, stream or None), "knn_block_append_dt")
+
+
 _live_contexts = weakref.WeakSet()
 
 
@@ -377,6 +388,12 @@ def block_pack_s8(d_sblock, cap, rows, n, d_src, ld, layout, stream=0, dtype="f6
     src_dtype "f64", "f32" or "u8"."""
     _check(lib.knn_block_pack_s8(d_sblock, DTYPES[dtype], cap, rows, n, d_src, SRC_DTYPES[src_dtype], ld, layout,
                                  stream or None), "knn_block_pack_s8")
+
+
+def block_append_s8(d_sblock, cap, row0, rows, n, d_src, ld, layout, stream=0, dtype="f64", src_dtype="f64"):
+    """knn_block_append_s8: the same rows of a byte block packed by block_pack_s8."""
+    _check(lib.knn_block_append_s8(d_sblock, DTYPES[dtype], cap, row0, rows, n, d_src, SRC_DTYPES[src_dtype], ld,
+                                   layout, stream or None), "knn_block_append_s8")
 
 
 def s8_spec_ok(meta_host, n, dtype="f64"):
@@ -498,6 +515,26 @@ class Index:
         _check(lib.knn_index_query(self._h, ptr, mq, lay, src, k, flags, optr), "knn_index_query")
         del keep
         return res, lib.knn_last_search_seconds()
+
+    def add(self, X, labels=None):
+        """knn_index_add: append the rows of X ((rows, n), in the index's
+        layout argument; types as the constructor's X, its own) without
+        repacking what is resident.  labels: one a row when the index was
+        made with labels, else None.  Returns the 1-based id of the first
+        added row; the index keeps nothing of X after the call returns."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        ptr, keep, rows, n, lay, src, dev = _index_source(X, self.layout, "X")
+        if n != self.n:
+            raise ValueError("X must be (rows, %d), got (%d, %d)" % (self.n, rows, n))
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.float64)
+        if lab is not None and lab.shape[0] != rows:
+            raise ValueError("labels must have %d entries, got %d" % (rows, lab.shape[0]))
+        _check(lib.knn_index_add(self._h, ptr, rows, lay, src, _ptr(lab), dev), "knn_index_add")
+        del keep
+        first = self.m + 1
+        self.m += rows
+        return first
 
     def info(self):
         """knn_index_info: IndexInfo(m, n, nblocks, device_bytes, last_bits)."""

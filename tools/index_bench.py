@@ -15,6 +15,15 @@ Legs (one a process, so two builds of the library can be run in alternation:
           HIP events, fraction of HBM over the algorithmic bytes (source read
           once + byte rows and two norm words written, as bench.py prices it)
 
+  add     Index.add of 1, 128 and 10000 rows to the 60000-row index, from uint8
+          and from float64 rows: host wall of the call from a host array, host
+          wall and device span (events around the call) from a device tensor,
+          then the span of the first query (mq = 128) after the add against
+          the same query on a fresh index of the grown size
+  rebuild what a user without add does: knn_index_create of the 60000 + rows
+          concatenated corpus (host wall), same sources and sizes; runs on a
+          build without add too
+
 Median of --runs after --warmup, with min and max.  Each leg appends one JSON
 line to --out; --merge FILES... folds such lines into profiles/index_bench.json.
 
@@ -108,8 +117,90 @@ def leg_pack(knn, a):
     return out
 
 
-def merge(files, out):
+ADD_ROWS = (1, 128, 10000)
+
+
+def leg_add(knn, a, X, Qall):
+    """every timed add goes to a fresh 60000-row index (an add's cost must not
+    depend on the adds before it); indices are created outside the timings"""
+    import numpy as np
+    import torch
+    dev = torch.device("cuda", 0)
+    Q = Qall[:128]
+    rows_out = []
+    extra, _ = synth_rows(knn, max(ADD_ROWS))
+    for src in ("u8", "f64"):
+        cast = (lambda A: A.astype(np.uint8)) if src == "u8" else (lambda A: A)
+        Xs, Qs = cast(X), cast(Q)
+        for rows in ADD_ROWS:
+            A = np.ascontiguousarray(cast(extra[:rows]))
+            dA = torch.from_numpy(A).to(dev)
+            wall_h, wall_d, span_d, q_after, q_fresh = [], [], [], [], []
+            for i in range(a.warmup + a.runs):
+                for device in (False, True):
+                    ix = knn.Index(Xs)
+                    ix.query(Qs, a.k)                       # the kept context exists, as in a server
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    e0.record()
+                    ix.add(dA if device else A)
+                    e1.record()
+                    w = (time.perf_counter() - t0) * 1e3
+                    e1.synchronize()
+                    _, s = ix.query(Qs, a.k)
+                    ix.close()
+                    if i >= a.warmup:
+                        if device:
+                            wall_d.append(w)
+                            span_d.append(e0.elapsed_time(e1))
+                        else:
+                            wall_h.append(w)
+                            q_after.append(s * 1e3)
+            fresh = knn.Index(np.vstack([Xs, A]))
+            for i in range(a.warmup + a.runs):
+                _, s = fresh.query(Qs, a.k)
+                if i >= a.warmup:
+                    q_fresh.append(s * 1e3)
+            fresh.close()
+            rows_out.append({"rows": rows, "source": src, "wall_host_src": stats(wall_h), "wall_device_src": stats(wall_d),
+                             "span_device_src": stats(span_d), "first_query_after_add": stats(q_after),
+                             "query_fresh_index": stats(q_fresh)})
+    return rows_out
+
+
+def synth_rows(knn, rows):
+    from mpiknn import synth
+    return synth.mnist_like(rows, seed=99)
+
+
+def leg_rebuild(knn, a, X):
+    import numpy as np
+    out = []
+    extra, _ = synth_rows(knn, max(ADD_ROWS))
+    for src in ("u8", "f64"):
+        if src == "u8" and not hasattr(knn, "U8"):
+            continue
+        for rows in ADD_ROWS:
+            C = np.vstack([X, extra[:rows]])
+            C = np.ascontiguousarray(C.astype(np.uint8) if src == "u8" else C)
+            t = []
+            for i in range(a.warmup + a.runs):
+                t0 = time.perf_counter()
+                ix = knn.Index(C)
+                w = (time.perf_counter() - t0) * 1e3
+                ix.close()
+                if i >= a.warmup:
+                    t.append(w)
+            out.append(dict(rows=rows, source=src, create_wall=stats(t)))
+    return out
+
+
+def merge(files, out, keep=False):
     legs = []
+    if keep and os.path.exists(out):
+        with open(out) as fh:
+            legs = json.load(fh).get("legs", [])
     for f in files:
         with open(f) as fh:
             legs += [json.loads(line) for line in fh if line.strip()]
@@ -124,7 +215,7 @@ def merge(files, out):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=["query", "index", "pack"])
+    ap.add_argument("--leg", choices=["query", "index", "pack", "add", "rebuild"])
     ap.add_argument("--root", default=ROOT, help="tree whose mpi-knn_amd/ is imported")
     ap.add_argument("--tag", default="this", help="name of the build in the output")
     ap.add_argument("--round", type=int, default=0)
@@ -135,9 +226,10 @@ def main():
     ap.add_argument("--mq", type=int, nargs="*", default=[1, 16, 128, 1024, 10000])
     ap.add_argument("--out", default=os.path.join(ROOT, "bench_out", "index_bench.jsonl"))
     ap.add_argument("--merge", nargs="+")
+    ap.add_argument("--keep", action="store_true", help="--merge: keep the legs profiles/index_bench.json holds")
     a = ap.parse_args()
     if a.merge:
-        merge(a.merge, os.path.join(ROOT, "profiles", "index_bench.json"))
+        merge(a.merge, os.path.join(ROOT, "profiles", "index_bench.json"), a.keep)
         return
     sys.path.insert(0, os.path.join(os.path.abspath(a.root), "mpi-knn_amd"))
     import mpiknn
@@ -151,6 +243,10 @@ def main():
         Qall, _ = synth.mnist_like(max(a.mq), seed=77)
         if a.leg == "query":
             rec["results"] = leg_query(mpiknn, a, X, Qall)
+        elif a.leg == "add":
+            rec["results"] = leg_add(mpiknn, a, X, Qall)
+        elif a.leg == "rebuild":
+            rec["results"] = leg_rebuild(mpiknn, a, X)
         else:
             rec.update(leg_index(mpiknn, a, X, Qall))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
