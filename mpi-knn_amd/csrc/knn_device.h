@@ -1,5 +1,6 @@
 // knn_device.h -- device helpers shared by the kernel translation units
-// (knn_kernels.hip: element / fp16 contraction; knn_i8.hip: int8 contraction).
+// (knn_pack.hip: the block writers; knn_kernels.hip: element / fp16
+// contraction; knn_i8.hip: int8 contraction).
 #ifndef KNN_DEVICE_H
 #define KNN_DEVICE_H
 #include <hip/hip_runtime.h>
@@ -9,9 +10,14 @@
 typedef double dbl4 __attribute__((ext_vector_type(4)));
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 typedef float flt4 __attribute__((ext_vector_type(4)));
+// 8 halves: one operand of v_mfma_f32_16x16x32_f16, 16 bytes of an fp16 shadow row
+typedef _Float16 knn_h8 __attribute__((ext_vector_type(8)));
 #define LDS_AS __attribute__((address_space(3)))
 
 static constexpr double KNN_INF = __builtin_inf();
+
+// what a launcher returns after its launches
+static inline int hip_status(void) { return hipGetLastError() == hipSuccess ? KNN_OK : KNN_ERR_HIP; }
 
 // LDS-DMA issue as inline asm (guide: glds16_asm).  Written through
 // __builtin_amdgcn_global_load_lds, the loads make hipcc's waitcnt pass treat
@@ -122,7 +128,7 @@ __device__ __forceinline__ void wave_argmin(double &d, int &i)
 
 // ---------------------------------------------------------------------------
 // Byte blocks (the int8 contraction, knn_i8.hip; written by k_shadow8 from an
-// element block or by k_pack8_* straight from the source, knn_kernels.hip)
+// element block or by k_pack8_* straight from the source, knn_pack.hip)
 // ---------------------------------------------------------------------------
 // Row r of a byte block -> its slot in the norm array.  Tile t = r >> 7 owns
 // 512 bytes; inside, [m-block b][lane half h][j][i] holds row 32b + 8j + 4h +

@@ -1,6 +1,7 @@
 /*
- * knn_internal.h -- launchers exported by knn_kernels.hip to the host C
- * engine (knn_engine.c).  Plain C ABI, device pointers, hipStream_t as void*.
+ * knn_internal.h -- launchers exported by the kernel units (knn_pack.hip,
+ * knn_kernels.hip, knn_i8.hip, knn_split.hip, knn_order.hip) to the host C
+ * engine (knn_engine.c, knn_index.c).  Plain C ABI, device pointers, hipStream_t as void*.
  */
 #ifndef KNN_INTERNAL_H
 #define KNN_INTERNAL_H
@@ -262,7 +263,7 @@ int knn_launch_rescan_end(int kp, const int *fail_list, int nfail, const double 
 int knn_launch_vote(knn_neighbour_t *nb, size_t m, int k, int nclasses, int rule,
                     const double *labels, size_t nlabels, size_t q_base, int *pred,
                     unsigned long long *matches, void *stream);
-/* knn_kernels.hip: block elements <-> int16 wire elements (cnt % 8 == 0) */
+/* knn_pack.hip: block elements <-> int16 wire elements (cnt % 8 == 0) */
 int knn_launch_wire(int unpack, void *dst, const void *src, int dtype, size_t cnt, void *stream);
 /* knn_engine.c: the value knn_last_search_seconds() returns (this thread) */
 void knn_set_last_search_seconds(double s);

@@ -4,9 +4,7 @@
 // knn-serial.c:72-93 (and its per-block copies mpi-knn-parallel_blocking.c:
 // 155-181, 217-242).  Re-designed for MI355X:
 //
-//   k_pack_col / k_pack_row   column/row-major fp64/fp32 -> padded
-//                row-major block + norms + meta in one pass (replaces
-//                blk:100-109's packing).
+//   (packing: knn_pack.hip writes the blocks these kernels read)
 //   k_dist_topk  fused fp64-MFMA contraction G = C.Q^T (v_mfma_f64_16x16x4)
 //                with d^2 = |q|^2 + |c|^2 - 2G and a per-lane register top-k
 //                (insertion network) behind a shared threshold.  One
@@ -61,7 +59,7 @@ template <typename T> static constexpr int knn_bk() { return 128 / (int)sizeof(T
 // Lane (row, g) converts its two 16-byte fp32 slots of a chunk (features
 // 4g..4g+3 of pieces 0 and 1) into one 8-half operand; the query side is
 // converted identically, so each chunk's 32 features are summed once.
-typedef _Float16 knn_h8 __attribute__((ext_vector_type(8)));
+// (knn_h8: knn_device.h)
 typedef _Float16 knn_h4 __attribute__((ext_vector_type(4)));
 // fp64 blocks (H16 with ES 8): integer data with max|x| <= 256.  A chunk is
 // 16 features; lane (row, g) converts its two 16-byte slots (features
@@ -170,418 +168,6 @@ __device__ __forceinline__ double knn_cert_E(int n, double qn, double maxnorm, i
     }
     if constexpr (sizeof(TE) == 8) return 8.0 * nn * u * qc;
     else return nn * qc * (u * (1.0 + 2.0 * nn * u) + 4.0 * 1.1102230246251565e-16);
-}
-
-// ---------------------------------------------------------------------------
-// Packing (blk:100-109): src (S = fp64, fp32 or unsigned char; col-major, ld >= rows |
-// row-major, ld >= n) -> padded row-major block of T, the squared norms
-// (fp64 accumulate, stored as T) and the meta (max|x|, max norm,
-// non-integer, non-finite, max(x)+, max(-x)+), in ONE pass over the source
-// (the norms are taken from the stored T values).  Per workgroup the meta
-// is reduced, then one atomicMax per word (non-negative doubles order like
-// their bits; the caller zeroes the meta).
-// ---------------------------------------------------------------------------
-// (SEL, the append kernels' form: the two flags as selects.  The branches
-// below end in a store through a selected address, which keeps the struct in
-// scratch, 24 bytes a lane; the pack kernels keep the code they always had.)
-template <bool SEL>
-struct knn_meta_acc_t {
-    double mabs = 0.0, nonint = 0.0, nonfin = 0.0, mpos = 0.0, mneg = 0.0;
-    __device__ __forceinline__ void add(double v, double &s)
-    {
-        s = fma(v, v, s);
-        if constexpr (SEL) {
-            const bool fin = __builtin_isfinite(v);
-            const double a = fabs(v);
-            nonfin = fin ? nonfin : 1.0;
-            mabs = fin && a > mabs ? a : mabs;
-            mpos = fin && v > mpos ? v : mpos;
-            mneg = fin && -v > mneg ? -v : mneg;
-            nonint = fin && v != rint(v) ? 1.0 : nonint;
-        } else if (!__builtin_isfinite(v)) nonfin = 1.0;
-        else {
-            const double a = fabs(v);
-            mabs = a > mabs ? a : mabs;
-            mpos = v > mpos ? v : mpos;
-            mneg = -v > mneg ? -v : mneg;
-            if (v != rint(v)) nonint = 1.0;
-        }
-    }
-};
-typedef knn_meta_acc_t<false> knn_meta_acc;
-
-// workgroup reduction of the 6 meta words (64 W threads) + atomicMax
-template <int W, typename A>
-__device__ __forceinline__ void knn_meta_flush_w(const A &a, double mnorm, double *meta)
-{
-    __shared__ double red[W][6];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double w[6] = {a.mabs, mnorm, a.nonint, a.nonfin, a.mpos, a.mneg};
-#pragma unroll
-    for (int q = 0; q < 6; q++)
-        for (int off = 32; off > 0; off >>= 1) w[q] = fmax(w[q], __shfl_xor(w[q], off));
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < 6; q++) red[wave][q] = w[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        double v = red[0][threadIdx.x];
-#pragma unroll
-        for (int x = 1; x < W; x++) v = fmax(v, red[x][threadIdx.x]);
-        if (!(v >= 0.0)) v = __builtin_inf();   // NaN norm -> treat as overflow
-        atomicMax((unsigned long long *)&meta[threadIdx.x], (unsigned long long)__double_as_longlong(v));
-    }
-}
-template <typename A>
-__device__ __forceinline__ void knn_meta_flush(const A &a, double mnorm, double *meta)
-{
-    knn_meta_flush_w<4>(a, mnorm, meta);
-}
-
-// Column-major source (the .mat layout): a workgroup owns 64 rows and walks
-// the columns in 64 x 64 tiles through LDS (reads: 64 consecutive rows of a
-// column, 512 B; writes: 64 consecutive features of a row).  Thread (ty,
-// tx) accumulates row tx's squared terms over columns = ty mod 4; the four
-// partials are summed at the end (a fixed order).
-//
-// APPEND (knn_block_append_dt / _s8, every pack kernel below): the source's
-// rows 0 .. rows-1 land at block rows row0 .. of a block packed before.  Only
-// those rows, their norms and the meta are written (the grid covers `rows`,
-// not rows_pad: padding rows are the first pack's), and the meta is
-// atomicMax'ed into the words already there.  A row is summed by the same
-// lanes in the same order wherever it lands, so pack + appends write the
-// bytes one pack of all the rows writes.
-template <typename T, typename S, bool APPEND>
-__global__ __launch_bounds__(256) void k_pack_col(T *__restrict__ blk, size_t rows, size_t rows_pad, int n,
-                                                  int n_pad, const S *__restrict__ src, size_t ld, size_t row0)
-{
-    __shared__ T tile[64][65];
-    __shared__ double part[4][64];
-    T *norms = blk + rows_pad * (size_t)n_pad;
-    double *meta = (double *)(norms + rows_pad);
-    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;   // rows written; the first one's block row
-    const size_t i0 = (size_t)blockIdx.x * 64;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const size_t i = i0 + tx;
-    knn_meta_acc_t<APPEND> ma;
-    double s = 0.0;
-    for (int j0 = 0; j0 < n_pad; j0 += 64) {
-#pragma unroll 4
-        for (int jj = ty; jj < 64; jj += 4) {
-            const int j = j0 + jj;
-            const T v = (i < rows && j < n) ? (T)src[i + (size_t)j * ld] : (T)0;
-            tile[jj][tx] = v;
-            ma.add((double)v, s);
-        }
-        __syncthreads();
-        const int j = j0 + tx;
-#pragma unroll 4
-        for (int ii = ty; ii < 64; ii += 4)
-            if (i0 + ii < lim && j < n_pad) blk[(d0 + i0 + ii) * n_pad + j] = tile[tx][ii];
-        __syncthreads();
-    }
-    part[ty][tx] = s;
-    __syncthreads();
-    double mnorm = 0.0;
-    if (ty == 0 && i < lim) {
-        const double nr = (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
-        norms[d0 + i] = (T)nr;
-        if (nr == nr) mnorm = nr;
-        else ma.nonfin = 1.0;
-    }
-    knn_meta_flush(ma, mnorm, meta);
-}
-
-// ---------------------------------------------------------------------------
-// Speculative byte block straight from the source (knn_block_pack_s8): the
-// int8 contraction's rows x' = x - 128 (rows of rs = round_up(n, 32) bytes,
-// zero past n and on padding rows), its norm words (i8_norm_word of the
-// exact int32 |x'|^2) and the block meta of the element pack above (the same
-// six words over the values as T).  The shift the int8 path uses is
-// o = 128 - max(-x)+ of the reduced meta (knn_i8.hip), so the image is the
-// one k_shadow8 would write exactly when every value is an integer in
-// [0, 255] -- knn_s8_spec_ok on the reduced meta (MNIST pixels, SIFT
-// descriptors); otherwise the caller packs the element block after all.  One
-// read of the source and 1 byte written an element, instead of the element
-// block (8 or 4 bytes written, read back by k_shadow8).
-// ---------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ int knn_spec8(T v)
-{
-    // x - 128 of an in-window integer; anything else gives garbage the meta
-    // rejects: NaN -> 0 and a clamp to [-32640, 32895], so the conversion is
-    // defined and (x - 128)^2 < 2^31 (the squares are summed as unsigned)
-    const T c = v == v ? (v < (T)-32640 ? (T)-32640 : (v > (T)32895 ? (T)32895 : v)) : (T)0;
-    return (int)c - 128;
-}
-
-// col-major source (the .mat layout): a workgroup owns RW rows and walks
-// the columns in 64-column tiles (RW = 64: each wave reads 64 consecutive
-// rows of one column, 512-byte runs; RW = 32: two columns of 32 rows a
-// wave), all of a thread's loads of a tile in flight before their
-// conversion; bytes go through LDS into 16-byte row stores.  Thread (ty, tx)
-// sums row tx's squares over columns = ty mod (256 / RW); the partials add
-// exactly for the integer data the byte block holds (the meta decides
-// that; rejected data is packed again from elements).
-// (Issuing the next tile's loads before converting this one -- 32 in
-// flight at RW = 64 -- measured slower: 106 -> 130 us for MNIST, rocprofv3.)
-template <typename T, typename S, int RW, bool APPEND>
-__global__ __launch_bounds__(256) void k_pack8_col(signed char *__restrict__ dst, size_t rows, size_t rows_pad,
-                                                   int n, int rs, const S *__restrict__ src, size_t ld, size_t row0)
-{
-    constexpr int CG = 256 / RW;      // column groups
-    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
-    constexpr int NE = 64 / CG;       // loads a thread a tile
-    __shared__ unsigned char tb[64][RW + 4];   // [column of the tile][row]
-    __shared__ double part[CG][RW];
-    __shared__ unsigned ipart[CG][RW];
-    int *norms = (int *)(dst + rows_pad * (size_t)rs);
-    double *meta = (double *)(norms + 2 * rows_pad);
-    const size_t i0 = (size_t)blockIdx.x * RW;
-    const int tx = threadIdx.x % RW, ty = threadIdx.x / RW;
-    const size_t i = i0 + tx;
-    const bool live = i < rows;
-    const S *xp = src + (live ? i : 0);
-    knn_meta_acc_t<APPEND> ma;
-    double s = 0.0;
-    unsigned si = 0u;
-    for (int j0 = 0; j0 < rs; j0 += 64) {
-        S v[NE];
-#pragma unroll
-        for (int e = 0; e < NE; e++) {
-            const int j = j0 + ty + CG * e;
-            v[e] = (live && j < n) ? __builtin_nontemporal_load(xp + (size_t)j * ld) : (S)0;
-        }
-#pragma unroll
-        for (int e = 0; e < NE; e++) {
-            const T x = (T)v[e];
-            ma.add((double)x, s);
-            const int xi = (live && j0 + ty + CG * e < n) ? knn_spec8(x) : 0;
-            si += (unsigned)(xi * xi);
-            tb[ty + CG * e][tx] = (unsigned char)xi;
-        }
-        __syncthreads();
-        // row r = t / 4: 16 bytes at column 16 (t % 4) of the tile
-        const int r = threadIdx.x >> 2, c0 = 16 * (threadIdx.x & 3);
-        if (r < RW && i0 + r < lim && j0 + c0 < rs) {
-            unsigned w4[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                w4[q] = (unsigned)tb[c0 + 4 * q][r] | ((unsigned)tb[c0 + 4 * q + 1][r] << 8) |
-                        ((unsigned)tb[c0 + 4 * q + 2][r] << 16) | ((unsigned)tb[c0 + 4 * q + 3][r] << 24);
-            *(knn_v4i *)(dst + (d0 + i0 + r) * (size_t)rs + j0 + c0) = (knn_v4i){(int)w4[0], (int)w4[1], (int)w4[2], (int)w4[3]};
-        }
-        __syncthreads();
-    }
-    part[ty][tx] = s;
-    ipart[ty][tx] = si;
-    __syncthreads();
-    double mnorm = 0.0;
-    if (ty == 0 && i < lim) {
-        double nr = 0.0;
-        unsigned ni = 0u;
-        if constexpr (CG == 4) {
-            nr = (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
-            ni = (ipart[0][tx] + ipart[1][tx]) + (ipart[2][tx] + ipart[3][tx]);
-        } else {
-#pragma unroll
-            for (int q = 0; q < CG; q++) {
-                nr += part[q][tx];
-                ni += ipart[q][tx];
-            }
-        }
-        norms[i8_norm_pos((int)(d0 + i))] = i8_norm_word((int)(d0 + i), (int)ni, rs);
-        norms[rows_pad + i8_norm_pos((int)(d0 + i))] = i8_init_word((int)ni, rs);
-        if (nr == nr) mnorm = nr;
-        else ma.nonfin = 1.0;
-    }
-    knn_meta_flush(ma, mnorm, meta);
-    if (!APPEND && blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;   // (an append finds it set)
-}
-
-// row-major source: one wave per row, lane l converts the 8-element groups
-// l, l + 64, ... (one 8-byte store each); VEC: 16-byte-aligned rows, whole
-// groups read as 16-byte vectors (sift: 0.68 ms for 512 MB with scalar loads)
-template <typename T, typename S, bool VEC, bool APPEND>
-__global__ __launch_bounds__(256) void k_pack8_row(signed char *__restrict__ dst, size_t rows, size_t rows_pad,
-                                                   int n, int rs, const S *__restrict__ src, size_t ld, size_t row0)
-{
-    typedef typename std::conditional<sizeof(S) == 8, dbl2, flt4>::type svec_t;
-    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
-    constexpr int SV = 16 / (int)sizeof(S);
-    int *norms = (int *)(dst + rows_pad * (size_t)rs);
-    double *meta = (double *)(norms + 2 * rows_pad);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int ng = rs / 8;
-    knn_meta_acc_t<APPEND> ma;
-    double mnorm = 0.0;
-    for (size_t r = (size_t)blockIdx.x * 4 + wave; r < lim; r += (size_t)gridDim.x * 4) {
-        double s = 0.0;
-        unsigned si = 0u;
-        const S *x = src + r * ld;
-        for (int g = lane; g < ng; g += 64) {
-            unsigned lo = 0u, hi = 0u;
-            S sv[8];
-            if (VEC && r < rows && 8 * g + 8 <= n) {
-#pragma unroll
-                for (int q = 0; q < 8 / SV; q++) {
-                    const svec_t w = *(const svec_t *)(x + 8 * g + SV * q);
-#pragma unroll
-                    for (int e = 0; e < SV; e++) sv[SV * q + e] = w[e];
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; e++) sv[e] = (r < rows && 8 * g + e < n) ? x[8 * g + e] : (S)0;
-            }
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const int j = 8 * g + e;
-                const bool in = r < rows && j < n;
-                const T v = in ? (T)sv[e] : (T)0;
-                ma.add((double)v, s);
-                const int xi = in ? knn_spec8(v) : 0;
-                si += (unsigned)(xi * xi);
-                if (e < 4) lo |= ((unsigned)xi & 0xffu) << (8 * e);
-                else hi |= ((unsigned)xi & 0xffu) << (8 * (e - 4));
-            }
-            typedef unsigned u2 __attribute__((ext_vector_type(2)));
-            *(u2 *)(dst + (d0 + r) * (size_t)rs + 8 * g) = (u2){lo, hi};
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            s += __shfl_xor(s, off);
-            si += (unsigned)__shfl_xor((int)si, off);
-        }
-        if (lane == 0) {
-            norms[i8_norm_pos((int)(d0 + r))] = i8_norm_word((int)(d0 + r), (int)si, rs);
-            norms[rows_pad + i8_norm_pos((int)(d0 + r))] = i8_init_word((int)si, rs);
-        }
-        if (s == s) mnorm = s > mnorm ? s : mnorm;
-        else ma.nonfin = 1.0;
-    }
-    knn_meta_flush(ma, mnorm, meta);
-    if (!APPEND && blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
-}
-
-// row-major KNN_U8 source: the byte image is x ^ 0x80 (x - 128 as int8), so a
-// lane moves one 16-byte group of a row, read as one vector and written as
-// one (2 bytes of traffic an element).  LPR lanes (a power of two >= rs / 16,
-// at most 64) share a row and a wave carries 64 / LPR rows at once: SIFT's
-// 128-byte rows 8 to a wave, MNIST's 800-byte rows one (four such row groups
-// in flight).  Everything is
-// integer arithmetic: sum (x - 128)^2 for the norm words, sum x^2 (< 2^26 at
-// n <= 896) and max x for the meta -- the words the fp64 source gives for the
-// same values, whatever the order of summation (exact integers below 2^53).
-// VEC: the source and ld are multiples of 16 bytes, so every whole group
-// inside n is read as a 16-byte vector; otherwise, in a row's tail group and
-// past n (ld > n), byte by byte.
-typedef unsigned knn_v4u __attribute__((ext_vector_type(4)));
-// APPEND: row groups are cut at `rows`, which a group may straddle: the rows
-// past it are neither stored nor given norm words.
-template <bool VEC, bool APPEND>
-__global__ __launch_bounds__(256) void k_pack8_row_u8(signed char *__restrict__ dst, size_t rows, size_t rows_pad,
-                                                      int n, int rs, const unsigned char *__restrict__ src,
-                                                      size_t ld, int lpr, size_t row0)
-{
-    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
-    int *norms = (int *)(dst + rows_pad * (size_t)rs);
-    double *meta = (double *)(norms + 2 * rows_pad);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int rpw = 64 / lpr;               // rows a wave
-    const int sub = lane / lpr, g = lane % lpr;
-    const bool has = 16 * g < rs;           // this lane's group lies inside the row
-    unsigned mx = 0u, mnorm = 0u;
-    // U row groups a wave in flight: their vector loads issue before the first
-    // conversion (one load a lane a row left the wave waiting on each row in
-    // turn).  rows_pad is a multiple of 128 and rpw divides 64, so a row group
-    // lies below rows_pad as a whole or not at all (wave-uniform).
-    constexpr int U = 4;
-    for (size_t rb = ((size_t)blockIdx.x * 4 + wave) * U * rpw; rb < lim;
-         rb += (size_t)gridDim.x * 4 * U * rpw) {
-        knn_v4u v[U];
-        bool full[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const size_t r = rb + (size_t)u * rpw + sub;
-            full[u] = VEC && has && r < rows && 16 * g + 16 <= n;
-            v[u] = (knn_v4u){0u, 0u, 0u, 0u};
-            if (full[u]) v[u] = *(const knn_v4u *)(src + r * ld + 16 * g);
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            if (rb + (size_t)u * rpw >= lim) break;
-            const size_t r = rb + (size_t)u * rpw + sub;
-            const bool wr = !APPEND || r < rows;
-            // bytes, and 0xff where a byte is data
-            unsigned w[4] = {v[u][0], v[u][1], v[u][2], v[u][3]};
-            const unsigned fm = full[u] ? 0xffffffffu : 0u;
-            unsigned live[4] = {fm, fm, fm, fm};
-            if (!full[u] && has && r < rows) {
-                const unsigned char *x = src + r * ld + 16 * g;
-#pragma unroll
-                for (int e = 0; e < 16; e++)
-                    if (16 * g + e < n) {
-                        w[e >> 2] |= (unsigned)x[e] << (8 * (e & 3));
-                        live[e >> 2] |= 0xffu << (8 * (e & 3));
-                    }
-            }
-            unsigned sx = 0u, si = 0u;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const unsigned b = (w[q] >> (8 * e)) & 0xffu;
-                    const int xi = ((live[q] >> (8 * e)) & 1u) ? (int)b - 128 : 0;
-                    sx += b * b;
-                    si += (unsigned)(xi * xi);
-                    mx = b > mx ? b : mx;
-                }
-                w[q] = (w[q] ^ 0x80808080u) & live[q];
-            }
-            if (has && wr) *(knn_v4u *)(dst + (d0 + r) * (size_t)rs + 16 * g) = (knn_v4u){w[0], w[1], w[2], w[3]};
-            for (int off = lpr >> 1; off > 0; off >>= 1) {
-                sx += (unsigned)__shfl_xor((int)sx, off);
-                si += (unsigned)__shfl_xor((int)si, off);
-            }
-            if (g == 0 && wr) {
-                norms[i8_norm_pos((int)(d0 + r))] = i8_norm_word((int)(d0 + r), (int)si, rs);
-                norms[rows_pad + i8_norm_pos((int)(d0 + r))] = i8_init_word((int)si, rs);
-            }
-            mnorm = sx > mnorm ? sx : mnorm;
-        }
-    }
-    knn_meta_acc_t<APPEND> ma;
-    ma.mabs = ma.mpos = (double)mx;
-    knn_meta_flush(ma, (double)mnorm, meta);
-    if (!APPEND && blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
-}
-
-// Row-major source: one wave per row (lane-strided features, butterfly sum).
-template <typename T, typename S, bool APPEND>
-__global__ __launch_bounds__(256) void k_pack_row(T *__restrict__ blk, size_t rows, size_t rows_pad, int n,
-                                                  int n_pad, const S *__restrict__ src, size_t ld, size_t row0)
-{
-    T *norms = blk + rows_pad * (size_t)n_pad;
-    double *meta = (double *)(norms + rows_pad);
-    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    knn_meta_acc_t<APPEND> ma;
-    double mnorm = 0.0;
-    for (size_t i = (size_t)blockIdx.x * 4 + wave; i < lim; i += (size_t)gridDim.x * 4) {
-        double s = 0.0;
-        const S *x = src + i * ld;
-        T *o = blk + (d0 + i) * (size_t)n_pad;
-        for (int j = lane; j < n_pad; j += 64) {
-            const T v = (i < rows && j < n) ? (T)x[j] : (T)0;
-            o[j] = v;
-            ma.add((double)v, s);
-        }
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) norms[d0 + i] = (T)s;
-        if (s == s) mnorm = s > mnorm ? s : mnorm;
-        else ma.nonfin = 1.0;
-    }
-    knn_meta_flush(ma, mnorm, meta);
 }
 
 // ---------------------------------------------------------------------------
@@ -2393,350 +1979,6 @@ __global__ void k_rescan_end(const int *__restrict__ fail_list, int nfail, int K
 // ---------------------------------------------------------------------------
 // C launchers
 // ---------------------------------------------------------------------------
-static int hip_status(void) { return hipGetLastError() == hipSuccess ? KNN_OK : KNN_ERR_HIP; }
-
-// append: rows row0 .. of a block packed before (knn_block_append_dt / _s8) --
-// no meta memset (the meta is max(old, new rows)), grids over `rows`
-template <typename T, typename S>
-static int launch_pack(T *blk, size_t cap, size_t rows, size_t n, const S *src, size_t ld,
-                       int layout, hipStream_t s, bool append = false, size_t row0 = 0)
-{
-    constexpr int dt = sizeof(T) == 8 ? KNN_F64 : KNN_F32;
-    const size_t rp = knn_rows_pad(cap), np = knn_n_pad_dt(n, dt);
-    if (append) {
-        if (layout == KNN_COLMAJOR) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_col<T, S, true>), dim3((unsigned)((rows + 63) / 64)), dim3(256), 0,
-                               s, blk, rows, rp, (int)n, (int)np, src, ld, row0);
-        } else {
-            const unsigned nb = (unsigned)((rows + 3) / 4 < 8192 ? (rows + 3) / 4 : 8192);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_row<T, S, true>), dim3(nb), dim3(256), 0, s, blk, rows, rp, (int)n,
-                               (int)np, src, ld, row0);
-        }
-        return hip_status();
-    }
-    double *meta = (double *)(blk + rp * np + rp);
-    if (hipMemsetAsync(meta, 0, KNN_META_DOUBLES * sizeof(double), s) != hipSuccess)
-        return KNN_ERR_HIP;
-    if (layout == KNN_COLMAJOR) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_col<T, S, false>), dim3((unsigned)((rp + 63) / 64)), dim3(256), 0, s,
-                           blk, rows, rp, (int)n, (int)np, src, ld, (size_t)0);
-    } else {
-        const unsigned nb = (unsigned)((rp + 3) / 4 < 8192 ? (rp + 3) / 4 : 8192);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_row<T, S, false>), dim3(nb), dim3(256), 0, s, blk, rows, rp,
-                           (int)n, (int)np, src, ld, (size_t)0);
-    }
-    return hip_status();
-}
-
-// the byte forms of an append: the same kernels' APPEND instantiations, grids over `rows`
-template <typename T, typename S>
-static int launch_append8(signed char *dst, size_t rp, size_t rs, size_t rows, size_t n, const S *src, size_t ld,
-                          int layout, hipStream_t s, size_t row0)
-{
-    if (layout == KNN_COLMAJOR) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_col<T, S, 64, true>), dim3((unsigned)((rows + 63) / 64)), dim3(256), 0,
-                           s, dst, rows, rp, (int)n, (int)rs, src, ld, row0);
-    } else if constexpr (sizeof(S) == 1) {
-        int lpr = 1;
-        while (lpr < 64 && 16 * (size_t)lpr < rs) lpr *= 2;
-        if (16 * (size_t)lpr < rs) return KNN_ERR_INVALID;
-        const size_t nw = (rows * lpr + 255) / 256;
-        const unsigned nb = (unsigned)((nw + 3) / 4 < 2048 ? (nw + 3) / 4 : 2048);
-        // (a source that starts at row0 * n of a larger array is rarely 16-byte aligned)
-        const bool vec = ((uintptr_t)src % 16 == 0) && ld % 16 == 0;
-        if (vec)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row_u8<true, true>), dim3(nb), dim3(256), 0, s, dst, rows, rp, (int)n, (int)rs, src,
-                               ld, lpr, row0);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row_u8<false, true>), dim3(nb), dim3(256), 0, s, dst, rows, rp, (int)n, (int)rs, src,
-                               ld, lpr, row0);
-    } else {
-        const unsigned nb = (unsigned)((rows + 3) / 4 < 8192 ? (rows + 3) / 4 : 8192);
-        const bool vec = ((uintptr_t)src % 16 == 0) && (ld * sizeof(S)) % 16 == 0;
-        if (vec)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, true, true>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
-                               (int)n, (int)rs, src, ld, row0);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, false, true>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
-                               (int)n, (int)rs, src, ld, row0);
-    }
-    return hip_status();
-}
-
-template <typename T, typename S>
-static int launch_pack8(signed char *dst, size_t cap, size_t rows, size_t n, const S *src, size_t ld, int layout,
-                        hipStream_t s, bool append = false, size_t row0 = 0)
-{
-    const size_t rp = knn_rows_pad(cap), rs = knn_s8_rs(n);
-    if (append) return launch_append8<T, S>(dst, rp, rs, rows, n, src, ld, layout, s, row0);
-    double *meta = (double *)(dst + knn_s8_meta_offset(cap, n));
-    if (hipMemsetAsync(meta, 0, KNN_META_DOUBLES * sizeof(double), s) != hipSuccess) return KNN_ERR_HIP;
-    if (layout == KNN_COLMAJOR) {
-        // (32-row workgroups, twice as many: 107.5 against 105.7 us for MNIST)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_col<T, S, 64, false>), dim3((unsigned)((rp + 63) / 64)), dim3(256), 0,
-                           s, dst, rows, rp, (int)n, (int)rs, src, ld, (size_t)0);
-    } else if constexpr (sizeof(S) == 1) {
-        // KNN_U8: lpr lanes a row (a power of two >= rs / 16), 64 / lpr rows a wave
-        int lpr = 1;
-        while (lpr < 64 && 16 * (size_t)lpr < rs) lpr *= 2;
-        if (16 * (size_t)lpr < rs) return KNN_ERR_INVALID;   // (rs <= 1024: n <= KNN_I8_MAX_N)
-        // waves for one pass at 4 row groups a wave; 2048 workgroups (8 a CU) at most:
-        // every workgroup ends in six atomics on the same meta words
-        const size_t nw = (rp * lpr + 255) / 256;
-        const unsigned nb = (unsigned)((nw + 3) / 4 < 2048 ? (nw + 3) / 4 : 2048);
-        const bool vec = ((uintptr_t)src % 16 == 0) && ld % 16 == 0;
-        if (vec)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row_u8<true, false>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
-                               (int)n, (int)rs, src, ld, lpr, (size_t)0);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row_u8<false, false>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
-                               (int)n, (int)rs, src, ld, lpr, (size_t)0);
-    } else {
-        const unsigned nb = (unsigned)((rp + 3) / 4 < 8192 ? (rp + 3) / 4 : 8192);
-        const bool vec = ((uintptr_t)src % 16 == 0) && (ld * sizeof(S)) % 16 == 0;
-        if (vec)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, true, false>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
-                               (int)n, (int)rs, src, ld, (size_t)0);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, false, false>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
-                               (int)n, (int)rs, src, ld, (size_t)0);
-    }
-    return hip_status();
-}
-
-static int pack_s8_any(void *dst, int dtype, size_t cap, size_t rows, size_t n, const void *src, int src_dtype,
-                       size_t ld, int layout, void *stream, bool ap, size_t row0)
-{
-    hipStream_t s = (hipStream_t)stream;
-    signed char *d = (signed char *)dst;
-    if (dtype == KNN_F64 && src_dtype == KNN_F64) return launch_pack8<double>(d, cap, rows, n, (const double *)src, ld, layout, s, ap, row0);
-    if (dtype == KNN_F64 && src_dtype == KNN_F32) return launch_pack8<double>(d, cap, rows, n, (const float *)src, ld, layout, s, ap, row0);
-    if (dtype == KNN_F32 && src_dtype == KNN_F64) return launch_pack8<float>(d, cap, rows, n, (const double *)src, ld, layout, s, ap, row0);
-    if (dtype == KNN_F32 && src_dtype == KNN_F32) return launch_pack8<float>(d, cap, rows, n, (const float *)src, ld, layout, s, ap, row0);
-    // (the bytes do not depend on the block's element type: every value is exact in both)
-    if (dtype == KNN_F64 && src_dtype == KNN_U8) return launch_pack8<double>(d, cap, rows, n, (const unsigned char *)src, ld, layout, s, ap, row0);
-    if (dtype == KNN_F32 && src_dtype == KNN_U8) return launch_pack8<float>(d, cap, rows, n, (const unsigned char *)src, ld, layout, s, ap, row0);
-    return KNN_ERR_INVALID;
-}
-extern "C" int knn_launch_pack_s8(void *dst, int dtype, size_t cap, size_t rows, size_t n, const void *src,
-                                  int src_dtype, size_t ld, int layout, void *stream)
-{
-    return pack_s8_any(dst, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, false, 0);
-}
-extern "C" int knn_launch_append_s8(void *dst, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
-                                    const void *src, int src_dtype, size_t ld, int layout, void *stream)
-{
-    return pack_s8_any(dst, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, true, row0);
-}
-
-// Ring wire form of a packed block (knn_wire_pack / knn_wire_unpack): the
-// element array as int16 (exact for integer data with max|x| <= 32767),
-// 8 elements a thread; norms and meta travel verbatim (hipMemcpyAsync).
-typedef short knn_s8v __attribute__((ext_vector_type(8)));
-template <typename T>
-__global__ __launch_bounds__(256) void k_wire_pack(knn_s8v *__restrict__ w, const T *__restrict__ b,
-                                                   size_t n8)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
-        knn_s8v v;
-#pragma unroll
-        for (int e = 0; e < 8; e++) v[e] = (short)b[8 * i + e];
-        w[i] = v;
-    }
-}
-template <typename T>
-__global__ __launch_bounds__(256) void k_wire_unpack(T *__restrict__ b, const knn_s8v *__restrict__ w,
-                                                     size_t n8)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
-        const knn_s8v v = w[i];
-#pragma unroll
-        for (int e = 0; e < 8; e++) b[8 * i + e] = (T)v[e];
-    }
-}
-
-// fp16 shadow rows of a packed block for the H16 == 2 contraction: rows
-// of round_up(n, 64) halves (zero padded), converted with v_cvt_pkrtz
-// (exact: shadows are only made for integer data with max|x| <= 2048).
-template <typename T>
-__global__ __launch_bounds__(256) void k_shadow(knn_h8 *__restrict__ dst, const T *__restrict__ src,
-                                                size_t rows, int n, int nps, int npd)
-{
-    const size_t per = (size_t)npd / 8, tot = rows * per;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < tot; i += (size_t)gridDim.x * 256) {
-        const size_t r = i / per;
-        const int c = (int)(i - r * per) * 8;
-        const T *row = src + r * (size_t)nps;
-        unsigned w[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const int j = c + 2 * e;
-            const float x0 = j < n ? (float)row[j] : 0.f;
-            const float x1 = j + 1 < n ? (float)row[j + 1] : 0.f;
-            w[e] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(x0, x1));
-        }
-        typedef unsigned u4 __attribute__((ext_vector_type(4)));
-        dst[i] = __builtin_bit_cast(knn_h8, (u4){w[0], w[1], w[2], w[3]});
-    }
-}
-
-extern "C" int knn_launch_shadow(void *dst, const void *blk, int dtype, size_t rows_pad, size_t n,
-                                 void *stream)
-{
-    const int npd = (int)knn_round_up(n, 64), nps = (int)knn_n_pad_dt(n, dtype);
-    const size_t tot = rows_pad * (size_t)npd / 8;
-    const unsigned grid = (unsigned)(tot / 256 + 1 < 8192 ? tot / 256 + 1 : 8192);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == KNN_F64)
-        hipLaunchKernelGGL(k_shadow<double>, dim3(grid), dim3(256), 0, s, (knn_h8 *)dst,
-                           (const double *)blk, rows_pad, (int)n, nps, npd);
-    else if (dtype == KNN_F32)
-        hipLaunchKernelGGL(k_shadow<float>, dim3(grid), dim3(256), 0, s, (knn_h8 *)dst,
-                           (const float *)blk, rows_pad, (int)n, nps, npd);
-    else
-        return KNN_ERR_INVALID;
-    return hip_status();
-}
-
-// Split fp16 shadow rows (the split filter) of fp32 / fp64 blocks: per row
-// and 32-feature group, the 32 halves hi = RN16(S x) then the 32 halves lo =
-// RN16(S x - hi), each rounded once from the block's precision (S x - hi is
-// exact there: Sterbenz); zero past n.  One thread per 16 bytes
-// of source row (V = 2 fp64 / 4 fp32 features): a wave reads 1 KiB of a row
-// contiguously and its 16-lane groups write whole 64-byte hi and lo runs.
-// (Round 4's form, one thread per 8 features with 8-byte loads 64 bytes
-// apart, moved a 7552 x 784 fp64 block in 35 us, 2 TB/s.)  Up to
-// KNN_SPLIT_MAXBLK blocks per launch (a ring rank's received blocks).
-struct knn_split_conv_t {
-    char *dst[KNN_SPLIT_MAXBLK];
-    const void *src[KNN_SPLIT_MAXBLK];
-    long long i0[KNN_SPLIT_MAXBLK + 1];   // first flat work item of block b
-    int nblk;
-};
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_shadow_split(const knn_split_conv_t cv, int n, int nps, int npd, float S)
-{
-    constexpr int V = 16 / (int)sizeof(T);
-    typedef typename std::conditional<sizeof(T) == 8, dbl2, flt4>::type vec_t;
-    typedef _Float16 hv_t __attribute__((ext_vector_type(V)));
-    const int per = npd / V;   // work items a row
-    const long long tot = cv.i0[cv.nblk];
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < tot; i += (long long)gridDim.x * 256) {
-        int b = 0;
-#pragma unroll
-        for (int x = 1; x < KNN_SPLIT_MAXBLK; x++) b = (x < cv.nblk && i >= cv.i0[x]) ? x : b;
-        const long long li = i - cv.i0[b];
-        const long long r = li / per;
-        const int j0 = (int)(li - r * per) * V;
-        vec_t v{};
-        if (j0 < n) v = *(const vec_t *)((const T *)cv.src[b] + r * (long long)nps + j0);
-        hv_t hi, lo;
-#pragma unroll
-        for (int e = 0; e < V; e++) {
-            // one rounding each, from the block's precision (x - hi is exact
-            // in it: Sterbenz).  (Written as conversions through fp32, the
-            // compiler folds them into these single roundings anyway.)
-            const T x = (j0 + e < n) ? v[e] * (T)S : (T)0;
-            const _Float16 h = (_Float16)x;
-            hi[e] = h;
-            lo[e] = (_Float16)(x - (T)h);
-        }
-        char *o = cv.dst[b] + r * (long long)npd * 4 + (long long)(j0 >> 5) * 128 + 2 * (j0 & 31);
-        *(hv_t *)o = hi;
-        *(hv_t *)(o + 64) = lo;
-    }
-}
-
-// nblk blocks: dst[b] <- split rows of src[b] (rows_pad[b] rows each)
-extern "C" int knn_launch_shadow_split_n(int nblk, void *const *dst, const void *const *src, const size_t *rows_pad,
-                                         int dtype, size_t n, float S, void *stream)
-{
-    if (nblk < 1 || nblk > KNN_SPLIT_MAXBLK || n == 0) return KNN_ERR_INVALID;
-    const int npd = (int)knn_round_up(n, 32), nps = (int)knn_n_pad_dt(n, dtype);
-    const int V = dtype == KNN_F64 ? 2 : 4;
-    knn_split_conv_t cv{};
-    cv.nblk = nblk;
-    cv.i0[0] = 0;
-    for (int b = 0; b < nblk; b++) {
-        if (!dst[b] || !src[b]) return KNN_ERR_INVALID;
-        cv.dst[b] = (char *)dst[b];
-        cv.src[b] = src[b];
-        cv.i0[b + 1] = cv.i0[b] + (long long)rows_pad[b] * (npd / V);
-    }
-    for (int b = nblk + 1; b <= KNN_SPLIT_MAXBLK; b++) cv.i0[b] = cv.i0[nblk];
-    const long long tot = cv.i0[nblk];
-    const unsigned grid = (unsigned)(tot / 256 + 1 < 16384 ? tot / 256 + 1 : 16384);
-    if (dtype == KNN_F32)
-        hipLaunchKernelGGL(k_shadow_split<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, cv, (int)n, nps,
-                           npd, S);
-    else if (dtype == KNN_F64)
-        hipLaunchKernelGGL(k_shadow_split<double>, dim3(grid), dim3(256), 0, (hipStream_t)stream, cv, (int)n, nps,
-                           npd, S);
-    else
-        return KNN_ERR_INVALID;
-    return hip_status();
-}
-
-extern "C" int knn_launch_shadow_split(void *dst, const void *blk, int dtype, size_t rows_pad, size_t n,
-                                       float S, void *stream)
-{
-    return knn_launch_shadow_split_n(1, &dst, &blk, &rows_pad, dtype, n, S, stream);
-}
-
-extern "C" int knn_launch_wire(int unpack, void *dst, const void *src, int dtype, size_t cnt,
-                               void *stream)
-{
-    if (cnt % 8) return KNN_ERR_INVALID;
-    const size_t n8 = cnt / 8;
-    const unsigned grid = (unsigned)(n8 / 256 + 1 < 4096 ? n8 / 256 + 1 : 4096);
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == KNN_F64 && !unpack)
-        hipLaunchKernelGGL(k_wire_pack<double>, dim3(grid), dim3(256), 0, s, (knn_s8v *)dst,
-                           (const double *)src, n8);
-    else if (dtype == KNN_F64)
-        hipLaunchKernelGGL(k_wire_unpack<double>, dim3(grid), dim3(256), 0, s, (double *)dst,
-                           (const knn_s8v *)src, n8);
-    else if (dtype == KNN_F32 && !unpack)
-        hipLaunchKernelGGL(k_wire_pack<float>, dim3(grid), dim3(256), 0, s, (knn_s8v *)dst,
-                           (const float *)src, n8);
-    else if (dtype == KNN_F32)
-        hipLaunchKernelGGL(k_wire_unpack<float>, dim3(grid), dim3(256), 0, s, (float *)dst,
-                           (const knn_s8v *)src, n8);
-    else
-        return KNN_ERR_INVALID;
-    return hip_status();
-}
-
-static int pack_any(void *blk, int dtype, size_t cap, size_t rows, size_t n, const void *src, int src_dtype,
-                    size_t ld, int layout, void *stream, bool ap, size_t row0)
-{
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == KNN_F64 && src_dtype == KNN_F64)
-        return launch_pack((double *)blk, cap, rows, n, (const double *)src, ld, layout, s, ap, row0);
-    if (dtype == KNN_F64 && src_dtype == KNN_F32)
-        return launch_pack((double *)blk, cap, rows, n, (const float *)src, ld, layout, s, ap, row0);
-    if (dtype == KNN_F32 && src_dtype == KNN_F64)
-        return launch_pack((float *)blk, cap, rows, n, (const double *)src, ld, layout, s, ap, row0);
-    if (dtype == KNN_F32 && src_dtype == KNN_F32)
-        return launch_pack((float *)blk, cap, rows, n, (const float *)src, ld, layout, s, ap, row0);
-    if (dtype == KNN_F64 && src_dtype == KNN_U8)
-        return launch_pack((double *)blk, cap, rows, n, (const unsigned char *)src, ld, layout, s, ap, row0);
-    if (dtype == KNN_F32 && src_dtype == KNN_U8)
-        return launch_pack((float *)blk, cap, rows, n, (const unsigned char *)src, ld, layout, s, ap, row0);
-    return KNN_ERR_INVALID;
-}
-extern "C" int knn_launch_pack(void *blk, int dtype, size_t cap, size_t rows, size_t n,
-                               const void *src, int src_dtype, size_t ld, int layout, void *stream)
-{
-    return pack_any(blk, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, false, 0);
-}
-extern "C" int knn_launch_append(void *blk, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
-                                 const void *src, int src_dtype, size_t ld, int layout, void *stream)
-{
-    return pack_any(blk, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, true, row0);
-}
-
 template <typename T, int KL, int KP>
 static int launch_dist_topk(const T *qblk, size_t q_rows_pad, size_t q_base, int nq, const T *cblk,
                             size_t c_rows_pad, size_t c_base, int nc, int n, const double *meta,
@@ -2785,6 +2027,14 @@ static int launch_dist_topk(const T *qblk, size_t q_rows_pad, size_t q_base, int
         return knn_launch_dist_split(dt, KL, qsh, qnorm, q_base, nq, &cb, n, meta, nsplit, part_d, part_i, part_T,
                                      nq_pad, qthr, uj, xarg, m2s, s);
     }
+    // k_dist_topk<.., STG, H16> over the rows q / c (their row length `len`)
+    auto launch = [&](auto stg, auto h16, const T *q, const T *c, int len) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dist_topk<T, KL, KP, decltype(stg)::value, decltype(h16)::value>), grid,
+                           dim3(512), 0, s, q, qnorm, q_base, nq, c, cnorm, c_base, nc, n, len, ntiles, nsplit,
+                           nqb, meta, part_d, part_i, part_T, nq_pad, (unsigned long long *)qthr, uj, xarg);
+        return hip_status();
+    };
+    using std::integral_constant;
     if ((flags & KNN_DIST_SHADOW) && (flags & KNN_DIST_H16)) {
         if (!qsh || !csh) return KNN_ERR_INVALID;
         const int nps = (int)knn_round_up((size_t)n, 64);   // shadow row length (halves)
@@ -2792,31 +2042,12 @@ static int launch_dist_topk(const T *qblk, size_t q_rows_pad, size_t q_base, int
         // 1; partial lists byte-identical)
         // Every wave stages its own rows (STG 0) for fp64 blocks (mnist 10.0
         // vs 10.1 ms); fp32 (sift) 607 vs 691 ms with waves 0..3 staging.
-        if constexpr (sizeof(T) == 8)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dist_topk<T, KL, KP, 0, 2>), grid, dim3(512), 0, s,
-                               (const T *)qsh, qnorm, q_base, nq, (const T *)csh, cnorm, c_base, nc, n,
-                               nps, ntiles, nsplit, nqb, meta, part_d, part_i, part_T, nq_pad,
-                               (unsigned long long *)qthr, uj, xarg);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dist_topk<T, KL, KP, 1, 2>), grid, dim3(512), 0, s,
-                               (const T *)qsh, qnorm, q_base, nq, (const T *)csh, cnorm, c_base, nc, n,
-                               nps, ntiles, nsplit, nqb, meta, part_d, part_i, part_T, nq_pad,
-                               (unsigned long long *)qthr, uj, xarg);
-        return hip_status();
+        return launch(integral_constant<int, sizeof(T) == 8 ? 0 : 1>(), integral_constant<int, 2>(),
+                      (const T *)qsh, (const T *)csh, nps);
     }
-    {
-        if (flags & KNN_DIST_H16) {   // host-checked: INT mode and max|x| <= 2048 (fp64: 256)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dist_topk<T, KL, KP, 0, 1>), grid, dim3(512), 0, s,
-                               qblk, qnorm, q_base, nq, cblk, cnorm, c_base, nc, n, np, ntiles, nsplit,
-                               nqb, meta, part_d, part_i, part_T, nq_pad, (unsigned long long *)qthr,
-                               uj, xarg);
-            return hip_status();
-        }
-    }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dist_topk<T, KL, KP>), grid, dim3(512), 0, s, qblk, qnorm,
-                       q_base, nq, cblk, cnorm, c_base, nc, n, np, ntiles, nsplit, nqb, meta, part_d,
-                       part_i, part_T, nq_pad, (unsigned long long *)qthr, uj, xarg);
-    return hip_status();
+    if (flags & KNN_DIST_H16)   // host-checked: INT mode and max|x| <= 2048 (fp64: 256)
+        return launch(integral_constant<int, 0>(), integral_constant<int, 1>(), qblk, cblk, np);
+    return launch(integral_constant<int, 0>(), integral_constant<int, 0>(), qblk, cblk, np);
 }
 
 // The served (element type, state capacity) pairs: fp64 k <= 16, 32 (16-deep
@@ -2897,28 +2128,24 @@ extern "C" int knn_launch_merge_n(int dtype, int kp, int k, const double *part_d
     const int two = lpq * nsplit + (pf ? 4 : 1) <= 32;
     const dim3 grid((unsigned)((nq + (two ? 7 : 3)) / (two ? 8 : 4)));
     hipStream_t s = (hipStream_t)stream;
-#define CALL(T, KL, KP)                                                                          \
-    if (pf && KP == 32 && two)                                                                   \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge<T, 32, 32, 8>), grid, dim3(256), 0, s, part_d,  \
-                           part_i, part_T, nsplit, lpq, kl, nq, nq_pad, first_step, st_d, st_x,    \
-                           st_i, st_T, (const T *)qblk, qn_off, mb, n,                             \
-                           np, meta, k, (unsigned long long *)qthr, filt, qperm);                         \
-    else if (pf && KP == 32)                                                                     \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge<T, 32, 64, 8>), grid, dim3(256), 0, s, part_d,  \
-                           part_i, part_T, nsplit, lpq, kl, nq, nq_pad, first_step, st_d, st_x,    \
-                           st_i, st_T, (const T *)qblk, qn_off, mb, n,                             \
-                           np, meta, k, (unsigned long long *)qthr, filt, qperm);                         \
-    else if (two)                                                                                \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge<T, KP, 32>), grid, dim3(256), 0, s, part_d,     \
-                           part_i, part_T, nsplit, lpq, kl, nq, nq_pad, first_step, st_d, st_x,    \
-                           st_i, st_T, (const T *)qblk, qn_off, mb, n,                             \
-                           np, meta, k, (unsigned long long *)qthr, filt, qperm);                         \
-    else                                                                                         \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge<T, KP, 64>), grid, dim3(256), 0, s, part_d,     \
-                           part_i, part_T, nsplit, lpq, kl, nq, nq_pad, first_step, st_d, st_x,    \
-                           st_i, st_T, (const T *)qblk, qn_off, mb, n,                             \
-                           np, meta, k, (unsigned long long *)qthr, filt, qperm);                         \
-    return hip_status()
+    // k_merge<element, KP, S lanes a query, PF>: pf is the 32-entry state's own
+    // form (kp == 32), two packs a query into 32 lanes
+    auto launch = [&](auto te, auto kpc, auto sc, auto pfc) {
+        typedef decltype(te) T;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_merge<T, decltype(kpc)::value, decltype(sc)::value, decltype(pfc)::value>),
+                           grid, dim3(256), 0, s, part_d, part_i, part_T, nsplit, lpq, kl, nq, nq_pad, first_step,
+                           st_d, st_x, st_i, st_T, (const T *)qblk, qn_off, mb, n, np, meta, k,
+                           (unsigned long long *)qthr, filt, qperm);
+        return hip_status();
+    };
+    using std::integral_constant;
+    const integral_constant<int, 32> c32;
+    const integral_constant<int, 64> c64;
+#define CALL(T, KL, KP)                                                                    \
+    if (pf && two) return launch(T(), c32, c32, integral_constant<int, 8>());              \
+    if (pf) return launch(T(), c32, c64, integral_constant<int, 8>());                     \
+    if (two) return launch(T(), integral_constant<int, KP>(), c32, integral_constant<int, 0>()); \
+    return launch(T(), integral_constant<int, KP>(), c64, integral_constant<int, 0>())
     KNN_DISPATCH(dtype, kp, CALL);
 #undef CALL
 }

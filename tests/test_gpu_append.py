@@ -4,7 +4,9 @@ a block packed over its first 70 rows and appended to at (70, 59), (129, 1) and
 offsets, one of a single row -- is byte for byte (rows, norms or norm words,
 meta, padding) the block one pack of all 300 rows writes.  cap = 300 (384
 padded rows); n = 20 (a padded short row; the row-major u8 pieces start
-unaligned), 128 (SIFT's short rows with init words), 784 (MNIST's long rows).
+unaligned), 31 (no row-major source has 16-byte-aligned rows: the scalar-load
+forms of every row kernel, fp32 and fp64 sources included), 128 (SIFT's short
+rows with init words), 784 (MNIST's long rows).
 Both buffers start zero-filled and are compared whole."""
 import numpy as np
 import pytest
@@ -59,16 +61,38 @@ def one_shot_and_pieces(torch, knn, V, form, layout, dtype, src, pieces=PIECES, 
     return a.cpu().numpy(), b.cpu().numpy()
 
 
-@pytest.mark.parametrize("n", [20, 128, 784])
+def check_byte_block(knn, V, a, what):
+    """a byte block against numpy alone: the image x ^ 0x80 in rows [:ROWS, :n]
+    and zero elsewhere, and the meta words of V"""
+    n = V.shape[1]
+    rs = (n + 31) // 32 * 32
+    img = a[:384 * rs].reshape(-1, rs)
+    assert np.array_equal(img[:ROWS, :n], V.astype(np.uint8) ^ 0x80), what
+    assert not img[:, n:].any() and not img[ROWS:].any(), what
+    moff = knn.s8_block_meta_offset(CAP, n)
+    meta = a[moff:moff + 64].view(np.float64)
+    assert meta[0] == np.abs(V).max() and meta[2] == 0.0 and meta[3] == 0.0, what
+    assert meta[4] == V.max() and meta[5] == 0.0, what
+    assert meta[1] == (V * V).sum(1).max(), what
+
+
+@pytest.mark.parametrize("n", [20, 31, 128, 784])
 @pytest.mark.parametrize("form", ["elem", "s8"])
 def test_append_equals_pack(knn, form, n):
     import torch
     V = values(n)
+    first = None
     for layout in ("row", "col"):
         for dtype in ("f64", "f32"):
             for src in ("f64", "f32", "u8"):
                 a, b = one_shot_and_pieces(torch, knn, V, form, layout, dtype, src)
                 assert np.array_equal(a, b), (form, layout, dtype, src)
+                if form == "s8" and n == 31:
+                    # the unaligned width: every combination against numpy, and
+                    # one byte block whatever the layout, block type and source
+                    check_byte_block(knn, V, a, (layout, dtype, src))
+                    first = a if first is None else first
+                    assert np.array_equal(a, first), (layout, dtype, src)
     # the comparison sees the appended rows: they are in the one-shot block
     if form == "s8":
         rs = (n + 31) // 32 * 32

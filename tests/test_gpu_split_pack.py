@@ -4,7 +4,7 @@ restatement below, for fp64 and fp32 blocks, ragged n (a partial last
 32-feature group), values over many binades including ones whose lo half
 is subnormal or zero, and several scales.
 
-Restatement (the filter's representation, knn_kernels.hip k_shadow_split):
+Restatement (the filter's representation, knn_pack.hip k_shadow_split):
 x = scale * v in the block's precision (scale a power of two: exact), hi =
 RN16(x), lo = RN16(x - hi), each rounded once from that precision (numpy's
 float64 -> float16 conversion rounds once; x - hi is exact); per row and 32-feature group the 32

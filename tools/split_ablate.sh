@@ -25,12 +25,12 @@ REV=$(git rev-parse HEAD)
 SCR=$(mktemp -d /tmp/split_ablate.XXXXXX)
 trap 'rm -rf "$SCR"' EXIT
 git archive HEAD mpi-knn_amd/csrc mpi-knn_amd/Makefile include | tar -x -C "$SCR"
-make -s -j8 -C "$SCR/mpi-knn_amd" build/knn_kernels.o build/knn_i8.o build/knn_engine.o build/knn_ring.o \
+make -s -j8 -C "$SCR/mpi-knn_amd" build/knn_kernels.o build/knn_pack.o build/knn_i8.o build/knn_engine.o build/knn_ring.o \
   build/knn_matio.o build/knn_vote.o build/knn_compat.o build/knn_order.o
 ROCM=/opt/rocm
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -I$SCR/include -I$SCR/mpi-knn_amd/csrc -I$ROCM/include"
 B="$SCR/mpi-knn_amd/build"
-OTHERS="$B/knn_kernels.o $B/knn_i8.o $B/knn_engine.o $B/knn_ring.o $B/knn_matio.o $B/knn_vote.o $B/knn_compat.o $B/knn_order.o"
+OTHERS="$B/knn_kernels.o $B/knn_pack.o $B/knn_i8.o $B/knn_engine.o $B/knn_ring.o $B/knn_matio.o $B/knn_vote.o $B/knn_compat.o $B/knn_order.o"
 rm -rf "$HERE/abl5"
 mkdir -p "$HERE/abl5/obj"
 for v in "noepi:-DSP_ABL_NOEPI=1" "noepi_nodma:-DSP_ABL_NOEPI=1 -DSP_ABL_NODMA=1" \
