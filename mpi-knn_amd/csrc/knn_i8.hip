@@ -104,7 +104,9 @@ __global__ __launch_bounds__(256) void k_shadow8(signed char *__restrict__ dst, 
 // Epilogue per tile: key = |c'|^2 - 2 q'.c' (int32) and the lane minimum
 // against min(own KL-th, shared bound) - |q'|^2; survivors, lowest row first
 // (the stable tie order), go through a select tree into a per-lane LDS
-// buffer of NB entries (d^2 = key + |q'|^2).  When some lane's buffer is
+// buffer of NB entries (d^2 = key + |q'|^2).  After the first survivor of
+// each lane the medians of the max tree tell whether any lane holds a second
+// one (i8_second32); only then do further rounds run.  When some lane's buffer is
 // full the wave merges all buffers into the KL-entry register lists (one
 // entry a round through the insertion network) and refreshes the bounds, so
 // the network runs on dense rounds instead of once per survivor of the
@@ -510,10 +512,21 @@ __global__ __launch_bounds__(64 * W, WPS) void k_dist_topk_i8(
     };
     // buffered survivors -> lists, in buffer (= row) order, one entry a
     // round; the rounds are dense: a merge runs when some lane's buffer is
-    // full, so most lanes insert a real entry every round
+    // full, so most lanes insert a real entry every round.  NB rounds, a
+    // counted loop: a tile's merge runs with a full buffer (the rounds a
+    // ballot of e < cnt gave), the launch's last one may run a few rounds
+    // that insert nothing.  Under the ballot the lists came out of the loop
+    // in other registers than they went in: 24 copies a round, and 24 where
+    // a tile's paths with and without a merge meet.
+    // (ONELOOP: 17-entry lists at 28 K-steps have no register to spare --
+    // in this form they spilled a query fragment, with a vmcnt(0) reload
+    // every tile; that instantiation keeps the ballot and the one
+    // extraction loop)
+    constexpr bool ONELOOP = KL == KNN_I8_KL && NKS == 28;
     auto merge = [&](int g) {
         const LDS_AS int *bk = bk0 + g * NB * 64, *bi = bi0 + g * NB * 64;
-        for (int e = 0; __ballot(e < cnt[g]) != 0ull; e++) {
+#pragma nounroll
+        for (int e = 0; ONELOOP ? __ballot(e < cnt[g]) != 0ull : e < NB; e++) {
             int d = I8_INF, id = -1;
             if (e < cnt[g]) {
                 d = bk[64 * e];
@@ -677,24 +690,61 @@ __global__ __launch_bounds__(64 * W, WPS) void k_dist_topk_i8(
                 for (int x = 0; x < 32; x++) v[x] = a[x] == A_NONE ? vnone[g] : v[x];
             }
             int T = thr_v(g);
-            int vm = i8_max32(v);
+            int tn[15];
+            int vm = ONELOOP ? i8_max32(v) : i8_max32n(v, tn);
             if (__ballot(vm >= T) == 0ull) continue;
             // survivors in (d^2, row) order, one a round per lane: into the
             // lane's LDS buffer (NB entries); a full buffer anywhere merges
             // the wave's buffers into the lists (dense insertion rounds)
-            do {
+            auto put = [&]() {
                 if (vm >= T) {
                     const int slot = 31 - (vm & 31);
                     bk[64 * cnt[g]] = qn[g] - (vm >> 5);   // d^2 (0 = a duplicate: dropped at the merge)
                     bi[64 * cnt[g]] = idb + 32 * (2 * pr + (slot >> 4)) + 8 * ((slot >> 2) & 3) + (slot & 3);
                     cnt[g]++;
                 }
-                if (__ballot(cnt[g] == NB) != 0ull) {
+            };
+            // The first round stands alone: on most tiles no lane holds a
+            // second key >= T, which the medians of the tree just built tell
+            // (i8_second32, exact, against T after the round's merge if one
+            // ran) at a third of a blind i8_next.  The merges sit outside
+            // the extraction rounds, so that the lists are not carried through
+            // them: inside, the compiler kept L / I in a second register set
+            // and copied all of them in and out every tile.
+            if constexpr (ONELOOP) {
+                do {
+                    put();
+                    if (__ballot(cnt[g] == NB) != 0ull) {
+                        merge(g);
+                        T = thr_v(g);
+                    }
+                    vm = i8_next(v, vm, vnone[g]);
+                } while (__ballot(vm >= T) != 0ull);
+                continue;
+            }
+            put();
+            if (__ballot(cnt[g] == NB) != 0ull) {
+                merge(g);
+                T = thr_v(g);
+            }
+            bool more = __ballot(i8_second32(v, tn) >= T) != 0ull;
+            while (more) {
+                // rounds until no lane has a key >= T left (more = false) or
+                // a buffer is full: then merge and resume from vm under the new T
+                bool full;
+                do {
+                    full = false;
+                    vm = i8_next(v, vm, vnone[g]);
+                    more = __ballot(vm >= T) != 0ull;
+                    if (!more) break;
+                    put();
+                    full = __ballot(cnt[g] == NB) != 0ull;
+                } while (!full);
+                if (full) {
                     merge(g);
                     T = thr_v(g);
                 }
-                vm = i8_next(v, vm, vnone[g]);
-            } while (__ballot(vm >= T) != 0ull);
+            }
         }
         }
     };

@@ -17,6 +17,12 @@ __device__ __forceinline__ int i8_max3(int a, int b, int c)
     asm("v_max3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+__device__ __forceinline__ int i8_med3(int a, int b, int c)
+{
+    int r;
+    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
 __device__ __forceinline__ unsigned i8_min3u(unsigned a, unsigned b, unsigned c)
 {
     unsigned r;
@@ -33,6 +39,41 @@ __device__ __forceinline__ int i8_max32(const int *v)
     const int a = i8_max3(m[0], m[1], m[2]), b = i8_max3(m[3], m[4], m[5]);
     const int c = i8_max3(m[6], m[7], m[8]), d = i8_max3(m[9], m[10], a);
     return i8_max3(b, c, d);
+}
+// the same tree with its nodes kept for i8_second32: n[0..10] the first-level
+// maxima, n[11..14] the second level's
+__device__ __forceinline__ int i8_max32n(const int *v, int (&n)[15])
+{
+#pragma unroll
+    for (int y = 0; y < 10; y++) n[y] = i8_max3(v[3 * y], v[3 * y + 1], v[3 * y + 2]);
+    n[10] = v[30] > v[31] ? v[30] : v[31];
+    n[11] = i8_max3(n[0], n[1], n[2]);
+    n[12] = i8_max3(n[3], n[4], n[5]);
+    n[13] = i8_max3(n[6], n[7], n[8]);
+    n[14] = i8_max3(n[9], n[10], n[11]);
+    return i8_max3(n[12], n[13], n[14]);
+}
+// the second largest of the 32 values (as a multiset) from the tree of
+// i8_max32n: at the node where the largest meets the second largest the
+// median of the node's inputs is the second largest, and no node's median
+// exceeds it (some other input of the node is at least as large) -- so it is
+// the maximum of the 16 nodes' medians: 15 v_med3, a v_min, 8 v_max
+__device__ __forceinline__ int i8_second32(const int *v, const int (&n)[15])
+{
+    int s[16];
+#pragma unroll
+    for (int y = 0; y < 10; y++) s[y] = i8_med3(v[3 * y], v[3 * y + 1], v[3 * y + 2]);
+    s[10] = v[30] < v[31] ? v[30] : v[31];
+    s[11] = i8_med3(n[0], n[1], n[2]);
+    s[12] = i8_med3(n[3], n[4], n[5]);
+    s[13] = i8_med3(n[6], n[7], n[8]);
+    s[14] = i8_med3(n[9], n[10], n[11]);
+    s[15] = i8_med3(n[12], n[13], n[14]);
+    int t[5];
+#pragma unroll
+    for (int y = 0; y < 5; y++) t[y] = i8_max3(s[3 * y], s[3 * y + 1], s[3 * y + 2]);
+    const int a = i8_max3(t[0], t[1], t[2]), b = i8_max3(t[3], t[4], s[15]);
+    return a > b ? a : b;
 }
 // the largest of the 32 values below vm, or `none` if there is none: the
 // unsigned minimum of vm - 1 - v.  Values below vm map to [0, span) and the
@@ -59,12 +100,6 @@ __device__ __forceinline__ int i8_next(const int *v, int vm, int none)
 // lane's candidates arrive in row order, so ties keep the lower index,
 // SURVEY F1); d >= L[KL-1] is a no-op.  Keys: L'[e] = med3(L[e-1], L[e], d)
 // (one v_med3_i32, since L[e-1] <= L[e]); ids move where d < L[e-1].
-__device__ __forceinline__ int i8_med3(int a, int b, int c)
-{
-    int r;
-    asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
 template <int KL>
 __device__ __forceinline__ void i8_insert(int (&L)[KL], int (&I)[KL], int d, int id)
 {
