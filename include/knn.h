@@ -249,7 +249,8 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * knn_index_add: rows that arrive later (blk:100-109's pack, without
  * repacking what is resident).  X is rows x n in `layout`, of src_dtype, its
  * own (KNN_INDEX_DEVICE_SRC: a device pointer); the rows take the 1-based ids
- * m+1 .. m+rows, m grows, and later queries take their ids from the new m.
+ * last_id+1 .. last_id+rows (knn_index_last_id: m while nothing was removed),
+ * m grows, and later queries take their ids from the new m.
  * The source is uploaded in its own type and packed into the last block's free
  * rows (knn_block_append_dt), then into new blocks of the index's capacity;
  * the touched blocks' meta is MAX-reduced into the corpus meta; an index with
@@ -270,8 +271,40 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * The caller may free or overwrite X when the call returns.  If the call
  * fails after its argument checks, the index answers queries as before it.
  * KNN_ERR_INVALID: NULL index or X, rows == 0, a bad layout, unknown flag bits,
- * m + rows > INT32_MAX, labels where the index has none or none where it has;
- * KNN_ERR_UNSUPPORTED: an unknown src_dtype -- before any device call.
+ * last_id + rows > INT32_MAX, labels where the index has none or none where it
+ * has; KNN_ERR_UNSUPPORTED: an unknown src_dtype -- before any device call.
+ *
+ * knn_index_remove: forget rows, by id.  A row keeps for its whole life the
+ * 1-based id it got at creation or at its add; ids are never reused
+ * (knn_index_last_id: the highest id handed out so far), and results keep
+ * reporting them.  ids: `count` ids on the host, each in [1, last_id], in any
+ * order; ids that are no longer live and repeats inside the list are skipped,
+ * *removed (nullable) gets the number of rows actually removed, and a call that
+ * removes nothing returns KNN_OK.  flags must be 0.  The survivors keep their
+ * order (a stable compaction on the device), so their positions in the blocks
+ * stay monotone in their ids and equal distances still come lower id first.
+ * Blocks in front of the first removed row are not touched; every block from
+ * there on is built again in a fresh buffer by knn_block_gather_dt (and
+ * knn_block_gather_s8 where the index has byte blocks), its meta the max of
+ * the blocks it drew from; old and new buffers of those blocks are resident
+ * together until the call's one wait.  When only the last rows go, nothing is
+ * moved.  The capacity stays (so do the kept context and tile buffers); blocks
+ * past the new count are freed; a later add fills the last block's free rows.
+ * The corpus meta is left as it is: it is a MAX-reduction, so a value that
+ * has only become too large is conservative -- it can cost a faster path or a
+ * rescan, never exactness.  In particular byte blocks that an add dropped do
+ * not come back through a removal.  From the first removal on the index keeps
+ * the live ids, ascending, on the host and on the device (counted in
+ * knn_index_info's device_bytes), and knn_index_query ends its span with one
+ * small kernel that turns each record's position into its id (host and
+ * KNN_INDEX_DEVICE_OUT calls alike; empty slots stay {INFINITY, 0, 0}); an
+ * index that never removed holds no such map and launches what it always
+ * launched.  Labels stay indexed by id (a knn_classify_device caller's
+ * d_labels by id stays valid); knn_index_info's m is the number of live rows.
+ * If the call fails after its argument checks, the index answers as before it.
+ * KNN_ERR_INVALID, before any device call and with nothing changed: NULL index
+ * or ids, count == 0, flags != 0, an id outside [1, last_id], a call that
+ * would leave no live row.
  *
  * KNN_ERR_INVALID: NULL index, X, Q or out, zero m, mq or n, k <= 0, a bad
  * layout, unknown flag bits, m + mq > INT32_MAX; KNN_ERR_UNSUPPORTED: an
@@ -290,6 +323,9 @@ KNN_API int knn_index_query(knn_index_t *index, const void *Q, size_t mq, int la
                             int k, int flags, knn_neighbour_t *out);
 KNN_API int knn_index_add(knn_index_t *index, const void *X, size_t rows, int layout, int src_dtype,
                           const double *labels, int flags);
+KNN_API int knn_index_remove(knn_index_t *index, const int32_t *ids, size_t count, int flags,
+                             size_t *removed /* nullable */);
+KNN_API int knn_index_last_id(const knn_index_t *index, size_t *last_id);
 KNN_API int knn_index_info(const knn_index_t *index, size_t *m, size_t *n, int *nblocks,
                            size_t *device_bytes, int *last_bits);
 KNN_API int knn_index_destroy(knn_index_t *index);
@@ -419,6 +455,17 @@ KNN_API int knn_block_pack_dt(void *d_block, int dtype, size_t cap, size_t rows,
  * knn_block_pack_dt. */
 KNN_API int knn_block_append_dt(void *d_block, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
                                 const void *d_src, int src_dtype, size_t ld, int layout, void *stream);
+/* Rows from another block: block row row0 + i of d_dst becomes row d_list[i]
+ * of d_src, i < rows.  Both are packed blocks of the given capacities with the
+ * same n and dtype; d_list is a device array of local source rows, each below
+ * src_cap, in any order and with repeats (a gather, not only a compaction).
+ * The n_pad elements and the norm of each row are copied bit for bit; nothing
+ * else of d_dst is touched -- not its other rows, not its padding, not its
+ * meta, which stays the caller's business.  Launches are sized by `rows`.
+ * KNN_ERR_INVALID, before any device call: a NULL pointer, rows == 0, row0 +
+ * rows > dst_cap, d_dst == d_src, a capacity above INT32_MAX, an unknown dtype. */
+KNN_API int knn_block_gather_dt(void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
+                                const int32_t *d_list, size_t rows, size_t n, int dtype, void *stream);
 
 typedef struct knn_ctx knn_ctx_t;
 
@@ -467,6 +514,12 @@ KNN_API int knn_block_pack_s8(void *d_sblock, int dtype, size_t cap, size_t rows
  * byte-for-byte contract against one knn_block_pack_s8 of all the rows. */
 KNN_API int knn_block_append_s8(void *d_sblock, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
                                 const void *d_src, int src_dtype, size_t ld, int layout, void *stream);
+/* knn_block_gather_dt for byte blocks: the row bytes are copied verbatim, and
+ * both norm words are made again for the new row (they depend on the row's
+ * position) from the norm the source's words hold.  KNN_ERR_INVALID also for
+ * n > 896, the byte path's limit. */
+KNN_API int knn_block_gather_s8(void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
+                                const int32_t *d_list, size_t rows, size_t n, void *stream);
 KNN_API int knn_s8_spec_ok(const double *h_meta, size_t n, int dtype);
 /* begin from the query block's speculative byte block (h_meta: the reduced
  * meta, host; KNN_ERR_INVALID unless knn_s8_spec_ok).  The element block is

@@ -16,8 +16,13 @@
  * until the last tile is done: a timed span holds no copy to the host.
  * knn_index_add repeats build_pack / build_finish for rows that arrive later,
  * with the packs at a row offset (knn_block_append_dt / _s8, defined here).
+ * knn_index_remove compacts the blocks from the first removed row on with the
+ * block gathers (knn_block_gather_dt / _s8, defined here; its host planning:
+ * knn_remove_plan.h) and from then on keeps the live rows' ids, which a small
+ * kernel writes into every batch's records.
  */
 #include "knn_internal.h"
+#include "knn_remove_plan.h"
 
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
@@ -45,7 +50,13 @@ struct knn_index {
     double cmeta[KNN_META_DOUBLES];   /* host copy of the corpus's reduced meta */
     double *chm;                      /* the blocks' meta as read back (8 doubles a block) */
     double *labels;
-    size_t lab_cap;                   /* doubles allocated at labels (>= m) */
+    size_t lab_cap;                   /* doubles allocated at labels (>= last_id: labels are indexed by id) */
+    /* ids: row p (0-based position in the blocks) has the 1-based id ids[p],
+     * ascending.  NULL until the first removal: the id is then p + 1 and
+     * last_id == m.  d_ids: its device copy (both of ids_cap entries). */
+    size_t last_id;
+    int32_t *ids, *d_ids;
+    size_t ids_cap;
     /* kept between queries: the context (for k, tile_cap query rows), ntile
      * tile buffers of capacity tile_cap (byte forms allocated on first use),
      * the records of a host-out call, the reduced meta, the span's events */
@@ -104,6 +115,8 @@ static void index_free(knn_index_t *ix)
     }
     hipFree(ix->d_out);
     hipFree(ix->d_meta);
+    hipFree(ix->d_ids);
+    free(ix->ids);
     if (ix->red) hipHostFree(ix->red);
     if (ix->e0) hipEventDestroy(ix->e0);
     if (ix->e1) hipEventDestroy(ix->e1);
@@ -124,7 +137,7 @@ static int index_alloc(knn_index_t **out, size_t m, size_t n, int dtype)
     knn_index_t *ix = (knn_index_t *)calloc(1, sizeof(*ix));
     if (!ix) return KNN_ERR_NOMEM;
     ix->dtype = dtype;
-    ix->m = m;
+    ix->m = ix->last_id = m;
     ix->n = n;
     const size_t fit = fit_rows(n, dtype);
     ix->cap = env_rows("KNN_QUERY_BLOCK", m < fit ? m : fit, m);
@@ -447,6 +460,8 @@ int knn_index_query(knn_index_t *ix, const void *Q, size_t mq, int layout, int s
         rc = run_pack(ix, src, mq, layout, src_dtype);
         if (!rc) rc = stream_wait();
         if (!rc) rc = run_finish(ix, src, mq, layout, src_dtype, flags, d_out);
+        /* rows were removed: positions -> the ids the caller knows */
+        if (!rc && ix->ids) rc = knn_launch_remap_idx(d_out, cnt, ix->d_ids, ix->m, NULL);
         if (!rc) rc = span_end(ix);
         if (!rc && !dev_out && hipMemcpy(out, d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
             rc = KNN_ERR_HIP;
@@ -486,6 +501,54 @@ int knn_block_append_s8(void *d_sblock, int dtype, size_t cap, size_t row0, size
     return knn_launch_append_s8(d_sblock, dtype, cap, row0, rows, n, d_src, src_dtype, ld, layout, stream);
 }
 
+/* Block row row0 + i of d_dst <- row d_list[i] of d_src (include/knn.h).
+ * Beside the appends for the same reason. */
+static int gather_args_ok(const void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
+                          const int32_t *d_list, size_t rows, size_t n)
+{
+    return d_dst && d_src && d_list && d_dst != d_src && rows != 0 && n != 0 && dst_cap <= 0x7fffffffULL &&
+           src_cap <= 0x7fffffffULL && src_cap != 0 && row0 <= dst_cap && rows <= dst_cap - row0;
+}
+
+int knn_block_gather_dt(void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
+                        const int32_t *d_list, size_t rows, size_t n, int dtype, void *stream)
+{
+    if (!gather_args_ok(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n) || !dtype_ok(dtype) ||
+        n > 0x7fffffffULL / 8)
+        return KNN_ERR_INVALID;
+    return knn_launch_gather(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, dtype, stream);
+}
+
+int knn_block_gather_s8(void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
+                        const int32_t *d_list, size_t rows, size_t n, void *stream)
+{
+    if (!gather_args_ok(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n) || n > KNN_I8_MAX_N)
+        return KNN_ERR_INVALID;
+    return knn_launch_gather_rows8(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, stream);
+}
+
+/* the id map (host and device) for at least `need` entries, its m entries kept */
+static int index_ids_reserve(knn_index_t *ix, size_t need)
+{
+    if (need <= ix->ids_cap) return KNN_OK;
+    const size_t nc = 2 * ix->ids_cap > need ? 2 * ix->ids_cap : need;
+    int32_t *d = NULL;
+    if (hipMalloc((void **)&d, nc * sizeof(int32_t)) != hipSuccess) return KNN_ERR_NOMEM;
+    int32_t *h = (int32_t *)realloc(ix->ids, nc * sizeof(int32_t));
+    if (!h) {
+        hipFree(d);
+        return KNN_ERR_NOMEM;
+    }
+    ix->ids = h;   /* (the same entries, whatever follows) */
+    if (hipMemcpy(d, h, ix->m * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(d);
+        return KNN_ERR_HIP;
+    }
+    hipFree(ix->d_ids);
+    ix->d_ids = d;
+    ix->ids_cap = nc;
+    return KNN_OK;
+}
 
 /* the per-block arrays for at least nb blocks, their nblk entries kept */
 static int index_grow_arrays(knn_index_t *ix, size_t nb)
@@ -652,7 +715,7 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
     if (!knn_src_esize(src_dtype)) return KNN_ERR_UNSUPPORTED;
     if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
     if (flags & ~KNN_INDEX_DEVICE_SRC) return KNN_ERR_INVALID;
-    if (rows > 0x7fffffffULL || ix->m + rows > 0x7fffffffULL) return KNN_ERR_INVALID;
+    if (rows > 0x7fffffffULL || ix->last_id + rows > 0x7fffffffULL) return KNN_ERR_INVALID;
     if ((ix->labels != NULL) != (labels != NULL)) return KNN_ERR_INVALID;
     if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
     const size_t m1 = ix->m + rows;
@@ -666,13 +729,15 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
     }
     const size_t nb0 = ix->nblk, nb1 = (m1 + ix->cap - 1) / ix->cap;
     RCHK(index_grow_arrays(ix, nb1));
-    if (labels && m1 > ix->lab_cap) {
-        const size_t lc = 2 * ix->lab_cap > m1 ? 2 * ix->lab_cap : m1;
+    const size_t id1 = ix->last_id + rows;   /* (labels are indexed by id) */
+    if (labels && id1 > ix->lab_cap) {
+        const size_t lc = 2 * ix->lab_cap > id1 ? 2 * ix->lab_cap : id1;
         double *l = (double *)realloc(ix->labels, lc * sizeof(double));
         if (!l) return KNN_ERR_NOMEM;
         ix->labels = l;
         ix->lab_cap = lc;
     }
+    if (ix->ids) RCHK(index_ids_reserve(ix, m1));
     void *d_X = NULL;
     int rc = KNN_OK;
     if (!(flags & KNN_INDEX_DEVICE_SRC)) rc = upload(&d_X, X, rows * ix->n * knn_src_esize(src_dtype));
@@ -689,6 +754,14 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
         meta_max(cmeta, ix->chm + ix->m / ix->cap * KNN_META_DOUBLES, nb1 - ix->m / ix->cap);
         keep_s8 = ix->have_s8 && knn_s8_spec_ok(cmeta, ix->n, ix->dtype);
         if (keep_s8) rc = add_rows(ix, ix->s8, src, rows, layout, src_dtype, 1);
+    }
+    /* the new rows' ids last_id + 1 .. behind the live ones (entries past m
+     * are read by nothing until m is committed below) */
+    if (!rc && ix->ids) {
+        for (size_t r = 0; r < rows; r++) ix->ids[ix->m + r] = (int32_t)(ix->last_id + 1 + r);
+        if (hipMemcpyAsync(ix->d_ids + ix->m, ix->ids + ix->m, rows * sizeof(int32_t), hipMemcpyHostToDevice, NULL) !=
+            hipSuccess)
+            rc = KNN_ERR_HIP;
     }
     /* the packs have read the source before the call returns */
     if (!rc) rc = stream_wait();
@@ -711,14 +784,162 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
         }
         ix->have_s8 = 0;
     }
-    if (labels) memcpy(ix->labels + ix->m, labels, rows * sizeof(double));
+    if (labels) memcpy(ix->labels + ix->last_id, labels, rows * sizeof(double));
     memcpy(ix->cmeta, cmeta, sizeof(cmeta));
     ix->nblk = nb1;
     ix->m = m1;
+    ix->last_id = id1;
     for (size_t b = 0; b < nb1; b++) {
         ix->cbase[b] = b * ix->cap;
         ix->cnc[b] = m1 - ix->cbase[b] < ix->cap ? m1 - ix->cbase[b] : ix->cap;
     }
+    return KNN_OK;
+}
+
+/* --------------------------------------------------------------- remove */
+
+/* The device side of a plan that moves rows: every block from pl->b0 on is
+ * built again in a fresh, zeroed buffer by one gather a run (and one of the
+ * byte rows where the index has byte blocks), its meta the max of the blocks
+ * it drew from.  Old and new buffers are resident together until the one wait
+ * at the end; on success the new ones are in nblk[] / ns8[] / nhm (entries
+ * b0 .. nb1-1), on failure everything made here is freed. */
+static int remove_move(knn_index_t *ix, const knn_rm_plan_t *pl, void **nblk, void **ns8, double *nhm)
+{
+    const size_t n = ix->n, cap = ix->cap, b0 = pl->b0, nb1 = pl->nb1;
+    const size_t ebytes = knn_block_bytes_dt(cap, n, ix->dtype), sbytes = knn_s8_bytes(cap, n);
+    int32_t *d_list = NULL;
+    double *hm = (double *)calloc(2 * (nb1 - b0) * KNN_META_DOUBLES, sizeof(double));   /* staged until the wait */
+    int rc = hm ? KNN_OK : KNN_ERR_NOMEM;
+    for (size_t b = b0; b < nb1 && !rc; b++) {
+        if (hipMalloc(&nblk[b], ebytes) != hipSuccess) rc = KNN_ERR_NOMEM;
+        else if (hipMemsetAsync(nblk[b], 0, ebytes, NULL) != hipSuccess) rc = KNN_ERR_HIP;
+        if (rc || !ix->have_s8) continue;
+        if (hipMalloc(&ns8[b], sbytes) != hipSuccess) rc = KNN_ERR_NOMEM;
+        else if (hipMemsetAsync(ns8[b], 0, sbytes, NULL) != hipSuccess) rc = KNN_ERR_HIP;
+    }
+    /* the runs' lists, one array */
+    if (!rc && hipMalloc((void **)&d_list, pl->nlist * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc && hipMemcpyAsync(d_list, pl->list, pl->nlist * sizeof(int32_t), hipMemcpyHostToDevice, NULL) != hipSuccess)
+        rc = KNN_ERR_HIP;
+    for (size_t r = 0; r < pl->nruns && !rc; r++) {
+        const knn_rm_run_t *run = &pl->runs[r];
+        rc = knn_block_gather_dt(nblk[run->nb], cap, run->dst0, ix->blk[run->ob], cap, d_list + run->list0, run->rows,
+                                 n, ix->dtype, NULL);
+        if (!rc && ix->have_s8)
+            rc = knn_block_gather_s8(ns8[run->nb], cap, run->dst0, ix->s8[run->ob], cap, d_list + run->list0,
+                                     run->rows, n, NULL);
+        meta_max(nhm + run->nb * KNN_META_DOUBLES, ix->chm + run->ob * KNN_META_DOUBLES, 1);
+    }
+    /* the trailing meta words, as index_reblock writes them (a later append
+     * takes its atomicMax into them) */
+    for (size_t b = b0; b < nb1 && !rc; b++) {
+        double *e = hm + 2 * (b - b0) * KNN_META_DOUBLES, *s = e + KNN_META_DOUBLES;
+        memcpy(e, nhm + b * KNN_META_DOUBLES, KNN_META_DOUBLES * sizeof(double));
+        e[KNN_META_S8] = 0.0;
+        if (hipMemcpyAsync((char *)nblk[b] + knn_block_meta_offset_dt(cap, n, ix->dtype), e,
+                           KNN_META_DOUBLES * sizeof(double), hipMemcpyHostToDevice, NULL) != hipSuccess)
+            rc = KNN_ERR_HIP;
+        if (rc || !ix->have_s8) continue;
+        memcpy(s, e, KNN_META_DOUBLES * sizeof(double));
+        s[KNN_META_S8] = 1.0;
+        if (hipMemcpyAsync((char *)ns8[b] + knn_s8_meta_offset(cap, n), s, KNN_META_DOUBLES * sizeof(double),
+                           hipMemcpyHostToDevice, NULL) != hipSuccess)
+            rc = KNN_ERR_HIP;
+    }
+    if (!rc) rc = stream_wait();
+    else hipStreamSynchronize(NULL);
+    hipFree(d_list);
+    free(hm);
+    if (rc)
+        for (size_t b = b0; b < nb1; b++) {
+            hipFree(nblk[b]);
+            hipFree(ns8[b]);
+            nblk[b] = ns8[b] = NULL;
+        }
+    return rc;
+}
+
+int knn_index_remove(knn_index_t *ix, const int32_t *ids, size_t count, int flags, size_t *removed)
+{
+    if (!ix || !ids || count == 0 || flags != 0) return KNN_ERR_INVALID;
+    for (size_t i = 0; i < count; i++)
+        if (ids[i] < 1 || (size_t)ids[i] > ix->last_id) return KNN_ERR_INVALID;
+    /* the plan, on the host alone (knn_remove_plan.h) */
+    int32_t *pos = (int32_t *)malloc(count * sizeof(int32_t));
+    if (!pos) return KNN_ERR_NOMEM;
+    memcpy(pos, ids, count * sizeof(int32_t));
+    const size_t npos = knn_rm_positions(ix->ids, ix->m, pos, knn_rm_sort_dedupe(pos, count));
+    if (npos == 0 || npos >= ix->m) {
+        /* nothing live in the list; or no live row would be left */
+        free(pos);
+        if (npos == 0 && removed) *removed = 0;
+        return npos == 0 ? KNN_OK : KNN_ERR_INVALID;
+    }
+    knn_rm_plan_t pl;
+    const int prc = knn_rm_plan(&pl, ix->ids, ix->m, ix->cap, pos, npos);
+    free(pos);
+    if (prc) return KNN_ERR_NOMEM;
+    int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+    /* the new id map beside the old one, and the moved blocks beside theirs */
+    const size_t icap = ix->ids_cap > pl.m1 ? ix->ids_cap : pl.m1;
+    int32_t *d_ids = NULL, *h_ids = NULL;
+    void **nblk = (void **)calloc(2 * ix->nblk, sizeof(void *)), **ns8 = nblk ? nblk + ix->nblk : NULL;
+    double *nhm = (double *)calloc(ix->nblk * KNN_META_DOUBLES, sizeof(double));
+    if (!rc && (!nblk || !nhm)) rc = KNN_ERR_NOMEM;
+    if (!rc && !(h_ids = (int32_t *)malloc(icap * sizeof(int32_t)))) rc = KNN_ERR_NOMEM;
+    if (!rc && hipMalloc((void **)&d_ids, icap * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc) {
+        memcpy(h_ids, pl.ids, pl.m1 * sizeof(int32_t));
+        if (hipMemcpy(d_ids, h_ids, pl.m1 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = KNN_ERR_HIP;
+    }
+    if (!rc && pl.moves) rc = remove_move(ix, &pl, nblk, ns8, nhm);
+    if (rc) {   /* the index answers as before the call */
+        hipFree(d_ids);
+        free(h_ids);
+        free(nblk);
+        free(nhm);
+        knn_rm_plan_free(&pl);
+        return rc;
+    }
+    /* commit: the moved blocks in place of the old ones, the blocks past the
+     * new count released, then m, cnc, cbase, nblk and the id map.  cmeta
+     * stays: a MAX that has only become too large is conservative. */
+    if (pl.moves)
+        for (size_t b = pl.b0; b < pl.nb1; b++) {
+            hipFree(ix->blk[b]);
+            hipFree(ix->s8[b]);
+            ix->blk[b] = nblk[b];
+            ix->s8[b] = ns8[b];
+            memcpy(ix->chm + b * KNN_META_DOUBLES, nhm + b * KNN_META_DOUBLES, KNN_META_DOUBLES * sizeof(double));
+        }
+    for (size_t b = pl.nb1; b < ix->nblk; b++) {
+        hipFree(ix->blk[b]);
+        hipFree(ix->s8[b]);
+        ix->blk[b] = ix->s8[b] = NULL;
+    }
+    ix->m = pl.m1;
+    ix->nblk = pl.nb1;
+    for (size_t b = 0; b < ix->nblk; b++) {
+        ix->cbase[b] = b * ix->cap;
+        ix->cnc[b] = ix->m - ix->cbase[b] < ix->cap ? ix->m - ix->cbase[b] : ix->cap;
+    }
+    hipFree(ix->d_ids);
+    free(ix->ids);
+    ix->ids = h_ids;
+    ix->d_ids = d_ids;
+    ix->ids_cap = icap;
+    if (removed) *removed = pl.removed;
+    free(nblk);
+    free(nhm);
+    knn_rm_plan_free(&pl);
+    return KNN_OK;
+}
+
+int knn_index_last_id(const knn_index_t *ix, size_t *last_id)
+{
+    if (!ix || !last_id) return KNN_ERR_INVALID;
+    *last_id = ix->last_id;
     return KNN_OK;
 }
 
@@ -737,6 +958,7 @@ int knn_index_info(const knn_index_t *ix, size_t *m, size_t *n, int *nblocks, si
             if (ix->ts8[t]) b += knn_s8_bytes(ix->tile_cap, ix->n);
         }
         b += ix->out_recs * sizeof(knn_neighbour_t);
+        if (ix->d_ids) b += ix->ids_cap * sizeof(int32_t);
         *device_bytes = b + knn_ctx_device_bytes(ix->ctx);
     }
     return KNN_OK;

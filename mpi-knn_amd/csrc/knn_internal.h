@@ -213,6 +213,18 @@ int knn_launch_append(void *blk, int dtype, size_t cap, size_t row0, size_t rows
                       int src_dtype, size_t ld, int layout, void *stream);
 int knn_launch_append_s8(void *dst, int dtype, size_t cap, size_t row0, size_t rows, size_t n, const void *src,
                          int src_dtype, size_t ld, int layout, void *stream);
+/* knn_pack.hip: block row row0 + i of dst <- row list[i] of src, i < rows
+ * (knn_block_gather_dt / knn_block_gather_s8): element rows and norms bit for
+ * bit; byte rows verbatim, their norm words made again for the new row.  Only
+ * those rows are written; grids over `rows` */
+int knn_launch_gather(void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap, const int32_t *list,
+                      size_t rows, size_t n, int dtype, void *stream);
+int knn_launch_gather_rows8(void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap,
+                            const int32_t *list, size_t rows, size_t n, void *stream);
+/* knn_kernels.hip: the records' idx from internal position to external id
+ * (knn_index_query of an index that removed rows): idx = ids[idx - 1], empty
+ * slots (idx 0) kept */
+int knn_launch_remap_idx(knn_neighbour_t *nb, size_t cnt, const int32_t *ids, size_t nids, void *stream);
 /* INT-mode merge of int8 lane lists (kl = KNN_I8_KL_S / KNN_I8_KL, kp <= 64)
  * by ranking the candidates at or below the shared bound (k_merge_rank) */
 int knn_launch_merge_rank(int dtype, int kp, int kl, int k, const double *part_d, const int *part_i,

@@ -2375,3 +2375,24 @@ extern "C" int knn_launch_vote(knn_neighbour_t *nb, size_t m, int k, int nclasse
                        nclasses, rule, labels, (long long)nlabels, (long long)q_base, pred, matches);
     return hip_status();
 }
+
+// k_remap_idx: the records of an index that removed rows (knn_index_remove)
+// carry internal positions; ids[] (ascending, one a live row) gives each its
+// external id.  Empty slots (idx 0) stay {inf, 0, 0}.
+__global__ __launch_bounds__(256) void k_remap_idx(knn_neighbour_t *__restrict__ nb, size_t cnt,
+                                                   const int *__restrict__ ids, int nids)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= cnt) return;
+    const int idx = nb[i].idx;
+    nb[i].idx = idx > 0 && idx <= nids ? ids[idx - 1] : 0;
+}
+
+extern "C" int knn_launch_remap_idx(knn_neighbour_t *nb, size_t cnt, const int32_t *ids, size_t nids, void *stream)
+{
+    if (cnt == 0) return KNN_OK;
+    if (nids > 0x7fffffffULL || (cnt + 255) / 256 > 0x7fffffffULL) return KNN_ERR_INVALID;
+    hipLaunchKernelGGL(k_remap_idx, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nb, cnt,
+                       ids, (int)nids);
+    return hip_status();
+}

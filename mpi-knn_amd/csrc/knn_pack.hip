@@ -10,6 +10,8 @@
 //   k_shadow     element block -> fp16 shadow rows (the H16 == 2 contraction)
 //   k_shadow_split   element blocks -> split fp16 rows (k_dist_split)
 //   k_wire_pack / k_wire_unpack  element array <-> int16 ring wire form
+//   k_gather_rows    listed rows of a block -> rows row0 .. of another block
+//                (element and byte blocks: knn_block_gather_dt / _s8)
 //
 // A source is fp64, fp32 or unsigned char (KNN_U8), column-major (ld >= rows)
 // or row-major (ld >= n).  The images, rows_pad = round_up(capacity, 128):
@@ -753,4 +755,101 @@ extern "C" int knn_launch_shadow_split(void *dst, const void *blk, int dtype, si
                                        float S, void *stream)
 {
     return knn_launch_shadow_split_n(1, &dst, &blk, &rows_pad, dtype, n, S, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Block gathers (knn_block_gather_dt / knn_block_gather_s8): block row
+// row0 + i of dst becomes row list[i] of src, i < rows -- the stable
+// compaction of knn_index_remove, and any other selection of rows.  Pure
+// copies: a row is rb bytes, whole 128-byte chunks in an element block and a
+// multiple of 32 bytes in a byte block, so a lane moves 16 bytes per load and
+// store.  lpr lanes (a power of two >= rb / 16, at most 64) share a row and a
+// wave carries 64 / lpr rows at once, as k_pack8_row_u8 does; a longer row is
+// walked by its 64 lanes, four 16-byte pieces a lane in flight.  Only the
+// listed rows and their norms are written: no padding, no meta.  A list entry
+// outside [0, src_cap) writes nothing.
+//
+//   element block: the norm (one T) is copied with the row, bit for bit (es =
+//       sizeof(T): the kernel never looks at the values).
+//   byte block: both norm words depend on the row's position (i8_norm_word's
+//       slot, i8_norm_pos); they are made again for row0 + i from the norm the
+//       source words hold (i8_norm_of), as k_gather8 does.
+// ---------------------------------------------------------------------------
+template <bool S8>
+__global__ __launch_bounds__(256) void k_gather_rows(char *__restrict__ dst, const char *__restrict__ src,
+                                                     const int *__restrict__ list, size_t rows, size_t row0,
+                                                     int src_cap, int rb, int es, size_t dst_rp, size_t src_rp,
+                                                     int lpr)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int rpw = 64 / lpr;               // rows a wave
+    const int sub = lane / lpr, g = lane % lpr;
+    const int c16 = rb / 16;                // 16-byte pieces a row
+    char *dn = dst + dst_rp * (size_t)rb;
+    const char *sn = src + src_rp * (size_t)rb;
+    for (size_t rbase = ((size_t)blockIdx.x * 4 + wave) * rpw; rbase < rows; rbase += (size_t)gridDim.x * 4 * rpw) {
+        const size_t r = rbase + sub;
+        const int q = r < rows ? list[r] : -1;
+        if ((unsigned)q >= (unsigned)src_cap) continue;
+        const knn_v4u *s = (const knn_v4u *)(src + (size_t)q * rb);
+        knn_v4u *d = (knn_v4u *)(dst + (row0 + r) * (size_t)rb);
+        for (int c = g; c < c16; c += 4 * lpr) {
+            knn_v4u v[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (c + u * lpr < c16) v[u] = __builtin_nontemporal_load(s + c + u * lpr);
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (c + u * lpr < c16) d[c + u * lpr] = v[u];
+        }
+        if (g != 0) continue;
+        const size_t t = row0 + r;
+        if constexpr (S8) {
+            const int *snw = (const int *)sn;
+            int *dnw = (int *)dn;
+            const int nrm = i8_norm_of(snw[i8_norm_pos(q)], snw[src_rp + i8_norm_pos(q)]);
+            dnw[i8_norm_pos((int)t)] = i8_norm_word((int)t, nrm, rb);
+            dnw[dst_rp + i8_norm_pos((int)t)] = i8_init_word(nrm, rb);
+        } else if (es == 8) {
+            ((unsigned long long *)dn)[t] = ((const unsigned long long *)sn)[q];
+        } else {
+            ((unsigned *)dn)[t] = ((const unsigned *)sn)[q];
+        }
+    }
+}
+
+// rb: the row bytes of both blocks (a multiple of 32); es: the element block's
+// element size, 0 for a byte block
+static int launch_gather(bool s8, void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap,
+                         const int32_t *list, size_t rows, size_t rb, int es, void *stream)
+{
+    if (rb > 0x7fffffffULL) return KNN_ERR_INVALID;
+    int lpr = 1;
+    while (lpr < 64 && 16 * (size_t)lpr < rb) lpr *= 2;
+    // waves for one pass: 64 / lpr rows a wave, 4 waves a workgroup
+    const size_t nw = (rows * lpr + 63) / 64;
+    const unsigned nb = (unsigned)((nw + 3) / 4 < 16384 ? (nw + 3) / 4 : 16384);
+    const size_t drp = knn_rows_pad(dst_cap), srp = knn_rows_pad(src_cap);
+    if (s8)
+        hipLaunchKernelGGL(k_gather_rows<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (char *)dst,
+                           (const char *)src, list, rows, row0, (int)src_cap, (int)rb, es, drp, srp, lpr);
+    else
+        hipLaunchKernelGGL(k_gather_rows<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (char *)dst,
+                           (const char *)src, list, rows, row0, (int)src_cap, (int)rb, es, drp, srp, lpr);
+    return hip_status();
+}
+
+extern "C" int knn_launch_gather(void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap,
+                                 const int32_t *list, size_t rows, size_t n, int dtype, void *stream)
+{
+    if (dtype != KNN_F64 && dtype != KNN_F32) return KNN_ERR_INVALID;
+    const int es = (int)knn_esize(dtype);
+    return launch_gather(false, dst, dst_cap, row0, src, src_cap, list, rows, knn_n_pad_dt(n, dtype) * es, es,
+                         stream);
+}
+
+extern "C" int knn_launch_gather_rows8(void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap,
+                                       const int32_t *list, size_t rows, size_t n, void *stream)
+{
+    return launch_gather(true, dst, dst_cap, row0, src, src_cap, list, rows, knn_s8_rs(n), 0, stream);
 }

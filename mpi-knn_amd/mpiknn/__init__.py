@@ -53,6 +53,7 @@ API_SYMBOLS = (
     "knn_ctx_set_solo", "knn_ctx_search_meta", "knn_query", "knn_classify_query", "knn_ctx_set_keep_zero",
     "knn_index_create", "knn_index_query", "knn_index_info", "knn_index_destroy",
     "knn_index_add", "knn_block_append_dt", "knn_block_append_s8",
+    "knn_index_remove", "knn_index_last_id", "knn_block_gather_dt", "knn_block_gather_s8",
 )
 DTYPES = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 # a pack / index SOURCE may also be unsigned bytes (KNN_U8: never a block or search dtype)
@@ -152,6 +153,10 @@ def _load():
         "knn_index_add": ([p, p, sz, i, i, p, i], i),
         "knn_block_append_dt": ([p, i, sz, sz, sz, sz, p, i, sz, i, p], i),
         "knn_block_append_s8": ([p, i, sz, sz, sz, sz, p, i, sz, i, p], i),
+        "knn_index_remove": ([p, p, sz, i, psz], i),
+        "knn_index_last_id": ([p, psz], i),
+        "knn_block_gather_dt": ([p, sz, sz, p, sz, p, sz, sz, i, p], i),
+        "knn_block_gather_s8": ([p, sz, sz, p, sz, p, sz, sz, p], i),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -371,6 +376,13 @@ def block_append(d_block, cap, row0, rows, n, d_src, ld, layout, stream=0, dtype
                                    ld, layout, stream or None), "knn_block_append_dt")
 
 
+def block_gather(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, stream=0, dtype="f64"):
+    """knn_block_gather_dt: block row row0 + i of d_dst <- row d_list[i] of
+    d_src, i < rows (device pointers; d_list: int32 local source rows)."""
+    _check(lib.knn_block_gather_dt(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, DTYPES[dtype],
+                                   stream or None), "knn_block_gather_dt")
+
+
 _live_contexts = weakref.WeakSet()
 
 
@@ -394,6 +406,13 @@ def block_append_s8(d_sblock, cap, row0, rows, n, d_src, ld, layout, stream=0, d
     """knn_block_append_s8: the same rows of a byte block packed by block_pack_s8."""
     _check(lib.knn_block_append_s8(d_sblock, DTYPES[dtype], cap, row0, rows, n, d_src, SRC_DTYPES[src_dtype], ld,
                                    layout, stream or None), "knn_block_append_s8")
+
+
+def block_gather_s8(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, stream=0):
+    """knn_block_gather_s8: the same rows of byte blocks, their norm words made
+    again for the new rows."""
+    _check(lib.knn_block_gather_s8(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, stream or None),
+           "knn_block_gather_s8")
 
 
 def s8_spec_ok(meta_host, n, dtype="f64"):
@@ -521,7 +540,8 @@ class Index:
         layout argument; types as the constructor's X, its own) without
         repacking what is resident.  labels: one a row when the index was
         made with labels, else None.  Returns the 1-based id of the first
-        added row; the index keeps nothing of X after the call returns."""
+        added row (last_id + 1: ids are never reused); the index keeps nothing
+        of X after the call returns."""
         if not self._h:
             raise ValueError("the index is closed")
         ptr, keep, rows, n, lay, src, dev = _index_source(X, self.layout, "X")
@@ -530,11 +550,40 @@ class Index:
         lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.float64)
         if lab is not None and lab.shape[0] != rows:
             raise ValueError("labels must have %d entries, got %d" % (rows, lab.shape[0]))
+        first = self.last_id + 1
         _check(lib.knn_index_add(self._h, ptr, rows, lay, src, _ptr(lab), dev), "knn_index_add")
         del keep
-        first = self.m + 1
         self.m += rows
         return first
+
+    def remove(self, ids):
+        """knn_index_remove: forget the rows with these 1-based ids (any integer
+        sequence or array; sent as int32).  Ids no longer live and repeats are
+        skipped; an id outside [1, last_id], or a list that would leave no row,
+        raises KnnError(ERR_INVALID) and changes nothing.  The other rows keep
+        their ids.  Returns the number of rows removed."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        a = np.asarray(ids).reshape(-1)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError("ids must be integers, got %s" % a.dtype)
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise KnnError(ERR_INVALID, "knn_index_remove")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        removed = ctypes.c_size_t()
+        _check(lib.knn_index_remove(self._h, _ptr(a), a.size, 0, ctypes.byref(removed)), "knn_index_remove")
+        self.m -= removed.value
+        return removed.value
+
+    @property
+    def last_id(self):
+        """knn_index_last_id: the highest id handed out so far (m while nothing
+        was removed)."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        v = ctypes.c_size_t()
+        _check(lib.knn_index_last_id(self._h, ctypes.byref(v)), "knn_index_last_id")
+        return v.value
 
     def info(self):
         """knn_index_info: IndexInfo(m, n, nblocks, device_bytes, last_bits)."""

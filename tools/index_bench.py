@@ -23,6 +23,20 @@ Legs (one a process, so two builds of the library can be run in alternation:
   rebuild what a user without add does: knn_index_create of the 60000 + rows
           concatenated corpus (host wall), same sources and sizes; runs on a
           build without add too
+  remove  Index.remove of 1, 128 and 10000 random ids from the 60000-row index
+          (uint8 and float64 source) that has served one query: host wall and
+          device span (events around the call), the span of the first query
+          (mq = 128) after it against the same query on a fresh index of the
+          survivors, and what a user without remove does: knn_index_create of
+          the surviving rows from a host array (host wall; --tag parent with
+          --leg rebuild-survivors runs that on a build without remove)
+  gather  knn_block_gather_dt / _s8 alone, 60000 x 784 and 1M x 128, every
+          second row dropped: HIP events, fraction of HBM over the algorithmic
+          bytes (each moved row read once and written once, plus its norm or
+          norm words), beside hipMemcpyAsync device to device of the same
+          byte count in the same process
+  mapcost Index.query spans at every --mq on one index before and after one
+          removal (the id translation at the end of the span)
 
 Median of --runs after --warmup, with min and max.  Each leg appends one JSON
 line to --out; --merge FILES... folds such lines into profiles/index_bench.json.
@@ -196,6 +210,143 @@ def leg_rebuild(knn, a, X):
     return out
 
 
+def removal_ids(m, rows):
+    import numpy as np
+    return np.sort(np.random.default_rng(1000 + rows).choice(np.arange(1, m + 1), rows, replace=False)).astype(np.int32)
+
+
+def leg_rebuild_survivors(knn, a, X):
+    """knn_index_create of the rows a removal leaves, from a host array"""
+    import numpy as np
+    out = []
+    for src in ("u8", "f64"):
+        for rows in ADD_ROWS:
+            keep = np.ones(len(X), dtype=bool)
+            keep[removal_ids(len(X), rows) - 1] = False
+            C = np.ascontiguousarray(X[keep].astype(np.uint8) if src == "u8" else X[keep])
+            t = []
+            for i in range(a.warmup + a.runs):
+                t0 = time.perf_counter()
+                ix = knn.Index(C)
+                w = (time.perf_counter() - t0) * 1e3
+                ix.close()
+                if i >= a.warmup:
+                    t.append(w)
+            out.append(dict(rows=rows, source=src, create_wall=stats(t)))
+    return out
+
+
+def leg_remove(knn, a, X, Qall):
+    """every timed removal meets a fresh 60000-row index that has served one
+    query; indices are created outside the timings"""
+    import numpy as np
+    import torch
+    Q = Qall[:128]
+    out = []
+    for src in ("u8", "f64"):
+        cast = (lambda A: A.astype(np.uint8)) if src == "u8" else (lambda A: A)
+        Xs, Qs = np.ascontiguousarray(cast(X)), cast(Q)
+        for rows in ADD_ROWS:
+            ids = removal_ids(len(X), rows)
+            wall, span, q_after, q_fresh = [], [], [], []
+            for i in range(a.warmup + a.runs):
+                ix = knn.Index(Xs)
+                ix.query(Qs, a.k)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                e0.record()
+                ix.remove(ids)
+                e1.record()
+                w = (time.perf_counter() - t0) * 1e3
+                e1.synchronize()
+                _, s = ix.query(Qs, a.k)
+                ix.close()
+                if i >= a.warmup:
+                    wall.append(w)
+                    span.append(e0.elapsed_time(e1))
+                    q_after.append(s * 1e3)
+            keep = np.ones(len(X), dtype=bool)
+            keep[ids - 1] = False
+            fresh = knn.Index(np.ascontiguousarray(Xs[keep]))
+            for i in range(a.warmup + a.runs):
+                _, s = fresh.query(Qs, a.k)
+                if i >= a.warmup:
+                    q_fresh.append(s * 1e3)
+            fresh.close()
+            out.append({"rows": rows, "source": src, "wall": stats(wall), "span": stats(span),
+                        "first_query_after_remove": stats(q_after), "query_fresh_index": stats(q_fresh)})
+    return out
+
+
+def leg_gather(knn, a):
+    import torch
+    dev = torch.device("cuda", 0)
+    out = []
+    for rows, n in ((60000, 784), (1000000, 128)):
+        V = torch.randint(0, 256, (rows, n), dtype=torch.uint8, device=dev)
+        lst = torch.arange(0, rows, 2, dtype=torch.int32, device=dev)
+        cnt = lst.numel()
+        st = torch.cuda.current_stream(dev).cuda_stream
+        for form in ("f64", "f32", "s8"):
+            nbytes = knn.s8_block_bytes(rows, n) if form == "s8" else knn.block_bytes(rows, n, form)
+            src = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+            dst = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+            if form == "s8":
+                knn.block_pack_s8(src.data_ptr(), rows, rows, n, V.data_ptr(), n, knn.ROWMAJOR, st, src_dtype="u8")
+                moved = cnt * (-(-n // 32) * 32 + 8)
+            else:
+                knn.block_pack(src.data_ptr(), rows, rows, n, V.data_ptr(), n, knn.ROWMAJOR, st, dtype=form,
+                               src_dtype="u8")
+                es = 8 if form == "f64" else 4
+                moved = cnt * (-(-n * es // 128) * 128 + es)
+            tg, tc = [], []
+            for i in range(a.warmup + a.runs):
+                e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+                e0.record()
+                if form == "s8":
+                    knn.block_gather_s8(dst.data_ptr(), rows, 0, src.data_ptr(), rows, lst.data_ptr(), cnt, n, st)
+                else:
+                    knn.block_gather(dst.data_ptr(), rows, 0, src.data_ptr(), rows, lst.data_ptr(), cnt, n, st,
+                                     dtype=form)
+                e1.record()
+                dst[:moved].copy_(src[:moved])        # hipMemcpyAsync, device to device
+                e2.record()
+                e2.synchronize()
+                if i >= a.warmup:
+                    tg.append(e0.elapsed_time(e1))
+                    tc.append(e1.elapsed_time(e2))
+            r = dict(rows=rows, n=n, form=form, moved_rows=cnt, bytes=2 * moved, gather=stats(tg), memcpy=stats(tc))
+            r["gather_hbm_frac"] = 2 * moved / (r["gather"]["median_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+            r["memcpy_hbm_frac"] = 2 * moved / (r["memcpy"]["median_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+            out.append(r)
+            del src, dst
+        del V, lst
+    return out
+
+
+def leg_mapcost(knn, a, X, Qall):
+    import numpy as np
+    rows = []
+    ix = knn.Index(X.astype(np.uint8))
+    # the kept context and tiles at the capacity of the largest batch first, so
+    # that both states run every mq on the same buffers
+    ix.query(Qall[:max(a.mq)].astype(np.uint8), a.k, keep_zero=True)
+    for state in ("before", "after"):
+        if state == "after":
+            ix.remove([len(X) // 2])
+        for mq in a.mq:
+            Q = Qall[:mq].astype(np.uint8)
+            t = []
+            for i in range(a.warmup + a.runs):
+                _, s = ix.query(Q, a.k, keep_zero=True)
+                if i >= a.warmup:
+                    t.append(s * 1e3)
+            rows.append({"mq": mq, "state": state, "span": stats(t)})
+    ix.close()
+    return rows
+
+
 def merge(files, out, keep=False):
     legs = []
     if keep and os.path.exists(out):
@@ -215,7 +366,8 @@ def merge(files, out, keep=False):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--leg", choices=["query", "index", "pack", "add", "rebuild"])
+    ap.add_argument("--leg", choices=["query", "index", "pack", "add", "rebuild", "remove", "rebuild-survivors", "gather",
+                                     "mapcost"])
     ap.add_argument("--root", default=ROOT, help="tree whose mpi-knn_amd/ is imported")
     ap.add_argument("--tag", default="this", help="name of the build in the output")
     ap.add_argument("--round", type=int, default=0)
@@ -238,6 +390,8 @@ def main():
     rec = {"leg": a.leg, "build": a.tag, "round": a.round, "warmup": a.warmup}
     if a.leg == "pack":
         rec["results"] = leg_pack(mpiknn, a)
+    elif a.leg == "gather":
+        rec["results"] = leg_gather(mpiknn, a)
     else:
         X, _ = synth.mnist_like(a.m)
         Qall, _ = synth.mnist_like(max(a.mq), seed=77)
@@ -247,6 +401,12 @@ def main():
             rec["results"] = leg_add(mpiknn, a, X, Qall)
         elif a.leg == "rebuild":
             rec["results"] = leg_rebuild(mpiknn, a, X)
+        elif a.leg == "rebuild-survivors":
+            rec["results"] = leg_rebuild_survivors(mpiknn, a, X)
+        elif a.leg == "remove":
+            rec["results"] = leg_remove(mpiknn, a, X, Qall)
+        elif a.leg == "mapcost":
+            rec["results"] = leg_mapcost(mpiknn, a, X, Qall)
         else:
             rec.update(leg_index(mpiknn, a, X, Qall))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
