@@ -306,6 +306,37 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * or ids, count == 0, flags != 0, an id outside [1, last_id], a call that
  * would leave no live row.
  *
+ * knn_index_update: give rows new coordinates, by id, in place.  X is count x
+ * n in `layout`, of src_dtype (fp64, fp32 or KNN_U8; KNN_INDEX_DEVICE_SRC: a
+ * device pointer -- no other flag), and its row i becomes the row with id
+ * ids[i] (`count` ids on the host, in any order).  Ids, last_id, m, the number
+ * of blocks, the capacity and every row's position stay, so equal distances
+ * still come lower id first, and so do the kept context and tile buffers; a
+ * caller's tables by id (d_labels of knn_classify_device) stay valid, which a
+ * remove + add of the same rows cannot offer: that pair hands out new ids and
+ * rebuilds every block from the first removed row on.  Here the ids are mapped
+ * to positions and grouped by block on the host (knn_update_plan.h), source
+ * and lists are uploaded, and each touched block takes one
+ * knn_block_scatter_dt: the moved bytes are the updated rows' own.  The touched
+ * blocks' meta is MAX-reduced into the corpus meta, which therefore only grows
+ * -- conservative, as after a removal: it can cost a faster path or a rescan,
+ * never exactness.  An index with byte blocks scatters the same rows into them
+ * straight from the source (knn_block_scatter_s8) while the corpus meta still
+ * passes knn_s8_spec_ok; when it no longer does the byte blocks are freed as
+ * in knn_index_add and never come back.  labels: count doubles that replace
+ * the labels of those ids, or NULL to leave the labels as they are.  The caller
+ * may free or overwrite X when the call returns.  A failure before the first
+ * overwritten row (every allocation and upload comes before it) leaves the
+ * index answering as before; a HIP error after it returns KNN_ERR_HIP and the
+ * index is then fit only for knn_index_destroy -- rows are written in place,
+ * so there is no older state to go back to.  Unlike knn_index_remove, ids that
+ * are no longer live and repeats are refused, not skipped: a silently dropped
+ * update is data loss.  KNN_ERR_INVALID, before any device call and with
+ * nothing changed: NULL index, ids or X, count == 0, a bad layout, unknown flag
+ * bits, an id outside [1, last_id], an id that is no longer live, an id twice
+ * in the list, labels where the index has none; KNN_ERR_UNSUPPORTED: an unknown
+ * src_dtype.
+ *
  * KNN_ERR_INVALID: NULL index, X, Q or out, zero m, mq or n, k <= 0, a bad
  * layout, unknown flag bits, m + mq > INT32_MAX; KNN_ERR_UNSUPPORTED: an
  * unknown src_dtype, dtype not KNN_F64 / KNN_F32, k above the dtype's limit
@@ -325,6 +356,8 @@ KNN_API int knn_index_add(knn_index_t *index, const void *X, size_t rows, int la
                           const double *labels, int flags);
 KNN_API int knn_index_remove(knn_index_t *index, const int32_t *ids, size_t count, int flags,
                              size_t *removed /* nullable */);
+KNN_API int knn_index_update(knn_index_t *index, const int32_t *ids, size_t count, const void *X, int layout,
+                             int src_dtype, const double *labels /* nullable */, int flags);
 KNN_API int knn_index_last_id(const knn_index_t *index, size_t *last_id);
 KNN_API int knn_index_info(const knn_index_t *index, size_t *m, size_t *n, int *nblocks,
                            size_t *device_bytes, int *last_bits);
@@ -455,6 +488,28 @@ KNN_API int knn_block_pack_dt(void *d_block, int dtype, size_t cap, size_t rows,
  * knn_block_pack_dt. */
 KNN_API int knn_block_append_dt(void *d_block, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
                                 const void *d_src, int src_dtype, size_t ld, int layout, void *stream);
+/* Rows given new values in place: work item i < rows reads row d_srow[i] (a
+ * NULL d_srow: row i) of the src_rows x n source and writes block row d_pos[i]
+ * of a block packed before with the same cap, n and dtype (layouts, ld and
+ * source types as knn_block_pack_dt; d_pos and d_srow are device int32 arrays
+ * of `rows` entries).  Otherwise an append: only the listed rows, their norms
+ * and the meta are touched -- no padding, no other row -- and launches are
+ * sized by `rows`.  A block packed before and scattered into with distinct
+ * positions is, outside its 8 meta doubles, byte for byte the block one
+ * knn_block_pack_dt of the updated array writes (a row's norm is summed by the
+ * same lanes in the same order wherever it lands and whichever source row it
+ * comes from); its meta is, word by word, max(the meta before, the meta of a
+ * pack of the listed source rows alone), word 7 as it was.  Repeated positions
+ * leave one of their rows, unspecified which.  A d_pos[i] outside [0, cap)
+ * writes nothing (the row's values may still reach the meta, which is
+ * conservative); a d_srow[i] outside [0, src_rows) reads nothing and writes
+ * nothing.  KNN_ERR_INVALID, before any device call: a NULL block, d_pos or
+ * d_src, rows, n or src_rows zero, cap or src_rows above INT32_MAX, a bad
+ * layout, ld below src_rows (column-major) or n (row-major), a dtype other
+ * than KNN_F64 / KNN_F32, an unknown src_dtype. */
+KNN_API int knn_block_scatter_dt(void *d_block, int dtype, size_t cap, const int32_t *d_pos,
+                                 const int32_t *d_srow /* nullable */, size_t rows, size_t n, const void *d_src,
+                                 size_t src_rows, int src_dtype, size_t ld, int layout, void *stream);
 /* Rows from another block: block row row0 + i of d_dst becomes row d_list[i]
  * of d_src, i < rows.  Both are packed blocks of the given capacities with the
  * same n and dtype; d_list is a device array of local source rows, each below
@@ -514,6 +569,13 @@ KNN_API int knn_block_pack_s8(void *d_sblock, int dtype, size_t cap, size_t rows
  * byte-for-byte contract against one knn_block_pack_s8 of all the rows. */
 KNN_API int knn_block_append_s8(void *d_sblock, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
                                 const void *d_src, int src_dtype, size_t ld, int layout, void *stream);
+/* knn_block_scatter_dt for a byte block packed by knn_block_pack_s8: the byte
+ * rows and both norm words of each listed row (made for the position it lands
+ * at) and the meta (word 7 stays 1); the same contract against one
+ * knn_block_pack_s8 of the updated array.  KNN_ERR_INVALID also for n > 896. */
+KNN_API int knn_block_scatter_s8(void *d_sblock, int dtype, size_t cap, const int32_t *d_pos,
+                                 const int32_t *d_srow /* nullable */, size_t rows, size_t n, const void *d_src,
+                                 size_t src_rows, int src_dtype, size_t ld, int layout, void *stream);
 /* knn_block_gather_dt for byte blocks: the row bytes are copied verbatim, and
  * both norm words are made again for the new row (they depend on the row's
  * position) from the norm the source's words hold.  KNN_ERR_INVALID also for

@@ -20,9 +20,13 @@
  * block gathers (knn_block_gather_dt / _s8, defined here; its host planning:
  * knn_remove_plan.h) and from then on keeps the live rows' ids, which a small
  * kernel writes into every batch's records.
+ * knn_index_update writes listed rows in place, one scatter a touched block
+ * (knn_block_scatter_dt / _s8, defined here; its host planning:
+ * knn_update_plan.h), in knn_index_add's two parts.
  */
 #include "knn_internal.h"
 #include "knn_remove_plan.h"
+#include "knn_update_plan.h"
 
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
@@ -501,6 +505,37 @@ int knn_block_append_s8(void *d_sblock, int dtype, size_t cap, size_t row0, size
     return knn_launch_append_s8(d_sblock, dtype, cap, row0, rows, n, d_src, src_dtype, ld, layout, stream);
 }
 
+/* Block row d_pos[i] <- source row d_srow[i] (include/knn.h).  Beside the
+ * appends for the same reason. */
+static int scatter_args_ok(const void *d_block, int dtype, size_t cap, const int32_t *d_pos, size_t rows, size_t n,
+                           const void *d_src, size_t src_rows, int src_dtype, size_t ld, int layout, size_t n_max)
+{
+    if (!d_block || !d_pos || !d_src || rows == 0 || n == 0 || src_rows == 0 || cap > 0x7fffffffULL ||
+        src_rows > 0x7fffffffULL || n > n_max || !dtype_ok(dtype) || !knn_src_esize(src_dtype))
+        return 0;
+    return layout == KNN_COLMAJOR ? ld >= src_rows : (layout == KNN_ROWMAJOR ? ld >= n : 0);
+}
+
+int knn_block_scatter_dt(void *d_block, int dtype, size_t cap, const int32_t *d_pos, const int32_t *d_srow,
+                         size_t rows, size_t n, const void *d_src, size_t src_rows, int src_dtype, size_t ld,
+                         int layout, void *stream)
+{
+    if (!scatter_args_ok(d_block, dtype, cap, d_pos, rows, n, d_src, src_rows, src_dtype, ld, layout, 0x7fffffffULL))
+        return KNN_ERR_INVALID;
+    return knn_launch_scatter(d_block, dtype, cap, d_pos, d_srow, rows, n, d_src, src_rows, src_dtype, ld, layout,
+                              stream);
+}
+
+int knn_block_scatter_s8(void *d_sblock, int dtype, size_t cap, const int32_t *d_pos, const int32_t *d_srow,
+                         size_t rows, size_t n, const void *d_src, size_t src_rows, int src_dtype, size_t ld,
+                         int layout, void *stream)
+{
+    if (!scatter_args_ok(d_sblock, dtype, cap, d_pos, rows, n, d_src, src_rows, src_dtype, ld, layout, KNN_I8_MAX_N))
+        return KNN_ERR_INVALID;
+    return knn_launch_scatter_s8(d_sblock, dtype, cap, d_pos, d_srow, rows, n, d_src, src_rows, src_dtype, ld, layout,
+                                 stream);
+}
+
 /* Block row row0 + i of d_dst <- row d_list[i] of d_src (include/knn.h).
  * Beside the appends for the same reason. */
 static int gather_args_ok(const void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
@@ -933,6 +968,101 @@ int knn_index_remove(knn_index_t *ix, const int32_t *ids, size_t count, int flag
     free(nblk);
     free(nhm);
     knn_rm_plan_free(&pl);
+    return KNN_OK;
+}
+
+/* --------------------------------------------------------------- update */
+
+/* one scatter a run of the plan, into the element blocks (s8 = 0: the touched
+ * blocks' meta on its way to chm) or the byte blocks; d_list: the plan's pos
+ * then its srow.  NULL stream, no wait. */
+static int update_rows(knn_index_t *ix, const knn_up_plan_t *pl, const int32_t *d_list, const void *d_X, int layout,
+                       int src_dtype, int s8)
+{
+    const size_t n = ix->n, cap = ix->cap, count = pl->count;
+    const size_t ld = layout == KNN_COLMAJOR ? count : n;
+    for (size_t r = 0; r < pl->nruns; r++) {
+        const knn_up_run_t *run = &pl->runs[r];
+        const int32_t *pos = d_list + run->list0, *srow = d_list + count + run->list0;
+        void *blk = s8 ? ix->s8[run->blk] : ix->blk[run->blk];
+        RCHK(s8 ? knn_block_scatter_s8(blk, ix->dtype, cap, pos, srow, run->rows, n, d_X, count, src_dtype, ld, layout,
+                                       NULL)
+                : knn_block_scatter_dt(blk, ix->dtype, cap, pos, srow, run->rows, n, d_X, count, src_dtype, ld, layout,
+                                       NULL));
+        if (!s8 && hipMemcpyAsync(ix->chm + run->blk * KNN_META_DOUBLES,
+                                  (const char *)blk + knn_block_meta_offset_dt(cap, n, ix->dtype),
+                                  KNN_META_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, NULL) != hipSuccess)
+            return KNN_ERR_HIP;
+    }
+    return KNN_OK;
+}
+
+int knn_index_update(knn_index_t *ix, const int32_t *ids, size_t count, const void *X, int layout, int src_dtype,
+                     const double *labels, int flags)
+{
+    if (!ix || !ids || !X || count == 0) return KNN_ERR_INVALID;
+    if (!knn_src_esize(src_dtype)) return KNN_ERR_UNSUPPORTED;
+    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (flags & ~KNN_INDEX_DEVICE_SRC) return KNN_ERR_INVALID;
+    if (count > ix->m || (labels && !ix->labels)) return KNN_ERR_INVALID;   /* (more ids than live rows: a repeat) */
+    for (size_t i = 0; i < count; i++)
+        if (ids[i] < 1 || (size_t)ids[i] > ix->last_id) return KNN_ERR_INVALID;
+    /* the plan, on the host alone (knn_update_plan.h) */
+    knn_up_plan_t pl;
+    const int prc = knn_up_plan(&pl, ix->ids, ix->m, ix->cap, ids, count);
+    if (prc) return prc == KNN_UP_NOMEM ? KNN_ERR_NOMEM : KNN_ERR_INVALID;
+    /* every allocation and upload in front of the first overwritten row: up
+     * to there a failure leaves the index as it was */
+    int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+    void *d_X = NULL;
+    int32_t *d_list = NULL;
+    if (!rc && !(flags & KNN_INDEX_DEVICE_SRC)) rc = upload(&d_X, X, count * ix->n * knn_src_esize(src_dtype));
+    if (!rc && hipMalloc((void **)&d_list, 2 * count * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc && (hipMemcpy(d_list, pl.pos, count * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d_list + count, pl.srow, count * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess))
+        rc = KNN_ERR_HIP;
+    if (rc) {
+        hipFree(d_X);
+        hipFree(d_list);
+        knn_up_plan_free(&pl);
+        return rc;
+    }
+    const void *src = (flags & KNN_INDEX_DEVICE_SRC) ? X : d_X;
+    /* knn_index_add's two parts for the listed rows: the element rows and the
+     * touched blocks' meta, one wait, the corpus meta, the byte rows while it
+     * still allows them.  From here on a failure leaves rows half written:
+     * KNN_ERR_HIP, and the index is fit only for knn_index_destroy. */
+    rc = update_rows(ix, &pl, d_list, src, layout, src_dtype, 0);
+    if (!rc) rc = stream_wait();
+    double cmeta[KNN_META_DOUBLES];
+    memcpy(cmeta, ix->cmeta, sizeof(cmeta));
+    int keep_s8 = 0;
+    if (!rc) {
+        for (size_t r = 0; r < pl.nruns; r++) meta_max(cmeta, ix->chm + pl.runs[r].blk * KNN_META_DOUBLES, 1);
+        keep_s8 = ix->have_s8 && knn_s8_spec_ok(cmeta, ix->n, ix->dtype);
+        if (keep_s8) rc = update_rows(ix, &pl, d_list, src, layout, src_dtype, 1);
+    }
+    /* the scatters have read the source and the lists before the call returns */
+    if (!rc) rc = stream_wait();
+    else hipStreamSynchronize(NULL);
+    hipFree(d_X);
+    hipFree(d_list);
+    if (rc) {
+        knn_up_plan_free(&pl);
+        return KNN_ERR_HIP;
+    }
+    if (ix->have_s8 && !keep_s8) {
+        /* a value outside the byte image arrived: the element path from now on */
+        for (size_t b = 0; b < ix->nblk; b++) {
+            hipFree(ix->s8[b]);
+            ix->s8[b] = NULL;
+        }
+        ix->have_s8 = 0;
+    }
+    if (labels)
+        for (size_t i = 0; i < count; i++) ix->labels[ids[i] - 1] = labels[i];
+    memcpy(ix->cmeta, cmeta, sizeof(cmeta));
+    knn_up_plan_free(&pl);
     return KNN_OK;
 }
 

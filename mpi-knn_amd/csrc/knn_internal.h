@@ -213,6 +213,15 @@ int knn_launch_append(void *blk, int dtype, size_t cap, size_t row0, size_t rows
                       int src_dtype, size_t ld, int layout, void *stream);
 int knn_launch_append_s8(void *dst, int dtype, size_t cap, size_t row0, size_t rows, size_t n, const void *src,
                          int src_dtype, size_t ld, int layout, void *stream);
+/* listed rows of a block / byte block packed before (knn_block_scatter_dt /
+ * knn_block_scatter_s8): item i < rows reads row srow[i] (NULL: i) of a
+ * src_rows-row source and writes block row pos[i] (device lists); otherwise an
+ * append: no meta memset, grids over `rows` */
+int knn_launch_scatter(void *blk, int dtype, size_t cap, const int32_t *pos, const int32_t *srow, size_t rows,
+                       size_t n, const void *src, size_t src_rows, int src_dtype, size_t ld, int layout, void *stream);
+int knn_launch_scatter_s8(void *dst, int dtype, size_t cap, const int32_t *pos, const int32_t *srow, size_t rows,
+                          size_t n, const void *src, size_t src_rows, int src_dtype, size_t ld, int layout,
+                          void *stream);
 /* knn_pack.hip: block row row0 + i of dst <- row list[i] of src, i < rows
  * (knn_block_gather_dt / knn_block_gather_s8): element rows and norms bit for
  * bit; byte rows verbatim, their norm words made again for the new row.  Only

@@ -28,10 +28,54 @@
 //   split rows: rows_pad rows of round_up(n, 32) * 4 bytes: per 32 features,
 //       32 halves hi then 32 halves lo.
 //
-// Pack and append are one launch path (launch_pack, launch_pack8): an append
-// runs the kernels' APPEND instantiations over `rows` instead of rows_pad, at
-// row0, without zeroing the meta first.
+// Pack, append and scatter are one launch path (launch_pack, launch_pack8): an
+// append runs the kernels' KNN_APPEND instantiations over `rows` instead of
+// rows_pad, at row0, without zeroing the meta first; a scatter runs the
+// KNN_SCATTER ones the same way, with a listed block row (and source row) for
+// every work item instead of row0.
 #include "knn_device.h"
+
+// The three forms of every pack kernel (its MODE argument) and where their
+// rows go (its last argument): a pack's and an append's first block row (0 in a
+// pack: the argument is not read), a scatter's lists.
+enum { KNN_PACK = 0, KNN_APPEND = 1, KNN_SCATTER = 2 };
+template <int MODE>
+struct knn_dst_t {
+    size_t row0;
+};
+template <>
+struct knn_dst_t<KNN_SCATTER> {
+    const int *pos;    // item i writes block row pos[i]; outside [0, cap): writes nothing
+    const int *srow;   // and reads source row srow[i] (NULL: i); outside [0, src_rows): no row at all
+    int src_rows, cap;
+};
+template <int MODE>
+__device__ __forceinline__ size_t knn_dst_row0(const knn_dst_t<MODE> &d)
+{
+    if constexpr (MODE == KNN_SCATTER) return 0;
+    else return d.row0;
+}
+// Item i of a scatter.  In: live = i < rows.  Out: live, it has a source row,
+// sr; wr, it is written, to block row dr.  (An item without a source row is
+// not written; one with a source row and no block row still reaches the meta.)
+__device__ __forceinline__ void knn_scatter_item(const knn_dst_t<KNN_SCATTER> &d, size_t i, bool &live, size_t &sr,
+                                                 size_t &dr, bool &wr)
+{
+    const int s = !live ? -1 : d.srow ? d.srow[i] : i < (size_t)d.src_rows ? (int)i : -1;
+    const int p = live ? d.pos[i] : -1;
+    live = (unsigned)s < (unsigned)d.src_rows;
+    sr = live ? (size_t)s : 0;
+    wr = live && (unsigned)p < (unsigned)d.cap;
+    dr = wr ? (size_t)p : 0;
+}
+// the block rows of a workgroup's 64 items, -1 where none is written (the
+// column kernels' SCATTER form: the thread that stores a row is not the one
+// that read its item)
+__device__ __forceinline__ int *knn_scatter_rows64()
+{
+    __shared__ int dp[64];
+    return dp;
+}
 
 // ---------------------------------------------------------------------------
 // Packing (blk:100-109): src (S = fp64, fp32 or unsigned char; col-major, ld >= rows |
@@ -44,8 +88,8 @@
 // ---------------------------------------------------------------------------
 // The meta words a lane accumulates, in two forms that compute the same
 // values.  SEL = false, the branches, serves the pack instantiations
-// (APPEND = false), whose code was tuned and measured with it.  SEL = true,
-// every update a select, serves the APPEND instantiations: there the
+// (MODE = KNN_PACK), whose code was tuned and measured with it.  SEL = true,
+// every update a select, serves the APPEND and SCATTER instantiations: there the
 // compiler ends the branches in a store through a selected address, which
 // keeps the struct in scratch memory, 24 bytes a lane; as selects it stays in
 // registers.  One form for both would change the pack kernels' code.
@@ -116,41 +160,69 @@ __device__ __forceinline__ void knn_meta_flush(const A &a, double mnorm, double 
 // atomicMax'ed into the words already there.  A row is summed by the same
 // lanes in the same order wherever it lands, so pack + appends write the
 // bytes one pack of all the rows writes.
-template <typename T, typename S, bool APPEND>
+//
+// SCATTER (knn_block_scatter_dt / _s8, every pack kernel below): an append
+// whose work item i reads source row srow[i] (i without a list) of a src_rows-row
+// source and lands at block row pos[i] -- rows given new values in place.  The
+// same lanes sum a row in the same order whichever source row it is and
+// wherever it lands, so a block scattered into is, outside its meta, the block
+// one pack of the updated array writes.
+template <typename T, typename S, int MODE>
 __global__ __launch_bounds__(256) void k_pack_col(T *__restrict__ blk, size_t rows, size_t rows_pad, int n,
-                                                  int n_pad, const S *__restrict__ src, size_t ld, size_t row0)
+                                                  int n_pad, const S *__restrict__ src, size_t ld,
+                                                  const knn_dst_t<MODE> dst)
 {
+    constexpr bool SCATTER = MODE == KNN_SCATTER;
     __shared__ T tile[64][65];
     __shared__ double part[4][64];
     T *norms = blk + rows_pad * (size_t)n_pad;
     double *meta = (double *)(norms + rows_pad);
-    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;   // rows written; the first one's block row
+    const size_t lim = MODE != KNN_PACK ? rows : rows_pad;   // rows written; the first one's block row
+    size_t d0 = 0;
+    if constexpr (MODE == KNN_APPEND) d0 = dst.row0;
     const size_t i0 = (size_t)blockIdx.x * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const size_t i = i0 + tx;
-    knn_meta_acc_t<APPEND> ma;
+    size_t si = i;          // the item's source row
+    bool live = i < rows;   // it has one
+    int *dp = nullptr;
+    if constexpr (SCATTER) {
+        size_t dr;
+        bool wr;
+        knn_scatter_item(dst, i, live, si, dr, wr);
+        dp = knn_scatter_rows64();
+        if (ty == 0) dp[tx] = wr ? (int)dr : -1;   // (read behind the loop's first barrier)
+    }
+    knn_meta_acc_t<MODE != KNN_PACK> ma;
     double s = 0.0;
     for (int j0 = 0; j0 < n_pad; j0 += 64) {
 #pragma unroll 4
         for (int jj = ty; jj < 64; jj += 4) {
             const int j = j0 + jj;
-            const T v = (i < rows && j < n) ? (T)src[i + (size_t)j * ld] : (T)0;
+            const T v = (live && j < n) ? (T)src[si + (size_t)j * ld] : (T)0;
             tile[jj][tx] = v;
             ma.add((double)v, s);
         }
         __syncthreads();
         const int j = j0 + tx;
 #pragma unroll 4
-        for (int ii = ty; ii < 64; ii += 4)
-            if (i0 + ii < lim && j < n_pad) blk[(d0 + i0 + ii) * n_pad + j] = tile[tx][ii];
+        for (int ii = ty; ii < 64; ii += 4) {
+            if constexpr (SCATTER) {
+                if (dp[ii] >= 0 && j < n_pad) blk[(size_t)dp[ii] * n_pad + j] = tile[tx][ii];
+            } else if (i0 + ii < lim && j < n_pad)
+                blk[(d0 + i0 + ii) * n_pad + j] = tile[tx][ii];
+        }
         __syncthreads();
     }
     part[ty][tx] = s;
     __syncthreads();
     double mnorm = 0.0;
-    if (ty == 0 && i < lim) {
+    if (ty == 0 && (SCATTER ? live : i < lim)) {
         const double nr = (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
-        norms[d0 + i] = (T)nr;
+        if constexpr (SCATTER) {
+            if (dp[tx] >= 0) norms[dp[tx]] = (T)nr;
+        } else
+            norms[d0 + i] = (T)nr;
         if (nr == nr) mnorm = nr;
         else ma.nonfin = 1.0;
     }
@@ -190,12 +262,17 @@ __device__ __forceinline__ int knn_spec8(T v)
 // that; rejected data is packed again from elements).
 // (Issuing the next tile's loads before converting this one -- 32 in
 // flight at RW = 64 -- measured slower: 106 -> 130 us for MNIST, rocprofv3.)
-template <typename T, typename S, int RW, bool APPEND>
+template <typename T, typename S, int RW, int MODE>
 __global__ __launch_bounds__(256) void k_pack8_col(signed char *__restrict__ dst, size_t rows, size_t rows_pad,
-                                                   int n, int rs, const S *__restrict__ src, size_t ld, size_t row0)
+                                                   int n, int rs, const S *__restrict__ src, size_t ld,
+                                                   const knn_dst_t<MODE> to)
 {
+    constexpr bool SCATTER = MODE == KNN_SCATTER;
+    static_assert(!SCATTER || RW == 64, "knn_scatter_rows64");
     constexpr int CG = 256 / RW;      // column groups
-    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
+    const size_t lim = MODE != KNN_PACK ? rows : rows_pad;
+    size_t d0 = 0;
+    if constexpr (MODE == KNN_APPEND) d0 = to.row0;
     constexpr int NE = 64 / CG;       // loads a thread a tile
     __shared__ unsigned char tb[64][RW + 4];   // [column of the tile][row]
     __shared__ double part[CG][RW];
@@ -205,9 +282,18 @@ __global__ __launch_bounds__(256) void k_pack8_col(signed char *__restrict__ dst
     const size_t i0 = (size_t)blockIdx.x * RW;
     const int tx = threadIdx.x % RW, ty = threadIdx.x / RW;
     const size_t i = i0 + tx;
-    const bool live = i < rows;
+    bool live = i < rows;   // the item has a source row
     const S *xp = src + (live ? i : 0);
-    knn_meta_acc_t<APPEND> ma;
+    int *dp = nullptr;
+    if constexpr (SCATTER) {
+        size_t sr, dr;
+        bool wr;
+        knn_scatter_item(to, i, live, sr, dr, wr);
+        xp = src + sr;
+        dp = knn_scatter_rows64();
+        if (ty == 0) dp[tx] = wr ? (int)dr : -1;   // (read behind the loop's first barrier)
+    }
+    knn_meta_acc_t<MODE != KNN_PACK> ma;
     double s = 0.0;
     unsigned si = 0u;
     for (int j0 = 0; j0 < rs; j0 += 64) {
@@ -228,21 +314,25 @@ __global__ __launch_bounds__(256) void k_pack8_col(signed char *__restrict__ dst
         __syncthreads();
         // row r = t / 4: 16 bytes at column 16 (t % 4) of the tile
         const int r = threadIdx.x >> 2, c0 = 16 * (threadIdx.x & 3);
-        if (r < RW && i0 + r < lim && j0 + c0 < rs) {
+        auto put = [&](size_t dr) {   // item i0 + r to block row dr
             unsigned w4[4];
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 w4[q] = (unsigned)tb[c0 + 4 * q][r] | ((unsigned)tb[c0 + 4 * q + 1][r] << 8) |
                         ((unsigned)tb[c0 + 4 * q + 2][r] << 16) | ((unsigned)tb[c0 + 4 * q + 3][r] << 24);
-            *(knn_v4i *)(dst + (d0 + i0 + r) * (size_t)rs + j0 + c0) = (knn_v4i){(int)w4[0], (int)w4[1], (int)w4[2], (int)w4[3]};
-        }
+            *(knn_v4i *)(dst + dr * (size_t)rs + j0 + c0) = (knn_v4i){(int)w4[0], (int)w4[1], (int)w4[2], (int)w4[3]};
+        };
+        if constexpr (SCATTER) {
+            if (dp[r] >= 0 && j0 + c0 < rs) put((size_t)dp[r]);
+        } else if (r < RW && i0 + r < lim && j0 + c0 < rs)
+            put(d0 + i0 + r);
         __syncthreads();
     }
     part[ty][tx] = s;
     ipart[ty][tx] = si;
     __syncthreads();
     double mnorm = 0.0;
-    if (ty == 0 && i < lim) {
+    if (ty == 0 && (SCATTER ? live : i < lim)) {
         double nr = 0.0;
         unsigned ni = 0u;
         if constexpr (CG == 4) {
@@ -255,39 +345,53 @@ __global__ __launch_bounds__(256) void k_pack8_col(signed char *__restrict__ dst
                 ni += ipart[q][tx];
             }
         }
-        norms[i8_norm_pos((int)(d0 + i))] = i8_norm_word((int)(d0 + i), (int)ni, rs);
-        norms[rows_pad + i8_norm_pos((int)(d0 + i))] = i8_init_word((int)ni, rs);
+        if constexpr (SCATTER) {
+            if (dp[tx] >= 0) {
+                norms[i8_norm_pos(dp[tx])] = i8_norm_word(dp[tx], (int)ni, rs);
+                norms[rows_pad + i8_norm_pos(dp[tx])] = i8_init_word((int)ni, rs);
+            }
+        } else {
+            norms[i8_norm_pos((int)(d0 + i))] = i8_norm_word((int)(d0 + i), (int)ni, rs);
+            norms[rows_pad + i8_norm_pos((int)(d0 + i))] = i8_init_word((int)ni, rs);
+        }
         if (nr == nr) mnorm = nr;
         else ma.nonfin = 1.0;
     }
     knn_meta_flush(ma, mnorm, meta);
-    if (!APPEND && blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;   // (an append finds it set)
+    if (MODE == KNN_PACK && blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;   // (an append finds it set)
 }
 
 // row-major source: one wave per row, lane l converts the 8-element groups
 // l, l + 64, ... (one 8-byte store each); VEC: 16-byte-aligned rows, whole
 // groups read as 16-byte vectors (sift: 0.68 ms for 512 MB with scalar loads)
-template <typename T, typename S, bool VEC, bool APPEND>
+template <typename T, typename S, bool VEC, int MODE>
 __global__ __launch_bounds__(256) void k_pack8_row(signed char *__restrict__ dst, size_t rows, size_t rows_pad,
-                                                   int n, int rs, const S *__restrict__ src, size_t ld, size_t row0)
+                                                   int n, int rs, const S *__restrict__ src, size_t ld,
+                                                   const knn_dst_t<MODE> to)
 {
     typedef typename std::conditional<sizeof(S) == 8, dbl2, flt4>::type svec_t;
-    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
+    constexpr bool SCATTER = MODE == KNN_SCATTER;
+    const size_t lim = MODE != KNN_PACK ? rows : rows_pad;
+    size_t d0 = 0;
+    if constexpr (MODE == KNN_APPEND) d0 = to.row0;
     constexpr int SV = 16 / (int)sizeof(S);
     int *norms = (int *)(dst + rows_pad * (size_t)rs);
     double *meta = (double *)(norms + 2 * rows_pad);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int ng = rs / 8;
-    knn_meta_acc_t<APPEND> ma;
+    knn_meta_acc_t<MODE != KNN_PACK> ma;
     double mnorm = 0.0;
     for (size_t r = (size_t)blockIdx.x * 4 + wave; r < lim; r += (size_t)gridDim.x * 4) {
         double s = 0.0;
         unsigned si = 0u;
-        const S *x = src + r * ld;
+        size_t sr = r, dr = d0 + r;   // the item's source row and block row
+        bool live = r < rows, wr = true;
+        if constexpr (SCATTER) knn_scatter_item(to, r, live, sr, dr, wr);
+        const S *x = src + sr * ld;
         for (int g = lane; g < ng; g += 64) {
             unsigned lo = 0u, hi = 0u;
             S sv[8];
-            if (VEC && r < rows && 8 * g + 8 <= n) {
+            if (VEC && live && 8 * g + 8 <= n) {
 #pragma unroll
                 for (int q = 0; q < 8 / SV; q++) {
                     const svec_t w = *(const svec_t *)(x + 8 * g + SV * q);
@@ -296,12 +400,12 @@ __global__ __launch_bounds__(256) void k_pack8_row(signed char *__restrict__ dst
                 }
             } else {
 #pragma unroll
-                for (int e = 0; e < 8; e++) sv[e] = (r < rows && 8 * g + e < n) ? x[8 * g + e] : (S)0;
+                for (int e = 0; e < 8; e++) sv[e] = (live && 8 * g + e < n) ? x[8 * g + e] : (S)0;
             }
 #pragma unroll
             for (int e = 0; e < 8; e++) {
                 const int j = 8 * g + e;
-                const bool in = r < rows && j < n;
+                const bool in = live && j < n;
                 const T v = in ? (T)sv[e] : (T)0;
                 ma.add((double)v, s);
                 const int xi = in ? knn_spec8(v) : 0;
@@ -310,21 +414,21 @@ __global__ __launch_bounds__(256) void k_pack8_row(signed char *__restrict__ dst
                 else hi |= ((unsigned)xi & 0xffu) << (8 * (e - 4));
             }
             typedef unsigned u2 __attribute__((ext_vector_type(2)));
-            *(u2 *)(dst + (d0 + r) * (size_t)rs + 8 * g) = (u2){lo, hi};
+            if (!SCATTER || wr) *(u2 *)(dst + dr * (size_t)rs + 8 * g) = (u2){lo, hi};
         }
         for (int off = 32; off > 0; off >>= 1) {
             s += __shfl_xor(s, off);
             si += (unsigned)__shfl_xor((int)si, off);
         }
-        if (lane == 0) {
-            norms[i8_norm_pos((int)(d0 + r))] = i8_norm_word((int)(d0 + r), (int)si, rs);
-            norms[rows_pad + i8_norm_pos((int)(d0 + r))] = i8_init_word((int)si, rs);
+        if (lane == 0 && (!SCATTER || wr)) {
+            norms[i8_norm_pos((int)dr)] = i8_norm_word((int)dr, (int)si, rs);
+            norms[rows_pad + i8_norm_pos((int)dr)] = i8_init_word((int)si, rs);
         }
         if (s == s) mnorm = s > mnorm ? s : mnorm;
         else ma.nonfin = 1.0;
     }
     knn_meta_flush(ma, mnorm, meta);
-    if (!APPEND && blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
+    if (MODE == KNN_PACK && blockIdx.x == 0 && threadIdx.x == 0) meta[KNN_META_S8] = 1.0;
 }
 
 // row-major KNN_U8 source: the byte image is x ^ 0x80 (x - 128 as int8), so a
@@ -341,13 +445,15 @@ __global__ __launch_bounds__(256) void k_pack8_row(signed char *__restrict__ dst
 // past n (ld > n), byte by byte.
 typedef unsigned knn_v4u __attribute__((ext_vector_type(4)));
 // APPEND: row groups are cut at `rows`, which a group may straddle: the rows
-// past it are neither stored nor given norm words.
-template <bool VEC, bool APPEND>
+// past it are neither stored nor given norm words.  SCATTER: the same for its
+// items; each row group looks its source and block rows up once.
+template <bool VEC, int MODE>
 __global__ __launch_bounds__(256) void k_pack8_row_u8(signed char *__restrict__ dst, size_t rows, size_t rows_pad,
                                                       int n, int rs, const unsigned char *__restrict__ src,
-                                                      size_t ld, int lpr, size_t row0)
+                                                      size_t ld, int lpr, const knn_dst_t<MODE> to)
 {
-    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
+    constexpr bool APPEND = MODE != KNN_PACK, SCATTER = MODE == KNN_SCATTER;
+    const size_t lim = APPEND ? rows : rows_pad, d0 = MODE == KNN_APPEND ? knn_dst_row0(to) : 0;
     int *norms = (int *)(dst + rows_pad * (size_t)rs);
     double *meta = (double *)(norms + 2 * rows_pad);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -364,24 +470,36 @@ __global__ __launch_bounds__(256) void k_pack8_row_u8(signed char *__restrict__ 
          rb += (size_t)gridDim.x * 4 * U * rpw) {
         knn_v4u v[U];
         bool full[U];
+        // SCATTER: item r's source row, block row, and whether it has the one and is written to the other
+        size_t srs[SCATTER ? U : 1], drs[SCATTER ? U : 1];
+        bool lvs[SCATTER ? U : 1], wrs[SCATTER ? U : 1];
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const size_t r = rb + (size_t)u * rpw + sub;
-            full[u] = VEC && has && r < rows && 16 * g + 16 <= n;
             v[u] = (knn_v4u){0u, 0u, 0u, 0u};
-            if (full[u]) v[u] = *(const knn_v4u *)(src + r * ld + 16 * g);
+            if constexpr (SCATTER) {
+                lvs[u] = r < rows;
+                knn_scatter_item(to, r, lvs[u], srs[u], drs[u], wrs[u]);
+                full[u] = VEC && has && lvs[u] && 16 * g + 16 <= n;
+                if (full[u]) v[u] = *(const knn_v4u *)(src + srs[u] * ld + 16 * g);
+            } else {
+                full[u] = VEC && has && r < rows && 16 * g + 16 <= n;
+                if (full[u]) v[u] = *(const knn_v4u *)(src + r * ld + 16 * g);
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; u++) {
             if (rb + (size_t)u * rpw >= lim) break;
             const size_t r = rb + (size_t)u * rpw + sub;
-            const bool wr = !APPEND || r < rows;
+            const bool wr = SCATTER ? wrs[SCATTER ? u : 0] : !APPEND || r < rows;
+            const bool lv = SCATTER ? lvs[SCATTER ? u : 0] : r < rows;
+            const size_t sr = SCATTER ? srs[SCATTER ? u : 0] : r, dr = SCATTER ? drs[SCATTER ? u : 0] : d0 + r;
             // bytes, and 0xff where a byte is data
             unsigned w[4] = {v[u][0], v[u][1], v[u][2], v[u][3]};
             const unsigned fm = full[u] ? 0xffffffffu : 0u;
             unsigned live[4] = {fm, fm, fm, fm};
-            if (!full[u] && has && r < rows) {
-                const unsigned char *x = src + r * ld + 16 * g;
+            if (!full[u] && has && lv) {
+                const unsigned char *x = src + sr * ld + 16 * g;
 #pragma unroll
                 for (int e = 0; e < 16; e++)
                     if (16 * g + e < n) {
@@ -402,14 +520,14 @@ __global__ __launch_bounds__(256) void k_pack8_row_u8(signed char *__restrict__ 
                 }
                 w[q] = (w[q] ^ 0x80808080u) & live[q];
             }
-            if (has && wr) *(knn_v4u *)(dst + (d0 + r) * (size_t)rs + 16 * g) = (knn_v4u){w[0], w[1], w[2], w[3]};
+            if (has && wr) *(knn_v4u *)(dst + dr * (size_t)rs + 16 * g) = (knn_v4u){w[0], w[1], w[2], w[3]};
             for (int off = lpr >> 1; off > 0; off >>= 1) {
                 sx += (unsigned)__shfl_xor((int)sx, off);
                 si += (unsigned)__shfl_xor((int)si, off);
             }
             if (g == 0 && wr) {
-                norms[i8_norm_pos((int)(d0 + r))] = i8_norm_word((int)(d0 + r), (int)si, rs);
-                norms[rows_pad + i8_norm_pos((int)(d0 + r))] = i8_init_word((int)si, rs);
+                norms[i8_norm_pos((int)dr)] = i8_norm_word((int)dr, (int)si, rs);
+                norms[rows_pad + i8_norm_pos((int)dr)] = i8_init_word((int)si, rs);
             }
             mnorm = sx > mnorm ? sx : mnorm;
         }
@@ -421,27 +539,34 @@ __global__ __launch_bounds__(256) void k_pack8_row_u8(signed char *__restrict__ 
 }
 
 // Row-major source: one wave per row (lane-strided features, butterfly sum).
-template <typename T, typename S, bool APPEND>
+template <typename T, typename S, int MODE>
 __global__ __launch_bounds__(256) void k_pack_row(T *__restrict__ blk, size_t rows, size_t rows_pad, int n,
-                                                  int n_pad, const S *__restrict__ src, size_t ld, size_t row0)
+                                                  int n_pad, const S *__restrict__ src, size_t ld,
+                                                  const knn_dst_t<MODE> dst)
 {
+    constexpr bool SCATTER = MODE == KNN_SCATTER;
     T *norms = blk + rows_pad * (size_t)n_pad;
     double *meta = (double *)(norms + rows_pad);
-    const size_t lim = APPEND ? rows : rows_pad, d0 = APPEND ? row0 : 0;
+    const size_t lim = MODE != KNN_PACK ? rows : rows_pad;
+    size_t d0 = 0;
+    if constexpr (MODE == KNN_APPEND) d0 = dst.row0;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    knn_meta_acc_t<APPEND> ma;
+    knn_meta_acc_t<MODE != KNN_PACK> ma;
     double mnorm = 0.0;
     for (size_t i = (size_t)blockIdx.x * 4 + wave; i < lim; i += (size_t)gridDim.x * 4) {
         double s = 0.0;
-        const S *x = src + i * ld;
-        T *o = blk + (d0 + i) * (size_t)n_pad;
+        size_t sr = i, dr = d0 + i;   // the item's source row and block row
+        bool live = i < rows, wr = true;
+        if constexpr (SCATTER) knn_scatter_item(dst, i, live, sr, dr, wr);
+        const S *x = src + sr * ld;
+        T *o = blk + dr * (size_t)n_pad;
         for (int j = lane; j < n_pad; j += 64) {
-            const T v = (i < rows && j < n) ? (T)x[j] : (T)0;
-            o[j] = v;
+            const T v = (live && j < n) ? (T)x[j] : (T)0;
+            if (!SCATTER || wr) o[j] = v;
             ma.add((double)v, s);
         }
         for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) norms[d0 + i] = (T)s;
+        if (lane == 0 && (!SCATTER || wr)) norms[dr] = (T)s;
         if (s == s) mnorm = s > mnorm ? s : mnorm;
         else ma.nonfin = 1.0;
     }
@@ -449,13 +574,14 @@ __global__ __launch_bounds__(256) void k_pack_row(T *__restrict__ blk, size_t ro
 }
 
 // ---------------------------------------------------------------------------
-// Launchers of the pack kernels.  A pack and an append (rows row0 .. of a
-// block packed before, knn_block_append_dt / _s8) take the same path and
-// differ in the kernels' APPEND argument, in the rows a grid covers (gr:
-// rows_pad for a pack, which also zeroes the padding rows; `rows` for an
-// append), in row0, and in the meta: a pack zeroes it first, an append leaves
-// it (the meta is max(old, new rows); the byte kernels set KNN_META_S8 in a
-// pack only).
+// Launchers of the pack kernels.  A pack, an append (rows row0 .. of a
+// block packed before, knn_block_append_dt / _s8) and a scatter (listed rows of
+// one, knn_block_scatter_dt / _s8) take the same path and
+// differ in the kernels' MODE argument, in the rows a grid covers (gr:
+// rows_pad for a pack, which also zeroes the padding rows; `rows` for the
+// other two), in where the rows go (knn_pack_to_t), and in the meta: a pack
+// zeroes it first, the others leave it (the meta is max(old, new rows); the
+// byte kernels set KNN_META_S8 in a pack only).
 // ---------------------------------------------------------------------------
 // a bool as a template argument: f(std::true_type()) or f(std::false_type())
 template <typename F>
@@ -463,51 +589,77 @@ static int with_bool(bool b, F f)
 {
     return b ? f(std::true_type()) : f(std::false_type());
 }
+// where a launch's rows go: the mode, an append's row0, a scatter's lists
+// (device arrays of `rows` entries; srow nullable) and its source's row count
+struct knn_pack_to_t {
+    int mode;
+    size_t row0;
+    const int32_t *pos, *srow;
+    size_t src_rows;
+};
+// the mode as a template argument, and the kernels' last argument for it
+template <typename F>
+static int with_mode(int mode, F f)
+{
+    if (mode == KNN_PACK) return f(std::integral_constant<int, KNN_PACK>());
+    if (mode == KNN_APPEND) return f(std::integral_constant<int, KNN_APPEND>());
+    return f(std::integral_constant<int, KNN_SCATTER>());
+}
+template <int MODE>
+static knn_dst_t<MODE> dst_arg(const knn_pack_to_t &to, size_t cap)
+{
+    if constexpr (MODE == KNN_SCATTER) return knn_dst_t<MODE>{to.pos, to.srow, (int)to.src_rows, (int)cap};
+    else return knn_dst_t<MODE>{to.row0};
+}
 
 // grid of the kernels that give a wave a row at a time: 4 rows a workgroup
 static unsigned grid_wave_rows(size_t gr) { return (unsigned)((gr + 3) / 4 < 8192 ? (gr + 3) / 4 : 8192); }
 
 template <typename T, typename S>
 static int launch_pack(T *blk, size_t cap, size_t rows, size_t n, const S *src, size_t ld, int layout,
-                       hipStream_t s, bool append, size_t row0)
+                       hipStream_t s, const knn_pack_to_t &to)
 {
     constexpr int dt = sizeof(T) == 8 ? KNN_F64 : KNN_F32;
     const size_t rp = knn_rows_pad(cap), np = knn_n_pad_dt(n, dt);
-    const size_t gr = append ? rows : rp;
+    const bool pack = to.mode == KNN_PACK;
+    const size_t gr = pack ? rp : rows;
     double *meta = (double *)(blk + rp * np + rp);
-    if (!append && hipMemsetAsync(meta, 0, KNN_META_DOUBLES * sizeof(double), s) != hipSuccess)
+    if (pack && hipMemsetAsync(meta, 0, KNN_META_DOUBLES * sizeof(double), s) != hipSuccess)
         return KNN_ERR_HIP;
-    return with_bool(append, [&](auto ap) {
-        constexpr bool AP = decltype(ap)::value;
+    return with_mode(to.mode, [&](auto md) {
+        constexpr int MD = decltype(md)::value;
         if (layout == KNN_COLMAJOR)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_col<T, S, AP>), dim3((unsigned)((gr + 63) / 64)), dim3(256), 0,
-                               s, blk, rows, rp, (int)n, (int)np, src, ld, row0);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_col<T, S, MD>), dim3((unsigned)((gr + 63) / 64)), dim3(256), 0,
+                               s, blk, rows, rp, (int)n, (int)np, src, ld, dst_arg<MD>(to, cap));
         else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_row<T, S, AP>), dim3(grid_wave_rows(gr)), dim3(256), 0, s, blk,
-                               rows, rp, (int)n, (int)np, src, ld, row0);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_row<T, S, MD>), dim3(grid_wave_rows(gr)), dim3(256), 0, s, blk,
+                               rows, rp, (int)n, (int)np, src, ld, dst_arg<MD>(to, cap));
         return hip_status();
     });
 }
 
 template <typename T, typename S>
 static int launch_pack8(signed char *dst, size_t cap, size_t rows, size_t n, const S *src, size_t ld, int layout,
-                        hipStream_t s, bool append, size_t row0)
+                        hipStream_t s, const knn_pack_to_t &to)
 {
     const size_t rp = knn_rows_pad(cap), rs = knn_s8_rs(n);
-    const size_t gr = append ? rows : rp;
+    const bool pack = to.mode == KNN_PACK;
+    const size_t gr = pack ? rp : rows;
     double *meta = (double *)(dst + knn_s8_meta_offset(cap, n));
-    if (!append && hipMemsetAsync(meta, 0, KNN_META_DOUBLES * sizeof(double), s) != hipSuccess) return KNN_ERR_HIP;
+    if (pack && hipMemsetAsync(meta, 0, KNN_META_DOUBLES * sizeof(double), s) != hipSuccess) return KNN_ERR_HIP;
     // row-major: rows that start on 16 bytes are read as vectors (ld % 16 for
     // a byte source).  (An append's source that starts at row0 * n of a larger
-    // array is rarely 16-byte aligned.)
+    // array is rarely 16-byte aligned.)  (A scatter reads any row of its
+    // source: the same condition holds for each.)
     const bool vec = ((uintptr_t)src % 16 == 0) && (ld * sizeof(S)) % 16 == 0;
-    return with_bool(append, [&](auto ap) {
+    return with_mode(to.mode, [&](auto md) {
         return with_bool(vec, [&](auto vc) -> int {
-            constexpr bool AP = decltype(ap)::value, VEC = decltype(vc)::value;
+            constexpr int MD = decltype(md)::value;
+            constexpr bool VEC = decltype(vc)::value;
             if (layout == KNN_COLMAJOR) {
                 // (32-row workgroups, twice as many: 107.5 against 105.7 us for MNIST)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_col<T, S, 64, AP>), dim3((unsigned)((gr + 63) / 64)),
-                                   dim3(256), 0, s, dst, rows, rp, (int)n, (int)rs, src, ld, row0);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_col<T, S, 64, MD>), dim3((unsigned)((gr + 63) / 64)),
+                                   dim3(256), 0, s, dst, rows, rp, (int)n, (int)rs, src, ld, dst_arg<MD>(to, cap));
             } else if constexpr (sizeof(S) == 1) {
                 // KNN_U8: lpr lanes a row (a power of two >= rs / 16), 64 / lpr rows a wave
                 int lpr = 1;
@@ -517,11 +669,11 @@ static int launch_pack8(signed char *dst, size_t cap, size_t rows, size_t n, con
                 // every workgroup ends in six atomics on the same meta words
                 const size_t nw = (gr * lpr + 255) / 256;
                 const unsigned nb = (unsigned)((nw + 3) / 4 < 2048 ? (nw + 3) / 4 : 2048);
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row_u8<VEC, AP>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
-                                   (int)n, (int)rs, src, ld, lpr, row0);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row_u8<VEC, MD>), dim3(nb), dim3(256), 0, s, dst, rows, rp,
+                                   (int)n, (int)rs, src, ld, lpr, dst_arg<MD>(to, cap));
             } else {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, VEC, AP>), dim3(grid_wave_rows(gr)), dim3(256), 0,
-                                   s, dst, rows, rp, (int)n, (int)rs, src, ld, row0);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack8_row<T, S, VEC, MD>), dim3(grid_wave_rows(gr)), dim3(256), 0,
+                                   s, dst, rows, rp, (int)n, (int)rs, src, ld, dst_arg<MD>(to, cap));
             }
             return hip_status();
         });
@@ -548,34 +700,51 @@ static int pack_dispatch(int dtype, const void *src, int src_dtype, F f)
 
 // the element block (s8 = false) or the byte block of `dtype` at blk
 static int pack_any(bool s8, void *blk, int dtype, size_t cap, size_t rows, size_t n, const void *src,
-                    int src_dtype, size_t ld, int layout, void *stream, bool append, size_t row0)
+                    int src_dtype, size_t ld, int layout, void *stream, const knn_pack_to_t &to)
 {
     hipStream_t s = (hipStream_t)stream;
     return pack_dispatch(dtype, src, src_dtype, [&](auto te, auto *sp) {
         typedef decltype(te) T;
-        return s8 ? launch_pack8<T>((signed char *)blk, cap, rows, n, sp, ld, layout, s, append, row0)
-                  : launch_pack((T *)blk, cap, rows, n, sp, ld, layout, s, append, row0);
+        return s8 ? launch_pack8<T>((signed char *)blk, cap, rows, n, sp, ld, layout, s, to)
+                  : launch_pack((T *)blk, cap, rows, n, sp, ld, layout, s, to);
     });
 }
 extern "C" int knn_launch_pack(void *blk, int dtype, size_t cap, size_t rows, size_t n,
                                const void *src, int src_dtype, size_t ld, int layout, void *stream)
 {
-    return pack_any(false, blk, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, false, 0);
+    return pack_any(false, blk, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, {KNN_PACK, 0, NULL, NULL, 0});
 }
 extern "C" int knn_launch_append(void *blk, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
                                  const void *src, int src_dtype, size_t ld, int layout, void *stream)
 {
-    return pack_any(false, blk, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, true, row0);
+    return pack_any(false, blk, dtype, cap, rows, n, src, src_dtype, ld, layout, stream,
+                    {KNN_APPEND, row0, NULL, NULL, 0});
 }
 extern "C" int knn_launch_pack_s8(void *dst, int dtype, size_t cap, size_t rows, size_t n, const void *src,
                                   int src_dtype, size_t ld, int layout, void *stream)
 {
-    return pack_any(true, dst, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, false, 0);
+    return pack_any(true, dst, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, {KNN_PACK, 0, NULL, NULL, 0});
 }
 extern "C" int knn_launch_append_s8(void *dst, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
                                     const void *src, int src_dtype, size_t ld, int layout, void *stream)
 {
-    return pack_any(true, dst, dtype, cap, rows, n, src, src_dtype, ld, layout, stream, true, row0);
+    return pack_any(true, dst, dtype, cap, rows, n, src, src_dtype, ld, layout, stream,
+                    {KNN_APPEND, row0, NULL, NULL, 0});
+}
+// (cap and src_rows <= INT32_MAX: the entry points check)
+extern "C" int knn_launch_scatter(void *blk, int dtype, size_t cap, const int32_t *pos, const int32_t *srow,
+                                  size_t rows, size_t n, const void *src, size_t src_rows, int src_dtype, size_t ld,
+                                  int layout, void *stream)
+{
+    return pack_any(false, blk, dtype, cap, rows, n, src, src_dtype, ld, layout, stream,
+                    {KNN_SCATTER, 0, pos, srow, src_rows});
+}
+extern "C" int knn_launch_scatter_s8(void *dst, int dtype, size_t cap, const int32_t *pos, const int32_t *srow,
+                                     size_t rows, size_t n, const void *src, size_t src_rows, int src_dtype,
+                                     size_t ld, int layout, void *stream)
+{
+    return pack_any(true, dst, dtype, cap, rows, n, src, src_dtype, ld, layout, stream,
+                    {KNN_SCATTER, 0, pos, srow, src_rows});
 }
 
 // Ring wire form of a packed block (knn_wire_pack / knn_wire_unpack): the

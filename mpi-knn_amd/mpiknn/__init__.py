@@ -54,6 +54,7 @@ API_SYMBOLS = (
     "knn_index_create", "knn_index_query", "knn_index_info", "knn_index_destroy",
     "knn_index_add", "knn_block_append_dt", "knn_block_append_s8",
     "knn_index_remove", "knn_index_last_id", "knn_block_gather_dt", "knn_block_gather_s8",
+    "knn_index_update", "knn_block_scatter_dt", "knn_block_scatter_s8",
 )
 DTYPES = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 # a pack / index SOURCE may also be unsigned bytes (KNN_U8: never a block or search dtype)
@@ -157,6 +158,9 @@ def _load():
         "knn_index_last_id": ([p, psz], i),
         "knn_block_gather_dt": ([p, sz, sz, p, sz, p, sz, sz, i, p], i),
         "knn_block_gather_s8": ([p, sz, sz, p, sz, p, sz, sz, p], i),
+        "knn_index_update": ([p, p, sz, p, i, i, p, i], i),
+        "knn_block_scatter_dt": ([p, i, sz, p, p, sz, sz, p, sz, i, sz, i, p], i),
+        "knn_block_scatter_s8": ([p, i, sz, p, p, sz, sz, p, sz, i, sz, i, p], i),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -376,6 +380,15 @@ def block_append(d_block, cap, row0, rows, n, d_src, ld, layout, stream=0, dtype
                                    ld, layout, stream or None), "knn_block_append_dt")
 
 
+def block_scatter(d_block, cap, d_pos, d_srow, rows, n, d_src, src_rows, ld, layout, stream=0, dtype="f64",
+                  src_dtype="f64"):
+    """knn_block_scatter_dt: block row d_pos[i] of a block packed before <- row
+    d_srow[i] (0 / None: row i) of the src_rows x n device source, i < rows
+    (d_pos, d_srow: device int32 arrays; the other arguments as block_pack)."""
+    _check(lib.knn_block_scatter_dt(d_block, DTYPES[dtype], cap, d_pos, d_srow or None, rows, n, d_src, src_rows,
+                                    SRC_DTYPES[src_dtype], ld, layout, stream or None), "knn_block_scatter_dt")
+
+
 def block_gather(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, stream=0, dtype="f64"):
     """knn_block_gather_dt: block row row0 + i of d_dst <- row d_list[i] of
     d_src, i < rows (device pointers; d_list: int32 local source rows)."""
@@ -406,6 +419,13 @@ def block_append_s8(d_sblock, cap, row0, rows, n, d_src, ld, layout, stream=0, d
     """knn_block_append_s8: the same rows of a byte block packed by block_pack_s8."""
     _check(lib.knn_block_append_s8(d_sblock, DTYPES[dtype], cap, row0, rows, n, d_src, SRC_DTYPES[src_dtype], ld,
                                    layout, stream or None), "knn_block_append_s8")
+
+
+def block_scatter_s8(d_sblock, cap, d_pos, d_srow, rows, n, d_src, src_rows, ld, layout, stream=0, dtype="f64",
+                     src_dtype="f64"):
+    """knn_block_scatter_s8: the same rows of a byte block packed by block_pack_s8."""
+    _check(lib.knn_block_scatter_s8(d_sblock, DTYPES[dtype], cap, d_pos, d_srow or None, rows, n, d_src, src_rows,
+                                    SRC_DTYPES[src_dtype], ld, layout, stream or None), "knn_block_scatter_s8")
 
 
 def block_gather_s8(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, stream=0):
@@ -574,6 +594,30 @@ class Index:
         _check(lib.knn_index_remove(self._h, _ptr(a), a.size, 0, ctypes.byref(removed)), "knn_index_remove")
         self.m -= removed.value
         return removed.value
+
+    def update(self, ids, X, labels=None):
+        """knn_index_update: row i of X ((count, n), in the index's layout
+        argument; types as the constructor's X, its own) becomes the row with
+        the 1-based id ids[i], in place: ids, positions and m stay.  labels:
+        count values that replace those rows' labels, or None to leave them.
+        An id outside [1, last_id], one that is no longer live or one given
+        twice raises KnnError(ERR_INVALID) and changes nothing."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        a = np.asarray(ids).reshape(-1)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError("ids must be integers, got %s" % a.dtype)
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise KnnError(ERR_INVALID, "knn_index_update")
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        ptr, keep, rows, n, lay, src, dev = _index_source(X, self.layout, "X")
+        if n != self.n or rows != a.size:
+            raise ValueError("X must be (%d, %d), got (%d, %d)" % (a.size, self.n, rows, n))
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.float64)
+        if lab is not None and lab.shape[0] != rows:
+            raise ValueError("labels must have %d entries, got %d" % (rows, lab.shape[0]))
+        _check(lib.knn_index_update(self._h, _ptr(a), a.size, ptr, lay, src, _ptr(lab), dev), "knn_index_update")
+        del keep
 
     @property
     def last_id(self):

@@ -37,6 +37,11 @@ Legs (one a process, so two builds of the library can be run in alternation:
           byte count in the same process
   mapcost Index.query spans at every --mq on one index before and after one
           removal (the id translation at the end of the span)
+  update  Index.update of 1 and 1000 rows spread over the whole 60000-row uint8
+          index that has served one query: host wall and device span (events
+          around the call), and in the same process, on another fresh index,
+          what a user without update does for the same rows: Index.remove of
+          their ids, then Index.add of the rows (which also changes their ids)
 
 Median of --runs after --warmup, with min and max.  Each leg appends one JSON
 line to --out; --merge FILES... folds such lines into profiles/index_bench.json.
@@ -325,6 +330,52 @@ def leg_gather(knn, a):
     return out
 
 
+UPDATE_ROWS = (1, 1000)
+
+
+def leg_update(knn, a, X, Qall):
+    """every timed call meets a fresh index that has served one query; the
+    update and the remove + add pair alternate, indices made outside the timings"""
+    import numpy as np
+    import torch
+    Xs, Qs = np.ascontiguousarray(X.astype(np.uint8)), Qall[:128].astype(np.uint8)
+    extra, _ = synth_rows(knn, max(UPDATE_ROWS))
+    out = []
+
+    def timed(ix, f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        f(ix)
+        e1.record()
+        w = (time.perf_counter() - t0) * 1e3
+        e1.synchronize()
+        return w, e0.elapsed_time(e1)
+
+    for rows in UPDATE_ROWS:
+        ids = np.linspace(1, len(X), rows + 2).astype(np.int32)[1:-1] if rows > 1 else np.array([len(X) // 8], np.int32)
+        A = np.ascontiguousarray(extra[:rows].astype(np.uint8))
+        t = {name: [] for name in ("update_wall", "update_span", "pair_wall", "pair_span", "q_update", "q_pair")}
+        for i in range(a.warmup + a.runs):
+            for pair in (False, True):
+                ix = knn.Index(Xs)
+                ix.query(Qs, a.k)
+                w, sp = timed(ix, (lambda x: (x.remove(ids), x.add(A))) if pair else (lambda x: x.update(ids, A)))
+                _, s = ix.query(Qs, a.k)
+                ix.close()
+                if i >= a.warmup:
+                    t["pair_wall" if pair else "update_wall"].append(w)
+                    t["pair_span" if pair else "update_span"].append(sp)
+                    t["q_pair" if pair else "q_update"].append(s * 1e3)
+        out.append({"rows": rows, "source": "u8", "first_id": int(ids[0]), "last_id": int(ids[-1]),
+                    "update_wall": stats(t["update_wall"]), "update_span": stats(t["update_span"]),
+                    "remove_add_wall": stats(t["pair_wall"]), "remove_add_span": stats(t["pair_span"]),
+                    "first_query_after_update": stats(t["q_update"]),
+                    "first_query_after_remove_add": stats(t["q_pair"])})
+    return out
+
+
 def leg_mapcost(knn, a, X, Qall):
     import numpy as np
     rows = []
@@ -367,7 +418,7 @@ def merge(files, out, keep=False):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", choices=["query", "index", "pack", "add", "rebuild", "remove", "rebuild-survivors", "gather",
-                                     "mapcost"])
+                                     "mapcost", "update"])
     ap.add_argument("--root", default=ROOT, help="tree whose mpi-knn_amd/ is imported")
     ap.add_argument("--tag", default="this", help="name of the build in the output")
     ap.add_argument("--round", type=int, default=0)
@@ -407,6 +458,8 @@ def main():
             rec["results"] = leg_remove(mpiknn, a, X, Qall)
         elif a.leg == "mapcost":
             rec["results"] = leg_mapcost(mpiknn, a, X, Qall)
+        elif a.leg == "update":
+            rec["results"] = leg_update(mpiknn, a, X, Qall)
         else:
             rec.update(leg_index(mpiknn, a, X, Qall))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
