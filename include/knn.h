@@ -337,6 +337,47 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * in the list, labels where the index has none; KNN_ERR_UNSUPPORTED: an unknown
  * src_dtype.
  *
+ * knn_index_neighbours: the neighbours of resident rows, by id -- knn_search's
+ * all-kNN (serial:72-93) over the corpus the index holds, after any add,
+ * remove or update, with no host copy of the rows and nothing uploaded but the
+ * ids.  For each listed live id the k nearest OTHER live rows; out holds
+ * count*k records, row i those of ids[i].  Ids come in any order and may
+ * repeat (the call only reads: a repeated id gets the same records twice).
+ * ids == NULL (count must then be 0) means every live row in ascending id, m*k
+ * records: the corpus's kNN graph.  idx is the neighbour's id, as in
+ * knn_index_query after a removal; .label from the index's labels on host-out
+ * calls; semantics, ordering, arithmetic and empty slots are knn_search's.
+ * flags: 0 drops every zero distance -- the row itself and its exact
+ * duplicates, the reference's leave-one-out rule as in knn_search;
+ * KNN_QUERY_KEEP_ZERO leaves out only the row itself, and exact duplicates
+ * come back at distance 0.0, lower id first (what knn_ctx_set_keep_zero
+ * documents for in-corpus ids); KNN_INDEX_DEVICE_OUT as in knn_index_query.
+ * There is no KNN_INDEX_DEVICE_SRC: there is no source.  How: ids are mapped to
+ * positions on the host (knn_neighbours_plan.h), the query tiles are filled
+ * from the resident blocks device to device (knn_block_gather_pos_dt, and
+ * knn_block_gather_pos_s8 when the index has byte blocks and its meta passes
+ * knn_s8_spec_ok), the batch's reduced meta is the corpus meta itself, and each
+ * tile is searched as in knn_index_query, with ids past the corpus.  Under
+ * flags 0 a row's own distance is exactly 0 on every path and the rule drops
+ * it.  Under KNN_QUERY_KEEP_ZERO the engine searches k + 1 and one kernel takes
+ * the row itself out of its records (and writes the ids): records are ordered
+ * by (distance, id) and the row sits at distance 0, so if it is among the k + 1
+ * the rest are the k nearest others, and if it is not, all k + 1 are duplicates
+ * with lower ids and the first k are the answer.  So under KNN_QUERY_KEEP_ZERO
+ * k + 1 must be within the dtype's limit: k = 32 on KNN_F64 and k = 128 on
+ * KNN_F32 are KNN_ERR_UNSUPPORTED there (and served under flags 0).  The kept
+ * context is keyed by the engine's k, which is k + 1 under KNN_QUERY_KEEP_ZERO:
+ * a caller who alternates knn_index_query(k) and keep-zero neighbours(k)
+ * recreates it each time.  knn_last_search_seconds() reports the span from the
+ * gather through the last records.  A failed call leaves the index answering
+ * as before (it drops the kept query state, as knn_index_query does).
+ * KNN_ERR_INVALID, before any device call: NULL index or out, ids == NULL with
+ * count != 0, ids != NULL with count == 0, k <= 0, unknown flag bits, an id
+ * outside [1, last_id], an id that is no longer live (refused as in
+ * knn_index_update, not skipped: a missing answer row would shift every later
+ * one); KNN_ERR_UNSUPPORTED: k (k + 1 under KNN_QUERY_KEEP_ZERO) above the
+ * dtype's limit.
+ *
  * KNN_ERR_INVALID: NULL index, X, Q or out, zero m, mq or n, k <= 0, a bad
  * layout, unknown flag bits, m + mq > INT32_MAX; KNN_ERR_UNSUPPORTED: an
  * unknown src_dtype, dtype not KNN_F64 / KNN_F32, k above the dtype's limit
@@ -358,12 +399,15 @@ KNN_API int knn_index_remove(knn_index_t *index, const int32_t *ids, size_t coun
                              size_t *removed /* nullable */);
 KNN_API int knn_index_update(knn_index_t *index, const int32_t *ids, size_t count, const void *X, int layout,
                              int src_dtype, const double *labels /* nullable */, int flags);
+KNN_API int knn_index_neighbours(knn_index_t *index, const int32_t *ids /* nullable */, size_t count, int k,
+                                 int flags, knn_neighbour_t *out);
 KNN_API int knn_index_last_id(const knn_index_t *index, size_t *last_id);
 KNN_API int knn_index_info(const knn_index_t *index, size_t *m, size_t *n, int *nblocks,
                            size_t *device_bytes, int *last_bits);
 KNN_API int knn_index_destroy(knn_index_t *index);
 
-/* Search wall time of the last knn_search() / knn_query() / knn_index_query() on this thread, seconds: the
+/* Search wall time of the last knn_search() / knn_query() / knn_index_query() / knn_index_neighbours() on this
+ * thread, seconds: the
  * span the reference times (serial:70-98, blk:120-250) -- device compute
  * only, excluding load, H2D, D2H and vote. */
 KNN_API double knn_last_search_seconds(void);
@@ -521,6 +565,17 @@ KNN_API int knn_block_scatter_dt(void *d_block, int dtype, size_t cap, const int
  * rows > dst_cap, d_dst == d_src, a capacity above INT32_MAX, an unknown dtype. */
 KNN_API int knn_block_gather_dt(void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
                                 const int32_t *d_list, size_t rows, size_t n, int dtype, void *stream);
+/* Rows from a corpus held as several blocks: block row row0 + i of d_dst
+ * becomes the row at global position d_pos[i], i < rows, of nblk packed blocks
+ * of one capacity src_cap -- row d_pos[i] % src_cap of block d_pos[i] /
+ * src_cap.  d_tab: the nblk block pointers, a device array; d_pos: device
+ * int32 positions in any order, with repeats.  Otherwise knn_block_gather_dt:
+ * rows and norms bit for bit, nothing else of d_dst touched, launches sized by
+ * `rows`.  A position outside [0, nblk * src_cap) writes nothing.
+ * KNN_ERR_INVALID as knn_block_gather_dt, and for a NULL d_tab or nblk == 0. */
+KNN_API int knn_block_gather_pos_dt(void *d_dst, size_t dst_cap, size_t row0, const void *const *d_tab,
+                                    size_t src_cap, size_t nblk, const int32_t *d_pos, size_t rows, size_t n,
+                                    int dtype, void *stream);
 
 typedef struct knn_ctx knn_ctx_t;
 
@@ -582,6 +637,11 @@ KNN_API int knn_block_scatter_s8(void *d_sblock, int dtype, size_t cap, const in
  * n > 896, the byte path's limit. */
 KNN_API int knn_block_gather_s8(void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
                                 const int32_t *d_list, size_t rows, size_t n, void *stream);
+/* knn_block_gather_pos_dt for byte blocks (d_tab: nblk byte blocks), the norm
+ * words made again for the destination row as in knn_block_gather_s8. */
+KNN_API int knn_block_gather_pos_s8(void *d_dst, size_t dst_cap, size_t row0, const void *const *d_tab,
+                                    size_t src_cap, size_t nblk, const int32_t *d_pos, size_t rows, size_t n,
+                                    void *stream);
 KNN_API int knn_s8_spec_ok(const double *h_meta, size_t n, int dtype);
 /* begin from the query block's speculative byte block (h_meta: the reduced
  * meta, host; KNN_ERR_INVALID unless knn_s8_spec_ok).  The element block is

@@ -23,10 +23,16 @@
  * knn_index_update writes listed rows in place, one scatter a touched block
  * (knn_block_scatter_dt / _s8, defined here; its host planning:
  * knn_update_plan.h), in knn_index_add's two parts.
+ * knn_index_neighbours searches resident rows themselves: its query tiles are
+ * filled from the blocks by position (knn_block_gather_pos_dt / _s8, defined
+ * here; its host planning: knn_neighbours_plan.h), searched by the same
+ * query_tile, and under the keep-zero rule searched at k + 1 with the row
+ * itself taken out of its records afterwards (k_drop_self).
  */
 #include "knn_internal.h"
 #include "knn_remove_plan.h"
 #include "knn_update_plan.h"
+#include "knn_neighbours_plan.h"
 
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
@@ -562,6 +568,25 @@ int knn_block_gather_s8(void *d_dst, size_t dst_cap, size_t row0, const void *d_
     return knn_launch_gather_rows8(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, stream);
 }
 
+/* The same out of a corpus held as nblk blocks of capacity src_cap, by global
+ * position (include/knn.h).  d_tab: the blocks' pointers, a device array. */
+int knn_block_gather_pos_dt(void *d_dst, size_t dst_cap, size_t row0, const void *const *d_tab, size_t src_cap,
+                            size_t nblk, const int32_t *d_pos, size_t rows, size_t n, int dtype, void *stream)
+{
+    if (!gather_args_ok(d_dst, dst_cap, row0, d_tab, src_cap, d_pos, rows, n) || nblk == 0 || !dtype_ok(dtype) ||
+        n > 0x7fffffffULL / 8)
+        return KNN_ERR_INVALID;
+    return knn_launch_gather_pos(d_dst, dst_cap, row0, d_tab, src_cap, nblk, d_pos, rows, n, dtype, stream);
+}
+
+int knn_block_gather_pos_s8(void *d_dst, size_t dst_cap, size_t row0, const void *const *d_tab, size_t src_cap,
+                            size_t nblk, const int32_t *d_pos, size_t rows, size_t n, void *stream)
+{
+    if (!gather_args_ok(d_dst, dst_cap, row0, d_tab, src_cap, d_pos, rows, n) || nblk == 0 || n > KNN_I8_MAX_N)
+        return KNN_ERR_INVALID;
+    return knn_launch_gather_pos8(d_dst, dst_cap, row0, d_tab, src_cap, nblk, d_pos, rows, n, stream);
+}
+
 /* the id map (host and device) for at least `need` entries, its m entries kept */
 static int index_ids_reserve(knn_index_t *ix, size_t need)
 {
@@ -1064,6 +1089,128 @@ int knn_index_update(knn_index_t *ix, const int32_t *ids, size_t count, const vo
     memcpy(ix->cmeta, cmeta, sizeof(cmeta));
     knn_up_plan_free(&pl);
     return KNN_OK;
+}
+
+/* ----------------------------------------------------------- neighbours */
+
+/* The query tiles of knn_index_neighbours: tile t's rows are the resident
+ * rows at positions d_pos[t tcap ..], copied out of the blocks (d_tab: the
+ * element blocks' pointers, then the byte blocks' when s8).  Device to device
+ * on the NULL stream, no wait, nothing read back.
+ *
+ * A gather writes the listed rows and their norms only, where a pack writes
+ * the whole padded tile, and the tile buffers are kept between calls: past
+ * `rows` they hold whatever an earlier, larger batch left there.  What reads
+ * those rows: the element kernels (k_dist_topk and its fp16 / fp32 / split
+ * forms) stage a tile's rows and norms up to round_up(rows, KNN_TQ) -- the
+ * padding queries reject every candidate and write nothing, so the values
+ * never reach a result -- and the query block's conversions in knn_ctx_begin*
+ * (fp16, split and byte shadows) convert every padded row for the same
+ * readers.  k_dist_topk_i8 reads row rows - 1 in their place, and the
+ * re-search and the rescan read listed queries only.  The element rows and
+ * norms in [rows, round_up(rows, KNN_TQ)) are cleared all the same, to the
+ * zeros a pack leaves there: no kernel then computes on stale or never
+ * written memory, whatever it does with the result.  The byte tile needs
+ * nothing. */
+static int gather_tiles(knn_index_t *ix, const void *const *d_tab, const int32_t *d_pos, size_t mq, int s8)
+{
+    const size_t n = ix->n, es = knn_esize(ix->dtype), np = knn_n_pad_dt(n, ix->dtype);
+    const size_t trp = knn_rows_pad(ix->tile_cap);
+    size_t tcap, ntile;
+    tile_shape(ix, mq, &tcap, &ntile);
+    for (size_t t = 0; t < ntile; t++) {
+        const size_t r0 = t * tcap, rows = mq - r0 < tcap ? mq - r0 : tcap;
+        const size_t pad = knn_round_up(rows, KNN_TQ) - rows;   /* (round_up(rows, KNN_TQ) <= trp) */
+        char *blk = (char *)ix->tblk[t];
+        RCHK(knn_block_gather_pos_dt(blk, ix->tile_cap, 0, d_tab, ix->cap, ix->nblk, d_pos + r0, rows, n, ix->dtype,
+                                     NULL));
+        if (pad && (hipMemsetAsync(blk + rows * np * es, 0, pad * np * es, NULL) != hipSuccess ||
+                    hipMemsetAsync(blk + (trp * np + rows) * es, 0, pad * es, NULL) != hipSuccess))
+            return KNN_ERR_HIP;
+        if (s8)
+            RCHK(knn_block_gather_pos_s8(ix->ts8[t], ix->tile_cap, 0, d_tab + ix->nblk, ix->cap, ix->nblk, d_pos + r0,
+                                         rows, n, NULL));
+    }
+    return KNN_OK;
+}
+
+int knn_index_neighbours(knn_index_t *ix, const int32_t *ids, size_t count, int k, int flags, knn_neighbour_t *out)
+{
+    if (!ix || !out || k <= 0 || (ids ? count == 0 : count != 0)) return KNN_ERR_INVALID;
+    if (flags & ~(KNN_QUERY_KEEP_ZERO | KNN_INDEX_DEVICE_OUT)) return KNN_ERR_INVALID;
+    /* keep-zero: the row itself comes back among its own neighbours and is
+     * taken out afterwards, so the engine searches one more */
+    const int kz = (flags & KNN_QUERY_KEEP_ZERO) != 0, dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
+    if (k > (ix->dtype == KNN_F32 ? KNN_MAX_K_F32 : KNN_MAX_K) - kz) return KNN_ERR_UNSUPPORTED;
+    const int ke = k + kz;
+    const size_t mq = ids ? count : ix->m;
+    if (mq > 0x7fffffffULL || ix->m + mq > 0x7fffffffULL) return KNN_ERR_INVALID;
+    for (size_t i = 0; i < count; i++)
+        if (ids[i] < 1 || (size_t)ids[i] > ix->last_id) return KNN_ERR_INVALID;
+    /* the positions, on the host alone (knn_neighbours_plan.h) */
+    int32_t *pos = (int32_t *)malloc(mq * sizeof(int32_t));
+    if (!pos) return KNN_ERR_NOMEM;
+    if (knn_nb_positions(ix->ids, ix->m, ids, count, pos)) {
+        free(pos);
+        return KNN_ERR_INVALID;
+    }
+    const size_t n = ix->n, cnt = mq * (size_t)k, wide = kz ? mq * (size_t)ke : 0;
+    int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+    /* every allocation and upload in front of the span: the positions, the
+     * blocks' pointers (element, then byte), the records of a host-out call
+     * and behind them the k + 1 wide ones of a keep-zero call */
+    const int use_s8 = ix->have_s8 && knn_s8_spec_ok(ix->cmeta, n, ix->dtype);
+    int32_t *d_pos = NULL;
+    void **d_tab = NULL;
+    if (!rc) rc = index_out(ix, (dev_out ? 0 : cnt) + wide);
+    if (!rc && hipMalloc((void **)&d_pos, mq * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc && hipMalloc((void **)&d_tab, 2 * ix->nblk * sizeof(void *)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc && (hipMemcpy(d_pos, pos, mq * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d_tab, ix->blk, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d_tab + ix->nblk, ix->s8, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess))
+        rc = KNN_ERR_HIP;
+    free(pos);
+    if (!rc) rc = index_reserve(ix, mq, ke, 1);
+    size_t tcap = 0, ntile = 0;
+    if (!rc) tile_shape(ix, mq, &tcap, &ntile);
+    for (size_t t = 0; t < ntile && !rc && use_s8; t++)
+        if (!ix->ts8[t] && hipMalloc(&ix->ts8[t], knn_s8_bytes(ix->tile_cap, n)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc) {
+        knn_neighbour_t *d_out = dev_out ? out : ix->d_out;
+        knn_neighbour_t *d_rec = kz ? ix->d_out + (dev_out ? 0 : cnt) : d_out;   /* what the tiles write */
+        hipEventRecord(ix->e0, NULL);
+        /* the batch's reduced meta is the corpus's: the queries are corpus
+         * rows and cmeta only grows.  No tile meta is read back, so the host
+         * does not wait between the gathers and the searches. */
+        memcpy(ix->red, ix->cmeta, KNN_META_DOUBLES * sizeof(double));
+        if (hipMemcpyAsync(ix->d_meta, ix->red, KNN_META_DOUBLES * sizeof(double), hipMemcpyHostToDevice, NULL) !=
+            hipSuccess)
+            rc = KNN_ERR_HIP;
+        if (!rc) rc = gather_tiles(ix, (const void *const *)d_tab, d_pos, mq, use_s8);
+        knn_ctx_set_keep_zero(ix->ctx, kz);
+        for (size_t t = 0; t < ntile && !rc; t++) {
+            const size_t r0 = t * tcap, rows = mq - r0 < tcap ? mq - r0 : tcap;
+            rc = query_tile(ix->ctx, ix->nblk, ix->blk, use_s8 ? ix->s8 : NULL, ix->cnc, ix->cbase, ix->tblk[t],
+                            use_s8 ? ix->ts8[t] : NULL, ix->tile_cap, rows, ix->m + r0, ix->d_meta, ix->red,
+                            d_rec + r0 * (size_t)ke);
+        }
+        if (!rc) ix->last_bits = knn_ctx_contraction_bits(ix->ctx);
+        /* keep-zero: the row itself out of its k + 1 records, positions -> ids
+         * in the same pass; else the ids as knn_index_query writes them */
+        if (!rc && kz) rc = knn_launch_drop_self(d_out, d_rec, d_pos, mq, k, ix->ids ? ix->d_ids : NULL, ix->m, NULL);
+        else if (!rc && ix->ids) rc = knn_launch_remap_idx(d_out, cnt, ix->d_ids, ix->m, NULL);
+        if (!rc) rc = span_end(ix);
+        if (!rc && !dev_out && hipMemcpy(out, d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
+            rc = KNN_ERR_HIP;
+    }
+    if (rc) {   /* nothing of a failed call is kept */
+        hipStreamSynchronize(NULL);
+        free_query_state(ix);
+    }
+    hipFree(d_pos);
+    hipFree(d_tab);
+    if (!rc && !dev_out && ix->labels) fill_labels(out, cnt, ix->labels);
+    return rc;
 }
 
 int knn_index_last_id(const knn_index_t *ix, size_t *last_id)

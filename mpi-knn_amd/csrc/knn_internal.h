@@ -230,6 +230,20 @@ int knn_launch_gather(void *dst, size_t dst_cap, size_t row0, const void *src, s
                       size_t rows, size_t n, int dtype, void *stream);
 int knn_launch_gather_rows8(void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap,
                             const int32_t *list, size_t rows, size_t n, void *stream);
+/* the same from a corpus held as nblk blocks of capacity src_cap (tab: their
+ * pointers, a device array): block row row0 + i of dst <- the row at global
+ * position pos[i] (knn_block_gather_pos_dt / knn_block_gather_pos_s8); a
+ * position outside [0, nblk * src_cap) writes nothing */
+int knn_launch_gather_pos(void *dst, size_t dst_cap, size_t row0, const void *const *tab, size_t src_cap, size_t nblk,
+                          const int32_t *pos, size_t rows, size_t n, int dtype, void *stream);
+int knn_launch_gather_pos8(void *dst, size_t dst_cap, size_t row0, const void *const *tab, size_t src_cap,
+                           size_t nblk, const int32_t *pos, size_t rows, size_t n, void *stream);
+/* knn_kernels.hip: knn_index_neighbours under the keep-zero rule.  Query q's
+ * k + 1 records at in + q (k + 1) -> its k records at out + q k: the first
+ * record whose idx is pos[q] + 1 (the query's own row) left out, else the
+ * last; idx through ids[] (nids entries; NULL: kept) as knn_launch_remap_idx */
+int knn_launch_drop_self(knn_neighbour_t *out, const knn_neighbour_t *in, const int32_t *pos, size_t nq, int k,
+                         const int32_t *ids, size_t nids, void *stream);
 /* knn_kernels.hip: the records' idx from internal position to external id
  * (knn_index_query of an index that removed rows): idx = ids[idx - 1], empty
  * slots (idx 0) kept */

@@ -2396,3 +2396,51 @@ extern "C" int knn_launch_remap_idx(knn_neighbour_t *nb, size_t cnt, const int32
                        ids, (int)nids);
     return hip_status();
 }
+
+// k_drop_self: knn_index_neighbours under the keep-zero rule.  The queries
+// are corpus rows searched with ids past the corpus, so a query meets its own
+// row as a candidate at distance 0; it was searched at k + 1.  Records come
+// ordered by (distance, idx), so either the own row (idx == pos[q] + 1) is
+// among the k + 1 -- without it they are the k nearest others -- or all k + 1
+// are duplicates at distance 0 with lower idx, and the first k are the answer.
+// A wave a query, a 16-byte record a lane, k + 1 records in passes of 64: a
+// ballot finds the own row, the records behind it move up by one.  idx goes
+// through ids[] as in k_remap_idx (ids == NULL: kept); empty slots stay
+// {inf, 0, 0}.
+typedef unsigned knn_rec4u __attribute__((ext_vector_type(4)));   // {distance lo, hi, idx, label}
+__global__ __launch_bounds__(256) void k_drop_self(knn_rec4u *__restrict__ out, const knn_rec4u *__restrict__ in,
+                                                   const int *__restrict__ pos, size_t nq, int k,
+                                                   const int *__restrict__ ids, int nids)
+{
+    static_assert(sizeof(knn_neighbour_t) == sizeof(knn_rec4u), "a record is one 16-byte vector");
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (size_t q = (size_t)blockIdx.x * 4 + wave; q < nq; q += (size_t)gridDim.x * 4) {
+        const knn_rec4u *r = in + q * ((size_t)k + 1);
+        knn_rec4u *o = out + q * (size_t)k;
+        const int self = pos[q] + 1;
+        int s = -1;   // the own row's record, once met (wave-uniform)
+        for (int e0 = 0; e0 <= k; e0 += 64) {
+            const int e = e0 + lane;
+            knn_rec4u v = {0u, 0u, 0u, 0u};
+            if (e <= k) v = r[e];
+            const unsigned long long hit = __ballot(e <= k && (int)v[2] == self);
+            if (s < 0 && hit) s = e0 + (int)__ffsll((long long)hit) - 1;
+            const int w = (s >= 0 && e > s) ? e - 1 : e;   // where record e goes
+            if (e > k || e == s || w >= k) continue;
+            const int idx = (int)v[2];
+            if (ids != nullptr) v[2] = (unsigned)(idx > 0 && idx <= nids ? ids[idx - 1] : 0);
+            o[w] = v;
+        }
+    }
+}
+
+extern "C" int knn_launch_drop_self(knn_neighbour_t *out, const knn_neighbour_t *in, const int32_t *pos, size_t nq,
+                                    int k, const int32_t *ids, size_t nids, void *stream)
+{
+    if (nq == 0) return KNN_OK;
+    if (k <= 0 || nids > 0x7fffffffULL) return KNN_ERR_INVALID;
+    const unsigned grid = (unsigned)((nq + 3) / 4 < 16384 ? (nq + 3) / 4 : 16384);
+    hipLaunchKernelGGL(k_drop_self, dim3(grid), dim3(256), 0, (hipStream_t)stream, (knn_rec4u *)out,
+                       (const knn_rec4u *)in, pos, nq, k, ids, (int)nids);
+    return hip_status();
+}

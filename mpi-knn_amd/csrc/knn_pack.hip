@@ -11,7 +11,9 @@
 //   k_shadow_split   element blocks -> split fp16 rows (k_dist_split)
 //   k_wire_pack / k_wire_unpack  element array <-> int16 ring wire form
 //   k_gather_rows    listed rows of a block -> rows row0 .. of another block
-//                (element and byte blocks: knn_block_gather_dt / _s8)
+//                (element and byte blocks: knn_block_gather_dt / _s8; from
+//                several blocks by global position: knn_block_gather_pos_dt /
+//                _s8)
 //
 // A source is fp64, fp32 or unsigned char (KNN_U8), column-major (ld >= rows)
 // or row-major (ld >= n).  The images, rows_pad = round_up(capacity, 128):
@@ -936,7 +938,9 @@ extern "C" int knn_launch_shadow_split(void *dst, const void *blk, int dtype, si
 // wave carries 64 / lpr rows at once, as k_pack8_row_u8 does; a longer row is
 // walked by its 64 lanes, four 16-byte pieces a lane in flight.  Only the
 // listed rows and their norms are written: no padding, no meta.  A list entry
-// outside [0, src_cap) writes nothing.
+// outside [0, src_cap) writes nothing.  knn_block_gather_pos_dt / _s8 are the
+// same copies out of several source blocks at once (the kernel's MULTI form):
+// the query tiles of knn_index_neighbours, filled from the resident corpus.
 //
 //   element block: the norm (one T) is copied with the row, bit for bit (es =
 //       sizeof(T): the kernel never looks at the values).
@@ -944,22 +948,33 @@ extern "C" int knn_launch_shadow_split(void *dst, const void *blk, int dtype, si
 //       slot, i8_norm_pos); they are made again for row0 + i from the norm the
 //       source words hold (i8_norm_of), as k_gather8 does.
 // ---------------------------------------------------------------------------
-template <bool S8>
-__global__ __launch_bounds__(256) void k_gather_rows(char *__restrict__ dst, const char *__restrict__ src,
+// MULTI (knn_block_gather_pos_dt / _s8): the source is a corpus held as blocks
+// of one capacity src_cap, their pointers in a device table (srcp), and
+// list[i] is a global position: row list[i] % src_cap of block list[i] /
+// src_cap.  lim: the first position that is no row (src_cap without MULTI);
+// an entry outside [0, lim) writes nothing.  Everything else is the one body.
+template <bool S8, bool MULTI>
+__global__ __launch_bounds__(256) void k_gather_rows(char *__restrict__ dst, const void *__restrict__ srcp,
                                                      const int *__restrict__ list, size_t rows, size_t row0,
-                                                     int src_cap, int rb, int es, size_t dst_rp, size_t src_rp,
-                                                     int lpr)
+                                                     int src_cap, unsigned lim, int rb, int es, size_t dst_rp,
+                                                     size_t src_rp, int lpr)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int rpw = 64 / lpr;               // rows a wave
     const int sub = lane / lpr, g = lane % lpr;
     const int c16 = rb / 16;                // 16-byte pieces a row
     char *dn = dst + dst_rp * (size_t)rb;
-    const char *sn = src + src_rp * (size_t)rb;
     for (size_t rbase = ((size_t)blockIdx.x * 4 + wave) * rpw; rbase < rows; rbase += (size_t)gridDim.x * 4 * rpw) {
         const size_t r = rbase + sub;
-        const int q = r < rows ? list[r] : -1;
-        if ((unsigned)q >= (unsigned)src_cap) continue;
+        int q = r < rows ? list[r] : -1;
+        if ((unsigned)q >= lim) continue;
+        const char *src;
+        if constexpr (MULTI) {
+            src = ((const char *const *)srcp)[q / src_cap];
+            q %= src_cap;
+        } else
+            src = (const char *)srcp;
+        const char *sn = src + src_rp * (size_t)rb;
         const knn_v4u *s = (const knn_v4u *)(src + (size_t)q * rb);
         knn_v4u *d = (knn_v4u *)(dst + (row0 + r) * (size_t)rb);
         for (int c = g; c < c16; c += 4 * lpr) {
@@ -988,9 +1003,12 @@ __global__ __launch_bounds__(256) void k_gather_rows(char *__restrict__ dst, con
 }
 
 // rb: the row bytes of both blocks (a multiple of 32); es: the element block's
-// element size, 0 for a byte block
+// element size, 0 for a byte block.  nblk == 0: src is the one source block
+// and list holds its local rows; nblk > 0: src is a device table of nblk block
+// pointers and list holds global positions (positions are int32: the limit
+// stops there).
 static int launch_gather(bool s8, void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap,
-                         const int32_t *list, size_t rows, size_t rb, int es, void *stream)
+                         size_t nblk, const int32_t *list, size_t rows, size_t rb, int es, void *stream)
 {
     if (rb > 0x7fffffffULL) return KNN_ERR_INVALID;
     int lpr = 1;
@@ -999,13 +1017,16 @@ static int launch_gather(bool s8, void *dst, size_t dst_cap, size_t row0, const 
     const size_t nw = (rows * lpr + 63) / 64;
     const unsigned nb = (unsigned)((nw + 3) / 4 < 16384 ? (nw + 3) / 4 : 16384);
     const size_t drp = knn_rows_pad(dst_cap), srp = knn_rows_pad(src_cap);
-    if (s8)
-        hipLaunchKernelGGL(k_gather_rows<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (char *)dst,
-                           (const char *)src, list, rows, row0, (int)src_cap, (int)rb, es, drp, srp, lpr);
-    else
-        hipLaunchKernelGGL(k_gather_rows<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (char *)dst,
-                           (const char *)src, list, rows, row0, (int)src_cap, (int)rb, es, drp, srp, lpr);
-    return hip_status();
+    const size_t tot = nblk ? nblk * src_cap : src_cap;
+    const unsigned lim = (unsigned)(tot < 0x80000000ULL ? tot : 0x80000000ULL);
+    return with_bool(s8, [&](auto b8) {
+        return with_bool(nblk != 0, [&](auto mu) -> int {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gather_rows<decltype(b8)::value, decltype(mu)::value>), dim3(nb),
+                               dim3(256), 0, (hipStream_t)stream, (char *)dst, src, list, rows, row0, (int)src_cap, lim,
+                               (int)rb, es, drp, srp, lpr);
+            return hip_status();
+        });
+    });
 }
 
 extern "C" int knn_launch_gather(void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap,
@@ -1013,12 +1034,30 @@ extern "C" int knn_launch_gather(void *dst, size_t dst_cap, size_t row0, const v
 {
     if (dtype != KNN_F64 && dtype != KNN_F32) return KNN_ERR_INVALID;
     const int es = (int)knn_esize(dtype);
-    return launch_gather(false, dst, dst_cap, row0, src, src_cap, list, rows, knn_n_pad_dt(n, dtype) * es, es,
+    return launch_gather(false, dst, dst_cap, row0, src, src_cap, 0, list, rows, knn_n_pad_dt(n, dtype) * es, es,
                          stream);
 }
 
 extern "C" int knn_launch_gather_rows8(void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap,
                                        const int32_t *list, size_t rows, size_t n, void *stream)
 {
-    return launch_gather(true, dst, dst_cap, row0, src, src_cap, list, rows, knn_s8_rs(n), 0, stream);
+    return launch_gather(true, dst, dst_cap, row0, src, src_cap, 0, list, rows, knn_s8_rs(n), 0, stream);
+}
+
+// the same from nblk blocks of capacity src_cap (tab: their pointers, a device
+// array), by global position (knn_block_gather_pos_dt / _s8)
+extern "C" int knn_launch_gather_pos(void *dst, size_t dst_cap, size_t row0, const void *const *tab, size_t src_cap,
+                                     size_t nblk, const int32_t *pos, size_t rows, size_t n, int dtype, void *stream)
+{
+    if ((dtype != KNN_F64 && dtype != KNN_F32) || nblk == 0) return KNN_ERR_INVALID;
+    const int es = (int)knn_esize(dtype);
+    return launch_gather(false, dst, dst_cap, row0, tab, src_cap, nblk, pos, rows, knn_n_pad_dt(n, dtype) * es, es,
+                         stream);
+}
+
+extern "C" int knn_launch_gather_pos8(void *dst, size_t dst_cap, size_t row0, const void *const *tab, size_t src_cap,
+                                      size_t nblk, const int32_t *pos, size_t rows, size_t n, void *stream)
+{
+    if (nblk == 0) return KNN_ERR_INVALID;
+    return launch_gather(true, dst, dst_cap, row0, tab, src_cap, nblk, pos, rows, knn_s8_rs(n), 0, stream);
 }

@@ -55,6 +55,7 @@ API_SYMBOLS = (
     "knn_index_add", "knn_block_append_dt", "knn_block_append_s8",
     "knn_index_remove", "knn_index_last_id", "knn_block_gather_dt", "knn_block_gather_s8",
     "knn_index_update", "knn_block_scatter_dt", "knn_block_scatter_s8",
+    "knn_index_neighbours", "knn_block_gather_pos_dt", "knn_block_gather_pos_s8",
 )
 DTYPES = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 # a pack / index SOURCE may also be unsigned bytes (KNN_U8: never a block or search dtype)
@@ -161,6 +162,9 @@ def _load():
         "knn_index_update": ([p, p, sz, p, i, i, p, i], i),
         "knn_block_scatter_dt": ([p, i, sz, p, p, sz, sz, p, sz, i, sz, i, p], i),
         "knn_block_scatter_s8": ([p, i, sz, p, p, sz, sz, p, sz, i, sz, i, p], i),
+        "knn_index_neighbours": ([p, p, sz, i, i, p], i),
+        "knn_block_gather_pos_dt": ([p, sz, sz, p, sz, sz, p, sz, sz, i, p], i),
+        "knn_block_gather_pos_s8": ([p, sz, sz, p, sz, sz, p, sz, sz, p], i),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -396,6 +400,14 @@ def block_gather(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, stream=0
                                    stream or None), "knn_block_gather_dt")
 
 
+def block_gather_pos(d_dst, dst_cap, row0, d_tab, src_cap, nblk, d_pos, rows, n, stream=0, dtype="f64"):
+    """knn_block_gather_pos_dt: block row row0 + i of d_dst <- the row at global
+    position d_pos[i] of nblk blocks of capacity src_cap, i < rows (d_tab: a
+    device array of the nblk block pointers; d_pos: device int32 positions)."""
+    _check(lib.knn_block_gather_pos_dt(d_dst, dst_cap, row0, d_tab, src_cap, nblk, d_pos, rows, n, DTYPES[dtype],
+                                       stream or None), "knn_block_gather_pos_dt")
+
+
 _live_contexts = weakref.WeakSet()
 
 
@@ -433,6 +445,13 @@ def block_gather_s8(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, strea
     again for the new rows."""
     _check(lib.knn_block_gather_s8(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, stream or None),
            "knn_block_gather_s8")
+
+
+def block_gather_pos_s8(d_dst, dst_cap, row0, d_tab, src_cap, nblk, d_pos, rows, n, stream=0):
+    """knn_block_gather_pos_s8: the same rows out of nblk byte blocks, their norm
+    words made again for the new rows."""
+    _check(lib.knn_block_gather_pos_s8(d_dst, dst_cap, row0, d_tab, src_cap, nblk, d_pos, rows, n, stream or None),
+           "knn_block_gather_pos_s8")
 
 
 def s8_spec_ok(meta_host, n, dtype="f64"):
@@ -618,6 +637,43 @@ class Index:
             raise ValueError("labels must have %d entries, got %d" % (rows, lab.shape[0]))
         _check(lib.knn_index_update(self._h, _ptr(a), a.size, ptr, lay, src, _ptr(lab), dev), "knn_index_update")
         del keep
+
+    def neighbours(self, ids=None, k=30, keep_zero=True, out=None):
+        """knn_index_neighbours: for each listed 1-based id (any order, repeats
+        allowed) the k nearest OTHER live rows of the index; ids=None: every
+        live row in ascending id, the corpus's kNN graph.  keep_zero=False
+        drops every zero distance (the row itself and its exact duplicates:
+        knn_search's leave-one-out rule); keep_zero=True leaves out only the
+        row itself (k + 1 must then be within the dtype's limit).  out as in
+        query.  An id outside [1, last_id] or one that is no longer live raises
+        KnnError(ERR_INVALID).  Returns (neighbours, device seconds)."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        if ids is None:
+            a, rows = None, self.m
+        else:
+            a = np.asarray(ids).reshape(-1)
+            if a.size and a.dtype.kind not in "iu":
+                raise ValueError("ids must be integers, got %s" % a.dtype)
+            if a.size == 0 or a.min() < -2 ** 31 or a.max() >= 2 ** 31:   # (an empty list is not ids=None)
+                raise KnnError(ERR_INVALID, "knn_index_neighbours")
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            rows = a.size
+        flags = QUERY_KEEP_ZERO if keep_zero else 0
+        if out is not None:
+            if not _is_device_tensor(out) or not out.is_contiguous() or \
+                    out.numel() * out.element_size() < rows * k * NB_DTYPE.itemsize:
+                raise ValueError("out must be a contiguous torch GPU buffer of >= %d bytes" %
+                                 (rows * k * NB_DTYPE.itemsize))
+            _on_index_device(out, "out")
+            flags |= INDEX_DEVICE_OUT
+            res, optr = out, ctypes.c_void_p(out.data_ptr())
+        else:
+            res = np.zeros((rows, max(k, 0)), dtype=NB_DTYPE)
+            optr = _ptr(res)
+        _check(lib.knn_index_neighbours(self._h, _ptr(a), rows if a is not None else 0, k, flags, optr),
+               "knn_index_neighbours")
+        return res, lib.knn_last_search_seconds()
 
     @property
     def last_id(self):

@@ -42,6 +42,9 @@ Legs (one a process, so two builds of the library can be run in alternation:
           around the call), and in the same process, on another fresh index,
           what a user without update does for the same rows: Index.remove of
           their ids, then Index.add of the rows (which also changes their ids)
+  neighbours  Index.neighbours on the 60000-row uint8 index, flags 0 and
+          keep-zero: every live row, one id, 1000 ids; beside knn_search's span
+          on the same corpus in the same process
 
 Median of --runs after --warmup, with min and max.  Each leg appends one JSON
 line to --out; --merge FILES... folds such lines into profiles/index_bench.json.
@@ -398,6 +401,33 @@ def leg_mapcost(knn, a, X, Qall):
     return rows
 
 
+def leg_neighbours(knn, a, X):
+    """Index.neighbours on the uint8 index under both zero rules: every live row
+    (the corpus's graph), one id, and 1000 ids spread over the corpus; and the
+    yardstick in the same process, knn_search's span on the same corpus"""
+    import numpy as np
+
+    def spans(f):
+        t = []
+        for i in range(a.warmup + a.runs):
+            _, s = f()
+            if i >= a.warmup:
+                t.append(s * 1e3)
+        return stats(t)
+
+    out = {"search": spans(lambda: knn.search(X, a.k)), "results": []}
+    ix = knn.Index(X.astype(np.uint8))
+    lists = {"all": None, "1": [len(X) // 2], "1000": np.random.default_rng(3).permutation(len(X))[:1000] + 1}
+    for keep_zero in (False, True):
+        for name, ids in lists.items():
+            r = spans(lambda: ix.neighbours(ids, a.k, keep_zero=keep_zero))
+            out["results"].append({"ids": name, "keep_zero": keep_zero, "bits": ix.info().last_bits, "span": r})
+    info = ix.info()
+    out["nblocks"], out["device_bytes"] = info.nblocks, info.device_bytes
+    ix.close()
+    return out
+
+
 def merge(files, out, keep=False):
     legs = []
     if keep and os.path.exists(out):
@@ -418,7 +448,7 @@ def merge(files, out, keep=False):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--leg", choices=["query", "index", "pack", "add", "rebuild", "remove", "rebuild-survivors", "gather",
-                                     "mapcost", "update"])
+                                     "mapcost", "update", "neighbours"])
     ap.add_argument("--root", default=ROOT, help="tree whose mpi-knn_amd/ is imported")
     ap.add_argument("--tag", default="this", help="name of the build in the output")
     ap.add_argument("--round", type=int, default=0)
@@ -460,6 +490,8 @@ def main():
             rec["results"] = leg_mapcost(mpiknn, a, X, Qall)
         elif a.leg == "update":
             rec["results"] = leg_update(mpiknn, a, X, Qall)
+        elif a.leg == "neighbours":
+            rec.update(leg_neighbours(mpiknn, a, X))
         else:
             rec.update(leg_index(mpiknn, a, X, Qall))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
