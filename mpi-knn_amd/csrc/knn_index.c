@@ -2,32 +2,32 @@
  * knn_index.c -- out-of-sample queries (include/knn.h): the resident corpus
  * index knn_index_* and the one-call knn_query() on top of it.
  *
- * One implementation of the sequence serves both.  build_pack / build_finish
- * pack the corpus from a device source into resident blocks of one capacity
- * (KNN_QUERY_BLOCK=rows overrides the choice): element blocks, their meta
- * MAX-reduced on the host, and byte blocks when that meta passes
- * knn_s8_spec_ok.  run_pack / run_finish pack a batch of queries into tiles of at most
- * KNN_QUERY_TILE_MAX rows (KNN_QUERY_TILE=rows overrides that, for tests)
- * with ids m.. (past every corpus id, so no row is ever "the query itself"),
- * MAX-reduces their meta with the corpus's, and runs the ring rank's sequence
- * against foreign blocks per tile (blk:217-242): begin, the fold of every
- * corpus block, end, the int8 re-search where it applies, then the exact
- * rescan over every block.  The records of every tile stay on the device
- * until the last tile is done: a timed span holds no copy to the host.
- * knn_index_add repeats build_pack / build_finish for rows that arrive later,
- * with the packs at a row offset (knn_block_append_dt / _s8, defined here).
- * knn_index_remove compacts the blocks from the first removed row on with the
- * block gathers (knn_block_gather_dt / _s8, defined here; its host planning:
- * knn_remove_plan.h) and from then on keeps the live rows' ids, which a small
- * kernel writes into every batch's records.
- * knn_index_update writes listed rows in place, one scatter a touched block
- * (knn_block_scatter_dt / _s8, defined here; its host planning:
- * knn_update_plan.h), in knn_index_add's two parts.
- * knn_index_neighbours searches resident rows themselves: its query tiles are
- * filled from the blocks by position (knn_block_gather_pos_dt / _s8, defined
- * here; its host planning: knn_neighbours_plan.h), searched by the same
- * query_tile, and under the keep-zero rule searched at k + 1 with the row
- * itself taken out of its records afterwards (k_drop_self).
+ * The corpus is resident as blocks of one capacity (KNN_QUERY_BLOCK=rows
+ * overrides the choice): element blocks, their meta MAX-reduced on the host,
+ * and byte blocks while that meta passes knn_s8_spec_ok.  The per-block host
+ * arrays are one blocks_t; set_counts, blocks_release, fresh_blocks,
+ * write_meta_words, read_meta and drop_s8 are what every entry point does
+ * with them.  A batch of queries is a batch_t: tiles of at most
+ * KNN_QUERY_TILE_MAX rows (KNN_QUERY_TILE=rows overrides that, for tests) with
+ * ids m.. (past every corpus id, so no row is ever "the query itself").
+ * Every entry point reads: checks, plan, reserve, enqueue, wait, commit.
+ * create, knn_query: build_pack / build_finish pack the corpus from a device
+ * source (dev_src_t) in two parts around one wait.  query: run_pack /
+ * run_finish pack the tiles, MAX-reduce their meta with the corpus's
+ * (put_meta) and run search_tiles -- per tile the ring rank's sequence against
+ * foreign blocks (blk:217-242; query_tile) -- and finish_search ends the call:
+ * ids for positions, the span, the records, which stay on the device until
+ * the last tile is done (a timed span holds no copy to the host).  add: the
+ * two parts again for rows that arrive later, the packs at a row offset, behind
+ * index_reblock where the blocks would become too many.  remove: compacts the
+ * blocks from the first removed row on with the block gathers
+ * (knn_remove_plan.h) and from then on keeps the live rows' ids.  update: one
+ * scatter a touched block (knn_update_plan.h) in add's two parts (s8_stays,
+ * commit_meta).  neighbours: tiles filled from the blocks by position
+ * (knn_neighbours_plan.h), the same search_tiles, and under the keep-zero rule
+ * k + 1 with the row itself taken out afterwards (k_drop_self).  The
+ * knn_block_* operations are in knn_blocks.c; what a failed call leaves behind
+ * is swept on a CPU by tests/index_trace.
  */
 #include "knn_internal.h"
 #include "knn_remove_plan.h"
@@ -47,18 +47,25 @@
 #define KNN_QUERY_BYTES_MAX ((size_t)1 << 30)   /* element bytes of one block / tile */
 #define KNN_QUERY_TILE_MAX ((size_t)1 << 18)
 #define KNN_INDEX_TILE_MIN 128                  /* tile capacity grows from here, doubling */
+#define META_BYTES (KNN_META_DOUBLES * sizeof(double))
+
+/* the per-block host arrays: each contiguous (knn_ctx_step_n takes them as
+ * arrays), cbase behind cnc in one allocation, chm 8 doubles a block */
+typedef struct {
+    void **blk, **s8;
+    size_t *cnc, *cbase;
+    double *chm;   /* the blocks' meta as read back */
+} blocks_t;
 
 struct knn_index {
     int dtype;
     size_t m, n;
-    /* the corpus: nblk blocks of capacity cap; s8[] only when have_s8 */
+    /* the corpus: nblk blocks of capacity cap; b.s8[] only when have_s8 */
     size_t cap, nblk;
     size_t nalloc;                    /* entries of the per-block arrays (>= nblk: knn_index_add grows them) */
-    void **blk, **s8;
-    size_t *cnc, *cbase;
+    blocks_t b;
     int have_s8;
     double cmeta[KNN_META_DOUBLES];   /* host copy of the corpus's reduced meta */
-    double *chm;                      /* the blocks' meta as read back (8 doubles a block) */
     double *labels;
     size_t lab_cap;                   /* doubles allocated at labels (>= last_id: labels are indexed by id) */
     /* ids: row p (0-based position in the blocks) has the 1-based id ids[p],
@@ -82,7 +89,21 @@ struct knn_index {
     int last_bits;
 };
 
+/* a batch of mq queries: ntile tiles of tcap rows */
+typedef struct {
+    size_t mq, tcap, ntile;
+} batch_t;
+
 static int dtype_ok(int dtype) { return dtype == KNN_F64 || dtype == KNN_F32; }
+static int layout_ok(int layout) { return layout == KNN_COLMAJOR || layout == KNN_ROWMAJOR; }
+static int k_max(int dtype) { return dtype == KNN_F32 ? KNN_MAX_K_F32 : KNN_MAX_K; }
+
+static int ids_ok(const knn_index_t *ix, const int32_t *ids, size_t count)
+{
+    for (size_t i = 0; i < count; i++)
+        if (ids[i] < 1 || (size_t)ids[i] > ix->last_id) return 0;
+    return 1;
+}
 
 static size_t fit_rows(size_t n, int dtype)
 {
@@ -98,6 +119,132 @@ static size_t env_rows(const char *name, size_t dflt, size_t limit)
     if (e && atol(e) > 0) return (size_t)atol(e) < limit ? (size_t)atol(e) : limit;
     return dflt;
 }
+
+static int stream_wait(void) { return hipStreamSynchronize(NULL) == hipSuccess ? KNN_OK : KNN_ERR_HIP; }
+
+static void blocks_free_arrays(blocks_t *b)
+{
+    free(b->blk);
+    free(b->s8);
+    free(b->cnc);
+    free(b->chm);
+    memset(b, 0, sizeof(*b));
+}
+
+/* arrays for na blocks, zeroed; all or nothing */
+static int blocks_alloc(blocks_t *b, size_t na)
+{
+    b->blk = (void **)calloc(na, sizeof(void *));
+    b->s8 = (void **)calloc(na, sizeof(void *));
+    b->cnc = (size_t *)calloc(2 * na, sizeof(size_t));
+    b->chm = (double *)calloc(na * KNN_META_DOUBLES, sizeof(double));
+    if (!b->blk || !b->s8 || !b->cnc || !b->chm) {
+        blocks_free_arrays(b);
+        return KNN_ERR_NOMEM;
+    }
+    b->cbase = b->cnc + na;
+    return KNN_OK;
+}
+
+/* the device memory of blocks b0 .. b1-1, both images */
+static void blocks_release(void **blk, void **s8, size_t b0, size_t b1)
+{
+    for (size_t b = b0; b < b1; b++) {
+        hipFree(blk[b]);
+        hipFree(s8[b]);
+        blk[b] = s8[b] = NULL;
+    }
+}
+
+/* cnc / cbase of the nblk blocks that hold m rows */
+static void set_counts(knn_index_t *ix)
+{
+    for (size_t b = 0; b < ix->nblk; b++) {
+        ix->b.cbase[b] = b * ix->cap;
+        ix->b.cnc[b] = ix->m - ix->b.cbase[b] < ix->cap ? ix->m - ix->b.cbase[b] : ix->cap;
+    }
+}
+
+/* a value outside the byte image arrived: the element path from now on */
+static void drop_s8(knn_index_t *ix)
+{
+    for (size_t b = 0; b < ix->nblk; b++) {
+        hipFree(ix->b.s8[b]);
+        ix->b.s8[b] = NULL;
+    }
+    ix->have_s8 = 0;
+}
+
+/* Fresh buffers for rebuilt blocks b0 .. b1-1 of capacity cap, into blk[] and
+ * (where the index has byte blocks) s8[]: the element image zeroed, the byte
+ * image when zero_s8.  On failure the caller releases what was made. */
+static int fresh_blocks(const knn_index_t *ix, size_t cap, size_t b0, size_t b1, void **blk, void **s8, int zero_s8)
+{
+    const size_t ebytes = knn_block_bytes_dt(cap, ix->n, ix->dtype), sbytes = knn_s8_bytes(cap, ix->n);
+    for (size_t b = b0; b < b1; b++) {
+        if (hipMalloc(&blk[b], ebytes) != hipSuccess) return KNN_ERR_NOMEM;
+        if (hipMemsetAsync(blk[b], 0, ebytes, NULL) != hipSuccess) return KNN_ERR_HIP;
+        if (!ix->have_s8) continue;
+        if (hipMalloc(&s8[b], sbytes) != hipSuccess) return KNN_ERR_NOMEM;
+        if (zero_s8 && hipMemsetAsync(s8[b], 0, sbytes, NULL) != hipSuccess) return KNN_ERR_HIP;
+    }
+    return KNN_OK;
+}
+
+/* A rebuilt block's trailing meta words at `at`: hm, its word KNN_META_S8 0
+ * (an element block) or 1 (a byte block).  No search reads a corpus block's
+ * trailing meta, but a later append takes its atomicMax into it.  stage: 8
+ * doubles of the caller's that live until its wait. */
+static int write_meta_words(void *at, const double *hm, int s8, double *stage)
+{
+    memcpy(stage, hm, META_BYTES);
+    stage[KNN_META_S8] = s8;
+    return hipMemcpyAsync(at, stage, META_BYTES, hipMemcpyHostToDevice, NULL) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+}
+
+/* an element block's meta words on their way to the host (NULL stream, no wait) */
+static int read_meta(const knn_index_t *ix, const void *blk, size_t cap, double *dst)
+{
+    const char *at = (const char *)blk + knn_block_meta_offset_dt(cap, ix->n, ix->dtype);
+    return hipMemcpyAsync(dst, at, META_BYTES, hipMemcpyDeviceToHost, NULL) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+}
+
+/* red = max(red, every buffer's meta) word by word */
+static void meta_max(double *red, const double *hm, size_t nb)
+{
+    for (size_t b = 0; b < nb; b++)
+        for (int j = 0; j < KNN_META_DOUBLES; j++)
+            if (hm[b * KNN_META_DOUBLES + j] > red[j]) red[j] = hm[b * KNN_META_DOUBLES + j];
+}
+
+/* red = max(the corpus meta, nb buffers' meta at hm), and on its way to
+ * d_meta (red is pinned, and its last reader done with the call before this
+ * one: the copy is enqueued without a wait for what is in front of it) */
+static int put_meta(knn_index_t *ix, const double *hm, size_t nb)
+{
+    memcpy(ix->red, ix->cmeta, META_BYTES);
+    meta_max(ix->red, hm, nb);
+    return hipMemcpyAsync(ix->d_meta, ix->red, META_BYTES, hipMemcpyHostToDevice, NULL) == hipSuccess ? KNN_OK
+                                                                                                        : KNN_ERR_HIP;
+}
+
+/* a caller's array on the device: X itself under KNN_INDEX_DEVICE_SRC, else
+ * an uploaded copy (zero-initialize; dev_src_free on every exit) */
+typedef struct {
+    const void *src;
+    void *own;
+} dev_src_t;
+
+static int dev_src(dev_src_t *d, const void *X, size_t bytes, int flags)
+{
+    d->src = X;
+    if (flags & KNN_INDEX_DEVICE_SRC) return KNN_OK;
+    if (hipMalloc(&d->own, bytes) != hipSuccess) return KNN_ERR_NOMEM;
+    d->src = d->own;
+    return hipMemcpy(d->own, X, bytes, hipMemcpyHostToDevice) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+}
+
+static void dev_src_free(dev_src_t *d) { hipFree(d->own); }
 
 static void free_query_state(knn_index_t *ix)
 {
@@ -119,10 +266,7 @@ static void index_free(knn_index_t *ix)
 {
     if (!ix) return;
     free_query_state(ix);
-    for (size_t b = 0; b < ix->nblk; b++) {
-        if (ix->blk) hipFree(ix->blk[b]);
-        if (ix->s8) hipFree(ix->s8[b]);
-    }
+    if (ix->b.blk) blocks_release(ix->b.blk, ix->b.s8, 0, ix->nblk);
     hipFree(ix->d_out);
     hipFree(ix->d_meta);
     hipFree(ix->d_ids);
@@ -130,10 +274,7 @@ static void index_free(knn_index_t *ix)
     if (ix->red) hipHostFree(ix->red);
     if (ix->e0) hipEventDestroy(ix->e0);
     if (ix->e1) hipEventDestroy(ix->e1);
-    free(ix->blk);
-    free(ix->s8);
-    free(ix->cnc);
-    free(ix->chm);
+    blocks_free_arrays(&ix->b);
     free(ix->labels);
     free(ix);
 }
@@ -153,25 +294,69 @@ static int index_alloc(knn_index_t **out, size_t m, size_t n, int dtype)
     ix->cap = env_rows("KNN_QUERY_BLOCK", m < fit ? m : fit, m);
     ix->nblk = (m + ix->cap - 1) / ix->cap;   /* (<= INT32_MAX) */
     ix->nalloc = ix->nblk;
-    ix->blk = (void **)calloc(ix->nblk, sizeof(void *));
-    ix->s8 = (void **)calloc(ix->nblk, sizeof(void *));
-    ix->cnc = (size_t *)calloc(2 * ix->nblk, sizeof(size_t));
-    ix->chm = (double *)calloc(ix->nblk * KNN_META_DOUBLES, sizeof(double));
-    if (!ix->blk || !ix->s8 || !ix->cnc || !ix->chm) {
+    int rc = blocks_alloc(&ix->b, ix->nblk);
+    if (!rc && (hipMalloc((void **)&ix->d_meta, META_BYTES) != hipSuccess ||
+                hipHostMalloc((void **)&ix->red, META_BYTES, hipHostMallocDefault) != hipSuccess))
+        rc = KNN_ERR_NOMEM;
+    if (!rc && (hipEventCreate(&ix->e0) != hipSuccess || hipEventCreate(&ix->e1) != hipSuccess)) rc = KNN_ERR_HIP;
+    if (rc) {
         index_free(ix);
-        return KNN_ERR_NOMEM;
-    }
-    ix->cbase = ix->cnc + ix->nblk;
-    if (hipMalloc((void **)&ix->d_meta, KNN_META_DOUBLES * sizeof(double)) != hipSuccess ||
-        hipHostMalloc((void **)&ix->red, KNN_META_DOUBLES * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-        index_free(ix);
-        return KNN_ERR_NOMEM;
-    }
-    if (hipEventCreate(&ix->e0) != hipSuccess || hipEventCreate(&ix->e1) != hipSuccess) {
-        index_free(ix);
-        return KNN_ERR_HIP;
+        return rc;
     }
     *out = ix;
+    return KNN_OK;
+}
+
+/* the per-block arrays for at least nb blocks, their nblk entries kept */
+static int index_grow_arrays(knn_index_t *ix, size_t nb)
+{
+    if (nb <= ix->nalloc) return KNN_OK;
+    const size_t na = 2 * ix->nalloc > nb ? 2 * ix->nalloc : nb;
+    blocks_t g;
+    RCHK(blocks_alloc(&g, na));
+    memcpy(g.blk, ix->b.blk, ix->nblk * sizeof(void *));
+    memcpy(g.s8, ix->b.s8, ix->nblk * sizeof(void *));
+    memcpy(g.cnc, ix->b.cnc, ix->nblk * sizeof(size_t));
+    memcpy(g.cbase, ix->b.cbase, ix->nblk * sizeof(size_t));
+    memcpy(g.chm, ix->b.chm, ix->nblk * META_BYTES);
+    blocks_free_arrays(&ix->b);
+    ix->b = g;
+    ix->nalloc = na;
+    return KNN_OK;
+}
+
+/* the id map (host and device) for at least `need` entries, its m entries kept */
+static int index_ids_reserve(knn_index_t *ix, size_t need)
+{
+    if (need <= ix->ids_cap) return KNN_OK;
+    const size_t nc = 2 * ix->ids_cap > need ? 2 * ix->ids_cap : need;
+    int32_t *d = NULL;
+    if (hipMalloc((void **)&d, nc * sizeof(int32_t)) != hipSuccess) return KNN_ERR_NOMEM;
+    int32_t *h = (int32_t *)realloc(ix->ids, nc * sizeof(int32_t));
+    if (!h) {
+        hipFree(d);
+        return KNN_ERR_NOMEM;
+    }
+    ix->ids = h;   /* (the same entries, whatever follows) */
+    if (hipMemcpy(d, h, ix->m * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(d);
+        return KNN_ERR_HIP;
+    }
+    hipFree(ix->d_ids);
+    ix->d_ids = d;
+    ix->ids_cap = nc;
+    return KNN_OK;
+}
+
+/* the index's own record buffer, for cnt records */
+static int index_out(knn_index_t *ix, size_t cnt)
+{
+    if (cnt <= ix->out_recs) return KNN_OK;
+    hipFree(ix->d_out);
+    ix->d_out = NULL;
+    ix->out_recs = 0;
+    if (hipMalloc((void **)&ix->d_out, cnt * sizeof(knn_neighbour_t)) != hipSuccess) return KNN_ERR_NOMEM;
+    ix->out_recs = cnt;
     return KNN_OK;
 }
 
@@ -179,43 +364,31 @@ static int index_alloc(knn_index_t **out, size_t m, size_t n, int dtype)
  * (buffer b: rows r0 = b * step ..), element blocks (s8 = 0; their meta
  * words gathered behind each pack into hm, 8 doubles a buffer) or byte
  * blocks (s8 = 1).  All on the NULL stream, no wait. */
-static int pack_rows(void *const *buf, size_t nb, size_t bc, size_t step, const void *d_src, size_t tot, size_t n,
-                     int layout, int src_dtype, int dtype, int s8, double *hm)
+static int pack_rows(const knn_index_t *ix, void *const *buf, size_t nb, size_t bc, size_t step, const void *d_src,
+                     size_t tot, int layout, int src_dtype, int s8, double *hm)
 {
-    const size_t es = knn_src_esize(src_dtype);
+    const size_t es = knn_src_esize(src_dtype), n = ix->n;
     for (size_t b = 0; b < nb; b++) {
         const size_t r0 = b * step, rows = tot - r0 < step ? tot - r0 : step;
         const char *src = (const char *)d_src + (layout == KNN_COLMAJOR ? r0 : r0 * n) * es;
         const size_t ld = layout == KNN_COLMAJOR ? tot : n;
         if (s8) {
-            RCHK(knn_block_pack_s8(buf[b], dtype, bc, rows, n, src, src_dtype, ld, layout, NULL));
+            RCHK(knn_block_pack_s8(buf[b], ix->dtype, bc, rows, n, src, src_dtype, ld, layout, NULL));
             continue;
         }
-        RCHK(knn_block_pack_dt(buf[b], dtype, bc, rows, n, src, src_dtype, ld, layout, NULL));
-        if (hipMemcpyAsync(hm + b * KNN_META_DOUBLES, (const char *)buf[b] + knn_block_meta_offset_dt(bc, n, dtype),
-                           KNN_META_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, NULL) != hipSuccess)
-            return KNN_ERR_HIP;
+        RCHK(knn_block_pack_dt(buf[b], ix->dtype, bc, rows, n, src, src_dtype, ld, layout, NULL));
+        RCHK(read_meta(ix, buf[b], bc, hm + b * KNN_META_DOUBLES));
     }
     return KNN_OK;
-}
-
-/* red = max(red, every buffer's meta) word by word */
-static void meta_max(double *red, const double *hm, size_t nb)
-{
-    for (size_t b = 0; b < nb; b++)
-        for (int j = 0; j < KNN_META_DOUBLES; j++)
-            if (hm[b * KNN_META_DOUBLES + j] > red[j]) red[j] = hm[b * KNN_META_DOUBLES + j];
 }
 
 /* the element blocks' memory (knn_query: ahead of its span) */
 static int index_alloc_blocks(knn_index_t *ix)
 {
-    for (size_t b = 0; b < ix->nblk; b++) {
-        ix->cbase[b] = b * ix->cap;
-        ix->cnc[b] = ix->m - ix->cbase[b] < ix->cap ? ix->m - ix->cbase[b] : ix->cap;
-        if (!ix->blk[b] && hipMalloc(&ix->blk[b], knn_block_bytes_dt(ix->cap, ix->n, ix->dtype)) != hipSuccess)
+    set_counts(ix);
+    for (size_t b = 0; b < ix->nblk; b++)
+        if (!ix->b.blk[b] && hipMalloc(&ix->b.blk[b], knn_block_bytes_dt(ix->cap, ix->n, ix->dtype)) != hipSuccess)
             return KNN_ERR_NOMEM;
-    }
     return KNN_OK;
 }
 
@@ -225,7 +398,7 @@ static int index_alloc_blocks(knn_index_t *ix)
 static int build_pack(knn_index_t *ix, const void *d_X, int layout, int src_dtype)
 {
     RCHK(index_alloc_blocks(ix));
-    return pack_rows(ix->blk, ix->nblk, ix->cap, ix->cap, d_X, ix->m, ix->n, layout, src_dtype, ix->dtype, 0, ix->chm);
+    return pack_rows(ix, ix->b.blk, ix->nblk, ix->cap, ix->cap, d_X, ix->m, layout, src_dtype, 0, ix->b.chm);
 }
 
 /* ... and, the meta arrived: its reduction, and for 8-bit data the byte blocks
@@ -235,7 +408,7 @@ static int build_finish(knn_index_t *ix, const void *d_X, int layout, int src_dt
                         size_t batch_n)
 {
     memset(ix->cmeta, 0, sizeof(ix->cmeta));   /* (every meta word is >= 0) */
-    meta_max(ix->cmeta, ix->chm, ix->nblk);
+    meta_max(ix->cmeta, ix->b.chm, ix->nblk);
     /* knn_query knows its only batch already (batch_hm: its tiles' meta): no
      * byte blocks for a corpus whose queries will not take the byte path */
     double joint[KNN_META_DOUBLES];
@@ -244,32 +417,31 @@ static int build_finish(knn_index_t *ix, const void *d_X, int layout, int src_dt
     ix->have_s8 = knn_s8_spec_ok(joint, ix->n, ix->dtype);
     if (!ix->have_s8) return KNN_OK;
     for (size_t b = 0; b < ix->nblk; b++)
-        if (hipMalloc(&ix->s8[b], knn_s8_bytes(ix->cap, ix->n)) != hipSuccess) return KNN_ERR_NOMEM;
-    return pack_rows(ix->s8, ix->nblk, ix->cap, ix->cap, d_X, ix->m, ix->n, layout, src_dtype, ix->dtype, 1, NULL);
+        if (hipMalloc(&ix->b.s8[b], knn_s8_bytes(ix->cap, ix->n)) != hipSuccess) return KNN_ERR_NOMEM;
+    return pack_rows(ix, ix->b.s8, ix->nblk, ix->cap, ix->cap, d_X, ix->m, layout, src_dtype, 1, NULL);
 }
 
-/* a batch of mq queries: tiles of *tcap rows, *ntile of them */
-static void tile_shape(const knn_index_t *ix, size_t mq, size_t *tcap, size_t *ntile)
+static batch_t tile_shape(const knn_index_t *ix, size_t mq)
 {
     const size_t fit = fit_rows(ix->n, ix->dtype);
     size_t t = mq < fit ? mq : fit;
     if (t > KNN_QUERY_TILE_MAX) t = KNN_QUERY_TILE_MAX;
-    *tcap = env_rows("KNN_QUERY_TILE", t, mq);
-    *ntile = (mq + *tcap - 1) / *tcap;
+    batch_t bt = {mq, env_rows("KNN_QUERY_TILE", t, mq), 0};
+    bt.ntile = (mq + bt.tcap - 1) / bt.tcap;
+    return bt;
 }
 
-/* The context and the tile buffers for a batch of mq queries at k.  grow: the
- * tile capacity doubles from KNN_INDEX_TILE_MIN rows, so that a stream of
- * varying batch sizes does not reallocate every call (knn_query, one batch:
- * the capacity it needs). */
-static int index_reserve(knn_index_t *ix, size_t mq, int k, int grow)
+/* The context and the tile buffers for the batch at k.  grow: the tile
+ * capacity doubles from KNN_INDEX_TILE_MIN rows, so that a stream of varying
+ * batch sizes does not reallocate every call (knn_query, one batch: the
+ * capacity it needs). */
+static int index_reserve(knn_index_t *ix, const batch_t *bt, int k, int grow)
 {
-    size_t tcap, ntile;
-    tile_shape(ix, mq, &tcap, &ntile);
-    if (ix->ctx && (k != ix->k || tcap > ix->tile_cap)) free_query_state(ix);
+    const size_t ntile = bt->ntile;
+    if (ix->ctx && (k != ix->k || bt->tcap > ix->tile_cap)) free_query_state(ix);
     if (!ix->ctx) {
-        size_t cap = grow ? (ix->tile_cap ? ix->tile_cap : KNN_INDEX_TILE_MIN) : tcap;
-        while (cap < tcap) cap *= 2;
+        size_t cap = grow ? (ix->tile_cap ? ix->tile_cap : KNN_INDEX_TILE_MIN) : bt->tcap;
+        while (cap < bt->tcap) cap *= 2;
         RCHK(knn_ctx_create_dt(&ix->ctx, 0, cap, ix->n, ix->cap, k, ix->dtype));
         ix->tile_cap = cap;
         ix->k = k;
@@ -297,6 +469,15 @@ static int index_reserve(knn_index_t *ix, size_t mq, int k, int grow)
     }
     for (size_t t = 0; t < ntile; t++)
         if (!ix->tblk[t] && hipMalloc(&ix->tblk[t], knn_block_bytes_dt(ix->tile_cap, ix->n, ix->dtype)) != hipSuccess)
+            return KNN_ERR_NOMEM;
+    return KNN_OK;
+}
+
+/* the byte forms of the batch's tiles, allocated on first use */
+static int reserve_ts8(knn_index_t *ix, size_t ntile)
+{
+    for (size_t t = 0; t < ntile; t++)
+        if (!ix->ts8[t] && hipMalloc(&ix->ts8[t], knn_s8_bytes(ix->tile_cap, ix->n)) != hipSuccess)
             return KNN_ERR_NOMEM;
     return KNN_OK;
 }
@@ -329,71 +510,45 @@ static int query_tile(knn_ctx_t *ctx, size_t nblk, void *const *cblk, void *cons
     return KNN_OK;
 }
 
-/* One batch against the resident blocks, mq queries from the device source
- * d_Q, in two parts around one wait for the NULL stream: the tiles' element
- * packs and their meta on their way to the host (the context and the tile
- * buffers reserved by the caller) ... */
-static int run_pack(knn_index_t *ix, const void *d_Q, size_t mq, int layout, int src_dtype)
+/* The batch's tiles against the resident blocks under the reduced meta in
+ * red / d_meta, on the byte path when use_s8: tile t's records (the
+ * context's k a query) to d_rec, complete on return (knn_ctx_end waits for
+ * each tile's). */
+static int search_tiles(knn_index_t *ix, const batch_t *bt, int use_s8, knn_neighbour_t *d_rec)
 {
-    size_t tcap, ntile;
-    tile_shape(ix, mq, &tcap, &ntile);
-    return pack_rows(ix->tblk, ntile, ix->tile_cap, tcap, d_Q, mq, ix->n, layout, src_dtype, ix->dtype, 0, ix->thm);
-}
-
-/* ... and, the meta arrived: its MAX-reduction with the corpus's, the path
- * that allows, and the tiles' searches -- their records into d_out (device),
- * complete on return (knn_ctx_end waits for each tile's). */
-static int run_finish(knn_index_t *ix, const void *d_Q, size_t mq, int layout, int src_dtype, int flags,
-                      knn_neighbour_t *d_out)
-{
-    const size_t n = ix->n;
-    size_t tcap, ntile;
-    tile_shape(ix, mq, &tcap, &ntile);
-    knn_ctx_set_keep_zero(ix->ctx, (flags & KNN_QUERY_KEEP_ZERO) != 0);
-    /* (pinned, and its last reader done with the call before this one: the
-     * copy is enqueued without a wait for the packs in front of it) */
-    double *red = ix->red;
-    memcpy(red, ix->cmeta, KNN_META_DOUBLES * sizeof(double));
-    meta_max(red, ix->thm, ntile);
-    if (hipMemcpyAsync(ix->d_meta, red, KNN_META_DOUBLES * sizeof(double), hipMemcpyHostToDevice, NULL) != hipSuccess)
-        return KNN_ERR_HIP;
-    /* the byte path: the corpus has its byte blocks and the batch is 8-bit too */
-    const int use_s8 = ix->have_s8 && knn_s8_spec_ok(red, n, ix->dtype);
-    if (use_s8) {
-        for (size_t t = 0; t < ntile; t++)
-            if (!ix->ts8[t] && hipMalloc(&ix->ts8[t], knn_s8_bytes(ix->tile_cap, n)) != hipSuccess)
-                return KNN_ERR_NOMEM;
-        RCHK(pack_rows(ix->ts8, ntile, ix->tile_cap, tcap, d_Q, mq, n, layout, src_dtype, ix->dtype, 1, NULL));
-    }
-    for (size_t t = 0; t < ntile; t++) {
-        const size_t r0 = t * tcap, rows = mq - r0 < tcap ? mq - r0 : tcap;
-        RCHK(query_tile(ix->ctx, ix->nblk, ix->blk, use_s8 ? ix->s8 : NULL, ix->cnc, ix->cbase, ix->tblk[t],
-                        use_s8 ? ix->ts8[t] : NULL, ix->tile_cap, rows, ix->m + r0, ix->d_meta, red,
-                        d_out + r0 * (size_t)ix->k));
+    for (size_t t = 0; t < bt->ntile; t++) {
+        const size_t r0 = t * bt->tcap, rows = bt->mq - r0 < bt->tcap ? bt->mq - r0 : bt->tcap;
+        RCHK(query_tile(ix->ctx, ix->nblk, ix->b.blk, use_s8 ? ix->b.s8 : NULL, ix->b.cnc, ix->b.cbase, ix->tblk[t],
+                        use_s8 ? ix->ts8[t] : NULL, ix->tile_cap, rows, ix->m + r0, ix->d_meta, ix->red,
+                        d_rec + r0 * (size_t)ix->k));
     }
     ix->last_bits = knn_ctx_contraction_bits(ix->ctx);
     return KNN_OK;
 }
 
-static int stream_wait(void) { return hipStreamSynchronize(NULL) == hipSuccess ? KNN_OK : KNN_ERR_HIP; }
-
-/* the index's own record buffer, for cnt records */
-static int index_out(knn_index_t *ix, size_t cnt)
+/* One batch against the resident blocks, its queries from the device source
+ * d_Q, in two parts around one wait for the NULL stream: the tiles' element
+ * packs and their meta on their way to the host (the context and the tile
+ * buffers reserved by the caller) ... */
+static int run_pack(knn_index_t *ix, const void *d_Q, const batch_t *bt, int layout, int src_dtype)
 {
-    if (cnt <= ix->out_recs) return KNN_OK;
-    hipFree(ix->d_out);
-    ix->d_out = NULL;
-    ix->out_recs = 0;
-    if (hipMalloc((void **)&ix->d_out, cnt * sizeof(knn_neighbour_t)) != hipSuccess) return KNN_ERR_NOMEM;
-    ix->out_recs = cnt;
-    return KNN_OK;
+    return pack_rows(ix, ix->tblk, bt->ntile, ix->tile_cap, bt->tcap, d_Q, bt->mq, layout, src_dtype, 0, ix->thm);
 }
 
-/* a host array on the device (*d: to hipFree) */
-static int upload(void **d, const void *h, size_t bytes)
+/* ... and, the meta arrived: its MAX-reduction with the corpus's, the path
+ * that allows, and the tiles' searches -- their records into d_out (device) */
+static int run_finish(knn_index_t *ix, const void *d_Q, const batch_t *bt, int layout, int src_dtype, int flags,
+                      knn_neighbour_t *d_out)
 {
-    if (hipMalloc(d, bytes) != hipSuccess) return KNN_ERR_NOMEM;
-    return hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+    knn_ctx_set_keep_zero(ix->ctx, (flags & KNN_QUERY_KEEP_ZERO) != 0);
+    RCHK(put_meta(ix, ix->thm, bt->ntile));
+    /* the byte path: the corpus has its byte blocks and the batch is 8-bit too */
+    const int use_s8 = ix->have_s8 && knn_s8_spec_ok(ix->red, ix->n, ix->dtype);
+    if (use_s8) {
+        RCHK(reserve_ts8(ix, bt->ntile));
+        RCHK(pack_rows(ix, ix->ts8, bt->ntile, ix->tile_cap, bt->tcap, d_Q, bt->mq, layout, src_dtype, 1, NULL));
+    }
+    return search_tiles(ix, bt, use_s8, d_out);
 }
 
 /* the span e0 .. e1 (e1 recorded here) into knn_last_search_seconds() */
@@ -412,33 +567,55 @@ static void fill_labels(knn_neighbour_t *out, size_t cnt, const double *labels)
     for (size_t i = 0; i < cnt; i++) out[i].label = out[i].idx > 0 ? (int32_t)labels[out[i].idx - 1] : 0;
 }
 
+/* The end of a search call that stands at rc, its mq x k records due in d_out:
+ * positions -> ids where rows were removed (the tiles wrote k + 1 wide records
+ * to d_rec != d_out: the row itself, d_pos, out of them in the same pass), the
+ * span's end, records and labels to the host.  A failed call keeps nothing. */
+static int finish_search(knn_index_t *ix, int rc, knn_neighbour_t *out, int dev_out, knn_neighbour_t *d_out,
+                         const knn_neighbour_t *d_rec, const int32_t *d_pos, size_t mq, int k)
+{
+    const size_t cnt = mq * (size_t)k;
+    if (!rc && d_rec != d_out)
+        rc = knn_launch_drop_self(d_out, d_rec, d_pos, mq, k, ix->ids ? ix->d_ids : NULL, ix->m, NULL);
+    else if (!rc && ix->ids) rc = knn_launch_remap_idx(d_out, cnt, ix->d_ids, ix->m, NULL);
+    if (!rc) rc = span_end(ix);
+    if (!rc && !dev_out && hipMemcpy(out, d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = KNN_ERR_HIP;
+    if (rc) {
+        hipStreamSynchronize(NULL);
+        free_query_state(ix);
+    } else if (!dev_out && ix->labels) {
+        fill_labels(out, cnt, ix->labels);
+    }
+    return rc;
+}
+
 int knn_index_create(knn_index_t **index, const void *X, size_t m, size_t n, int layout, int src_dtype,
                      const double *labels, int dtype, int flags)
 {
     if (!index || !X || m == 0 || n == 0) return KNN_ERR_INVALID;
     if (!knn_src_esize(src_dtype) || !dtype_ok(dtype)) return KNN_ERR_UNSUPPORTED;
-    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (!layout_ok(layout)) return KNN_ERR_INVALID;
     if (flags & ~KNN_INDEX_DEVICE_SRC) return KNN_ERR_INVALID;
     if (m > 0x7fffffffULL || n > 0x7fffffffULL) return KNN_ERR_INVALID;
     knn_index_t *ix = NULL;
     RCHK(index_alloc(&ix, m, n, dtype));
     int rc = KNN_OK;
-    void *d_X = NULL;
+    dev_src_t x = {0};
     if (labels) {
         ix->labels = (double *)malloc(m * sizeof(double));
         ix->lab_cap = m;
         if (ix->labels) memcpy(ix->labels, labels, m * sizeof(double));
         else rc = KNN_ERR_NOMEM;
     }
-    if (!rc && !(flags & KNN_INDEX_DEVICE_SRC)) rc = upload(&d_X, X, m * n * knn_src_esize(src_dtype));
-    const void *src = (flags & KNN_INDEX_DEVICE_SRC) ? X : d_X;
-    if (!rc) rc = build_pack(ix, src, layout, src_dtype);
+    if (!rc) rc = dev_src(&x, X, m * n * knn_src_esize(src_dtype), flags);
+    if (!rc) rc = build_pack(ix, x.src, layout, src_dtype);
     if (!rc) rc = stream_wait();
-    if (!rc) rc = build_finish(ix, src, layout, src_dtype, NULL, 0);
+    if (!rc) rc = build_finish(ix, x.src, layout, src_dtype, NULL, 0);
     /* the packs have read the source before the index is handed out */
     if (!rc) rc = stream_wait();
     else hipStreamSynchronize(NULL);
-    hipFree(d_X);
+    dev_src_free(&x);
     if (rc) {
         index_free(ix);
         return rc;
@@ -452,289 +629,86 @@ int knn_index_query(knn_index_t *ix, const void *Q, size_t mq, int layout, int s
 {
     if (!ix || !Q || !out || mq == 0 || k <= 0) return KNN_ERR_INVALID;
     if (!knn_src_esize(src_dtype)) return KNN_ERR_UNSUPPORTED;
-    if (k > (ix->dtype == KNN_F32 ? KNN_MAX_K_F32 : KNN_MAX_K)) return KNN_ERR_UNSUPPORTED;
-    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (k > k_max(ix->dtype)) return KNN_ERR_UNSUPPORTED;
+    if (!layout_ok(layout)) return KNN_ERR_INVALID;
     if (flags & ~(KNN_QUERY_KEEP_ZERO | KNN_INDEX_DEVICE_SRC | KNN_INDEX_DEVICE_OUT)) return KNN_ERR_INVALID;
     if (mq > 0x7fffffffULL || ix->m + mq > 0x7fffffffULL) return KNN_ERR_INVALID;
     if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
-    const size_t cnt = mq * (size_t)k;
     const int dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
-    void *d_Q = NULL;
-    int rc = dev_out ? KNN_OK : index_out(ix, cnt);
-    if (!rc && !(flags & KNN_INDEX_DEVICE_SRC)) rc = upload(&d_Q, Q, mq * ix->n * knn_src_esize(src_dtype));
-    if (!rc) rc = index_reserve(ix, mq, k, 1);
+    const batch_t bt = tile_shape(ix, mq);
+    dev_src_t q = {0};
+    int rc = dev_out ? KNN_OK : index_out(ix, mq * (size_t)k);
+    if (!rc) rc = dev_src(&q, Q, mq * ix->n * knn_src_esize(src_dtype), flags);
+    if (!rc) rc = index_reserve(ix, &bt, k, 1);
+    knn_neighbour_t *d_out = dev_out ? out : ix->d_out;
     if (!rc) {
-        knn_neighbour_t *d_out = dev_out ? out : ix->d_out;
-        const void *src = (flags & KNN_INDEX_DEVICE_SRC) ? Q : d_Q;
         hipEventRecord(ix->e0, NULL);
-        rc = run_pack(ix, src, mq, layout, src_dtype);
+        rc = run_pack(ix, q.src, &bt, layout, src_dtype);
         if (!rc) rc = stream_wait();
-        if (!rc) rc = run_finish(ix, src, mq, layout, src_dtype, flags, d_out);
-        /* rows were removed: positions -> the ids the caller knows */
-        if (!rc && ix->ids) rc = knn_launch_remap_idx(d_out, cnt, ix->d_ids, ix->m, NULL);
-        if (!rc) rc = span_end(ix);
-        if (!rc && !dev_out && hipMemcpy(out, d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = KNN_ERR_HIP;
+        if (!rc) rc = run_finish(ix, q.src, &bt, layout, src_dtype, flags, d_out);
     }
-    if (rc) {   /* nothing of a failed call is kept */
-        hipStreamSynchronize(NULL);
-        free_query_state(ix);
-    }
-    hipFree(d_Q);
-    if (!rc && !dev_out && ix->labels) fill_labels(out, cnt, ix->labels);
+    rc = finish_search(ix, rc, out, dev_out, d_out, d_out, NULL, mq, k);
+    dev_src_free(&q);
     return rc;
 }
 
 /* ------------------------------------------------------------------ add */
-
-/* Rows that arrive later: block rows row0 .. of a block packed before
- * (include/knn.h).  The entry points live here, beside their first user, and
- * not with knn_block_pack_* in knn_engine.c: that file is also built on its
- * own against stub launchers (tests/engine_trace). */
-int knn_block_append_dt(void *d_block, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
-                        const void *d_src, int src_dtype, size_t ld, int layout, void *stream)
-{
-    if (!d_block || !d_src || rows == 0 || n == 0 || cap > 0x7fffffffULL || row0 > cap || rows > cap - row0 ||
-        n > 0x7fffffffULL || !dtype_ok(dtype) || !knn_src_esize(src_dtype))
-        return KNN_ERR_INVALID;
-    if (layout == KNN_COLMAJOR ? ld < rows : (layout == KNN_ROWMAJOR ? ld < n : 1)) return KNN_ERR_INVALID;
-    return knn_launch_append(d_block, dtype, cap, row0, rows, n, d_src, src_dtype, ld, layout, stream);
-}
-
-int knn_block_append_s8(void *d_sblock, int dtype, size_t cap, size_t row0, size_t rows, size_t n,
-                        const void *d_src, int src_dtype, size_t ld, int layout, void *stream)
-{
-    if (!d_sblock || !d_src || rows == 0 || n == 0 || cap > 0x7fffffffULL || row0 > cap || rows > cap - row0 ||
-        n > KNN_I8_MAX_N || !dtype_ok(dtype) || !knn_src_esize(src_dtype))
-        return KNN_ERR_INVALID;
-    if (layout == KNN_COLMAJOR ? ld < rows : (layout == KNN_ROWMAJOR ? ld < n : 1)) return KNN_ERR_INVALID;
-    return knn_launch_append_s8(d_sblock, dtype, cap, row0, rows, n, d_src, src_dtype, ld, layout, stream);
-}
-
-/* Block row d_pos[i] <- source row d_srow[i] (include/knn.h).  Beside the
- * appends for the same reason. */
-static int scatter_args_ok(const void *d_block, int dtype, size_t cap, const int32_t *d_pos, size_t rows, size_t n,
-                           const void *d_src, size_t src_rows, int src_dtype, size_t ld, int layout, size_t n_max)
-{
-    if (!d_block || !d_pos || !d_src || rows == 0 || n == 0 || src_rows == 0 || cap > 0x7fffffffULL ||
-        src_rows > 0x7fffffffULL || n > n_max || !dtype_ok(dtype) || !knn_src_esize(src_dtype))
-        return 0;
-    return layout == KNN_COLMAJOR ? ld >= src_rows : (layout == KNN_ROWMAJOR ? ld >= n : 0);
-}
-
-int knn_block_scatter_dt(void *d_block, int dtype, size_t cap, const int32_t *d_pos, const int32_t *d_srow,
-                         size_t rows, size_t n, const void *d_src, size_t src_rows, int src_dtype, size_t ld,
-                         int layout, void *stream)
-{
-    if (!scatter_args_ok(d_block, dtype, cap, d_pos, rows, n, d_src, src_rows, src_dtype, ld, layout, 0x7fffffffULL))
-        return KNN_ERR_INVALID;
-    return knn_launch_scatter(d_block, dtype, cap, d_pos, d_srow, rows, n, d_src, src_rows, src_dtype, ld, layout,
-                              stream);
-}
-
-int knn_block_scatter_s8(void *d_sblock, int dtype, size_t cap, const int32_t *d_pos, const int32_t *d_srow,
-                         size_t rows, size_t n, const void *d_src, size_t src_rows, int src_dtype, size_t ld,
-                         int layout, void *stream)
-{
-    if (!scatter_args_ok(d_sblock, dtype, cap, d_pos, rows, n, d_src, src_rows, src_dtype, ld, layout, KNN_I8_MAX_N))
-        return KNN_ERR_INVALID;
-    return knn_launch_scatter_s8(d_sblock, dtype, cap, d_pos, d_srow, rows, n, d_src, src_rows, src_dtype, ld, layout,
-                                 stream);
-}
-
-/* Block row row0 + i of d_dst <- row d_list[i] of d_src (include/knn.h).
- * Beside the appends for the same reason. */
-static int gather_args_ok(const void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
-                          const int32_t *d_list, size_t rows, size_t n)
-{
-    return d_dst && d_src && d_list && d_dst != d_src && rows != 0 && n != 0 && dst_cap <= 0x7fffffffULL &&
-           src_cap <= 0x7fffffffULL && src_cap != 0 && row0 <= dst_cap && rows <= dst_cap - row0;
-}
-
-int knn_block_gather_dt(void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
-                        const int32_t *d_list, size_t rows, size_t n, int dtype, void *stream)
-{
-    if (!gather_args_ok(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n) || !dtype_ok(dtype) ||
-        n > 0x7fffffffULL / 8)
-        return KNN_ERR_INVALID;
-    return knn_launch_gather(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, dtype, stream);
-}
-
-int knn_block_gather_s8(void *d_dst, size_t dst_cap, size_t row0, const void *d_src, size_t src_cap,
-                        const int32_t *d_list, size_t rows, size_t n, void *stream)
-{
-    if (!gather_args_ok(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n) || n > KNN_I8_MAX_N)
-        return KNN_ERR_INVALID;
-    return knn_launch_gather_rows8(d_dst, dst_cap, row0, d_src, src_cap, d_list, rows, n, stream);
-}
-
-/* The same out of a corpus held as nblk blocks of capacity src_cap, by global
- * position (include/knn.h).  d_tab: the blocks' pointers, a device array. */
-int knn_block_gather_pos_dt(void *d_dst, size_t dst_cap, size_t row0, const void *const *d_tab, size_t src_cap,
-                            size_t nblk, const int32_t *d_pos, size_t rows, size_t n, int dtype, void *stream)
-{
-    if (!gather_args_ok(d_dst, dst_cap, row0, d_tab, src_cap, d_pos, rows, n) || nblk == 0 || !dtype_ok(dtype) ||
-        n > 0x7fffffffULL / 8)
-        return KNN_ERR_INVALID;
-    return knn_launch_gather_pos(d_dst, dst_cap, row0, d_tab, src_cap, nblk, d_pos, rows, n, dtype, stream);
-}
-
-int knn_block_gather_pos_s8(void *d_dst, size_t dst_cap, size_t row0, const void *const *d_tab, size_t src_cap,
-                            size_t nblk, const int32_t *d_pos, size_t rows, size_t n, void *stream)
-{
-    if (!gather_args_ok(d_dst, dst_cap, row0, d_tab, src_cap, d_pos, rows, n) || nblk == 0 || n > KNN_I8_MAX_N)
-        return KNN_ERR_INVALID;
-    return knn_launch_gather_pos8(d_dst, dst_cap, row0, d_tab, src_cap, nblk, d_pos, rows, n, stream);
-}
-
-/* the id map (host and device) for at least `need` entries, its m entries kept */
-static int index_ids_reserve(knn_index_t *ix, size_t need)
-{
-    if (need <= ix->ids_cap) return KNN_OK;
-    const size_t nc = 2 * ix->ids_cap > need ? 2 * ix->ids_cap : need;
-    int32_t *d = NULL;
-    if (hipMalloc((void **)&d, nc * sizeof(int32_t)) != hipSuccess) return KNN_ERR_NOMEM;
-    int32_t *h = (int32_t *)realloc(ix->ids, nc * sizeof(int32_t));
-    if (!h) {
-        hipFree(d);
-        return KNN_ERR_NOMEM;
-    }
-    ix->ids = h;   /* (the same entries, whatever follows) */
-    if (hipMemcpy(d, h, ix->m * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(d);
-        return KNN_ERR_HIP;
-    }
-    hipFree(ix->d_ids);
-    ix->d_ids = d;
-    ix->ids_cap = nc;
-    return KNN_OK;
-}
-
-/* the per-block arrays for at least nb blocks, their nblk entries kept */
-static int index_grow_arrays(knn_index_t *ix, size_t nb)
-{
-    if (nb <= ix->nalloc) return KNN_OK;
-    const size_t na = 2 * ix->nalloc > nb ? 2 * ix->nalloc : nb;
-    void **blk = (void **)calloc(na, sizeof(void *)), **s8 = (void **)calloc(na, sizeof(void *));
-    size_t *cnc = (size_t *)calloc(2 * na, sizeof(size_t));
-    double *chm = (double *)calloc(na * KNN_META_DOUBLES, sizeof(double));
-    if (!blk || !s8 || !cnc || !chm) {
-        free(blk);
-        free(s8);
-        free(cnc);
-        free(chm);
-        return KNN_ERR_NOMEM;
-    }
-    memcpy(blk, ix->blk, ix->nblk * sizeof(void *));
-    memcpy(s8, ix->s8, ix->nblk * sizeof(void *));
-    memcpy(cnc, ix->cnc, ix->nblk * sizeof(size_t));
-    memcpy(cnc + na, ix->cbase, ix->nblk * sizeof(size_t));
-    memcpy(chm, ix->chm, ix->nblk * KNN_META_DOUBLES * sizeof(double));
-    free(ix->blk);
-    free(ix->s8);
-    free(ix->cnc);
-    free(ix->chm);
-    ix->blk = blk;
-    ix->s8 = s8;
-    ix->cnc = cnc;
-    ix->cbase = cnc + na;
-    ix->chm = chm;
-    ix->nalloc = na;
-    return KNN_OK;
-}
 
 /* The corpus in blocks of capacity ncap (> cap): element rows and norms move
  * device to device, a new block's meta is the max of the blocks merged into
  * it, and the byte blocks are converted again from the new element blocks
  * (knn_launch_shadow8 with the corpus meta: for knn_s8_spec_ok data the image
  * the source pack writes on every corpus row; rows past a block's nc are not
- * searched).  No search reads a corpus byte block's trailing meta (begin_s8
- * and step_shadow_n take the reduced meta as arguments), but a later
- * knn_block_append_s8 takes its atomicMax into it: it is written.  Old and new
- * blocks are resident together until the last copy is done.  All or nothing. */
+ * searched).  Old and new blocks are resident together until the last copy is
+ * done.  All or nothing. */
 static int index_reblock(knn_index_t *ix, size_t ncap)
 {
     const size_t n = ix->n, es = knn_esize(ix->dtype), np = knn_n_pad_dt(n, ix->dtype);
     const size_t nb = (ix->m + ncap - 1) / ncap;
     const size_t orp = knn_rows_pad(ix->cap), nrp = knn_rows_pad(ncap);
-    void **blk = (void **)calloc(nb, sizeof(void *)), **s8 = (void **)calloc(nb, sizeof(void *));
-    size_t *cnc = (size_t *)calloc(2 * nb, sizeof(size_t));
-    double *chm = (double *)calloc(nb * KNN_META_DOUBLES, sizeof(double));
-    int rc = blk && s8 && cnc && chm ? KNN_OK : KNN_ERR_NOMEM;
-    for (size_t b = 0; b < nb && !rc; b++) {
-        const size_t bytes = knn_block_bytes_dt(ncap, n, ix->dtype);
-        if (hipMalloc(&blk[b], bytes) != hipSuccess) rc = KNN_ERR_NOMEM;
-        else if (hipMemsetAsync(blk[b], 0, bytes, NULL) != hipSuccess) rc = KNN_ERR_HIP;
-        if (!rc && ix->have_s8 && hipMalloc(&s8[b], knn_s8_bytes(ncap, n)) != hipSuccess) rc = KNN_ERR_NOMEM;
-    }
+    blocks_t g = {0};
+    double *stage = (double *)calloc(2 * nb * KNN_META_DOUBLES, sizeof(double));   /* until the wait */
+    int rc = stage ? blocks_alloc(&g, nb) : KNN_ERR_NOMEM;
+    if (!rc) rc = fresh_blocks(ix, ncap, 0, nb, g.blk, g.s8, 0);
     /* runs of rows that lie in one old and one new block */
-    for (size_t g = 0; g < ix->m && !rc;) {
-        const size_t ob = g / ix->cap, oo = g % ix->cap, b = g / ncap, no = g % ncap;
-        const size_t len = ix->cnc[ob] - oo < ncap - no ? ix->cnc[ob] - oo : ncap - no;
-        const char *src = (const char *)ix->blk[ob];
-        char *dst = (char *)blk[b];
+    for (size_t r = 0; r < ix->m && !rc;) {
+        const size_t ob = r / ix->cap, oo = r % ix->cap, b = r / ncap, no = r % ncap;
+        const size_t len = ix->b.cnc[ob] - oo < ncap - no ? ix->b.cnc[ob] - oo : ncap - no;
+        const char *src = (const char *)ix->b.blk[ob];
+        char *dst = (char *)g.blk[b];
         if (hipMemcpyAsync(dst + no * np * es, src + oo * np * es, len * np * es, hipMemcpyDeviceToDevice, NULL) !=
                 hipSuccess ||
             hipMemcpyAsync(dst + (nrp * np + no) * es, src + (orp * np + oo) * es, len * es, hipMemcpyDeviceToDevice,
                            NULL) != hipSuccess)
             rc = KNN_ERR_HIP;
-        meta_max(chm + b * KNN_META_DOUBLES, ix->chm + ob * KNN_META_DOUBLES, 1);
-        g += len;
+        meta_max(g.chm + b * KNN_META_DOUBLES, ix->b.chm + ob * KNN_META_DOUBLES, 1);
+        r += len;
     }
-    if (!rc && ix->have_s8) {
-        memcpy(ix->red, ix->cmeta, KNN_META_DOUBLES * sizeof(double));
-        if (hipMemcpyAsync(ix->d_meta, ix->red, KNN_META_DOUBLES * sizeof(double), hipMemcpyHostToDevice, NULL) !=
-            hipSuccess)
-            rc = KNN_ERR_HIP;
-    }
+    if (!rc && ix->have_s8) rc = put_meta(ix, NULL, 0);
     for (size_t b = 0; b < nb && !rc; b++) {
-        double hm[KNN_META_DOUBLES];
-        memcpy(hm, chm + b * KNN_META_DOUBLES, sizeof(hm));
-        hm[KNN_META_S8] = 0.0;   /* (an element block's word 7) */
-        if (hipMemcpy((char *)blk[b] + knn_block_meta_offset_dt(ncap, n, ix->dtype), hm, sizeof(hm),
-                      hipMemcpyHostToDevice) != hipSuccess)
-            rc = KNN_ERR_HIP;
+        const double *hm = g.chm + b * KNN_META_DOUBLES;
+        double *st = stage + 2 * b * KNN_META_DOUBLES;
+        rc = write_meta_words((char *)g.blk[b] + knn_block_meta_offset_dt(ncap, n, ix->dtype), hm, 0, st);
         if (rc || !ix->have_s8) continue;
-        rc = knn_launch_shadow8(s8[b], blk[b], ix->dtype, nrp, n, ix->d_meta, NULL);
-        hm[KNN_META_S8] = 1.0;
-        if (!rc && hipMemcpy((char *)s8[b] + knn_s8_meta_offset(ncap, n), hm, sizeof(hm), hipMemcpyHostToDevice) !=
-                       hipSuccess)
-            rc = KNN_ERR_HIP;
+        rc = knn_launch_shadow8(g.s8[b], g.blk[b], ix->dtype, nrp, n, ix->d_meta, NULL);
+        if (!rc) rc = write_meta_words((char *)g.s8[b] + knn_s8_meta_offset(ncap, n), hm, 1, st + KNN_META_DOUBLES);
     }
     if (!rc) rc = stream_wait();
     else hipStreamSynchronize(NULL);
+    free(stage);
     if (rc) {
-        for (size_t b = 0; b < nb; b++) {
-            if (blk) hipFree(blk[b]);
-            if (s8) hipFree(s8[b]);
-        }
-        free(blk);
-        free(s8);
-        free(cnc);
-        free(chm);
+        if (g.blk) blocks_release(g.blk, g.s8, 0, nb);
+        blocks_free_arrays(&g);
         return rc;
     }
-    /* the context was made for the old capacity */
+    /* commit; the context was made for the old capacity */
     free_query_state(ix);
-    for (size_t b = 0; b < ix->nblk; b++) {
-        hipFree(ix->blk[b]);
-        hipFree(ix->s8[b]);
-    }
-    free(ix->blk);
-    free(ix->s8);
-    free(ix->cnc);
-    free(ix->chm);
-    ix->blk = blk;
-    ix->s8 = s8;
-    ix->cnc = cnc;
-    ix->cbase = cnc + nb;
-    ix->chm = chm;
+    blocks_release(ix->b.blk, ix->b.s8, 0, ix->nblk);
+    blocks_free_arrays(&ix->b);
+    ix->b = g;
     ix->cap = ncap;
     ix->nblk = ix->nalloc = nb;
-    for (size_t b = 0; b < nb; b++) {
-        ix->cbase[b] = b * ncap;
-        ix->cnc[b] = ix->m - ix->cbase[b] < ncap ? ix->m - ix->cbase[b] : ncap;
-    }
+    set_counts(ix);
     return KNN_OK;
 }
 
@@ -759,13 +733,24 @@ static int add_rows(knn_index_t *ix, void **buf, const void *d_X, size_t rows, i
             RCHK(s8 ? knn_block_pack_s8(buf[b], ix->dtype, cap, len, n, src, src_dtype, ld, layout, NULL)
                     : knn_block_pack_dt(buf[b], ix->dtype, cap, len, n, src, src_dtype, ld, layout, NULL));
         }
-        if (!s8 && hipMemcpyAsync(ix->chm + b * KNN_META_DOUBLES,
-                                  (const char *)buf[b] + knn_block_meta_offset_dt(cap, n, ix->dtype),
-                                  KNN_META_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, NULL) != hipSuccess)
-            return KNN_ERR_HIP;
+        if (!s8) RCHK(read_meta(ix, buf[b], cap, ix->b.chm + b * KNN_META_DOUBLES));
         r += len;
     }
     return KNN_OK;
+}
+
+/* A write into resident blocks (add, update) in build_pack / build_finish's two
+ * parts: element rows and the touched blocks' meta, one wait, s8_stays of the
+ * candidate corpus meta, the byte rows where it does, a wait, commit_meta. */
+static int s8_stays(const knn_index_t *ix, const double *cmeta)
+{
+    return ix->have_s8 && knn_s8_spec_ok(cmeta, ix->n, ix->dtype);
+}
+
+static void commit_meta(knn_index_t *ix, const double *cmeta, int keep_s8)
+{
+    if (ix->have_s8 && !keep_s8) drop_s8(ix);
+    memcpy(ix->cmeta, cmeta, META_BYTES);
 }
 
 int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int src_dtype, const double *labels,
@@ -773,7 +758,7 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
 {
     if (!ix || !X || rows == 0) return KNN_ERR_INVALID;
     if (!knn_src_esize(src_dtype)) return KNN_ERR_UNSUPPORTED;
-    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (!layout_ok(layout)) return KNN_ERR_INVALID;
     if (flags & ~KNN_INDEX_DEVICE_SRC) return KNN_ERR_INVALID;
     if (rows > 0x7fffffffULL || ix->last_id + rows > 0x7fffffffULL) return KNN_ERR_INVALID;
     if ((ix->labels != NULL) != (labels != NULL)) return KNN_ERR_INVALID;
@@ -787,7 +772,7 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
         while ((m1 + ncap - 1) / ncap > KNN_I8_MAXBLK && ncap < fit) ncap = 2 * ncap < fit ? 2 * ncap : fit;
         RCHK(index_reblock(ix, ncap));
     }
-    const size_t nb0 = ix->nblk, nb1 = (m1 + ix->cap - 1) / ix->cap;
+    const size_t nb0 = ix->nblk, nb1 = (m1 + ix->cap - 1) / ix->cap, bf = ix->m / ix->cap;   /* bf: the first touched */
     RCHK(index_grow_arrays(ix, nb1));
     const size_t id1 = ix->last_id + rows;   /* (labels are indexed by id) */
     if (labels && id1 > ix->lab_cap) {
@@ -798,22 +783,17 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
         ix->lab_cap = lc;
     }
     if (ix->ids) RCHK(index_ids_reserve(ix, m1));
-    void *d_X = NULL;
-    int rc = KNN_OK;
-    if (!(flags & KNN_INDEX_DEVICE_SRC)) rc = upload(&d_X, X, rows * ix->n * knn_src_esize(src_dtype));
-    const void *src = (flags & KNN_INDEX_DEVICE_SRC) ? X : d_X;
-    /* build_pack / build_finish's two parts for the new rows: the element
-     * rows and the touched blocks' meta, one wait, the corpus meta, the byte
-     * rows while it still allows them */
-    if (!rc) rc = add_rows(ix, ix->blk, src, rows, layout, src_dtype, 0);
-    if (!rc) rc = stream_wait();
+    dev_src_t x = {0};
     double cmeta[KNN_META_DOUBLES];
     memcpy(cmeta, ix->cmeta, sizeof(cmeta));
     int keep_s8 = 0;
+    int rc = dev_src(&x, X, rows * ix->n * knn_src_esize(src_dtype), flags);
+    if (!rc) rc = add_rows(ix, ix->b.blk, x.src, rows, layout, src_dtype, 0);
+    if (!rc) rc = stream_wait();
     if (!rc) {
-        meta_max(cmeta, ix->chm + ix->m / ix->cap * KNN_META_DOUBLES, nb1 - ix->m / ix->cap);
-        keep_s8 = ix->have_s8 && knn_s8_spec_ok(cmeta, ix->n, ix->dtype);
-        if (keep_s8) rc = add_rows(ix, ix->s8, src, rows, layout, src_dtype, 1);
+        meta_max(cmeta, ix->b.chm + bf * KNN_META_DOUBLES, nb1 - bf);
+        keep_s8 = s8_stays(ix, cmeta);
+        if (keep_s8) rc = add_rows(ix, ix->b.s8, x.src, rows, layout, src_dtype, 1);
     }
     /* the new rows' ids last_id + 1 .. behind the live ones (entries past m
      * are read by nothing until m is committed below) */
@@ -826,33 +806,18 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
     /* the packs have read the source before the call returns */
     if (!rc) rc = stream_wait();
     else hipStreamSynchronize(NULL);
-    hipFree(d_X);
+    dev_src_free(&x);
     if (rc) {
         /* rows written past a block's nc are never read, and its meta only grew */
-        for (size_t b = nb0; b < nb1; b++) {
-            hipFree(ix->blk[b]);
-            hipFree(ix->s8[b]);
-            ix->blk[b] = ix->s8[b] = NULL;
-        }
+        blocks_release(ix->b.blk, ix->b.s8, nb0, nb1);
         return rc;
     }
-    if (ix->have_s8 && !keep_s8) {
-        /* a value outside the byte image arrived: the element path from now on */
-        for (size_t b = 0; b < nb0; b++) {
-            hipFree(ix->s8[b]);
-            ix->s8[b] = NULL;
-        }
-        ix->have_s8 = 0;
-    }
+    commit_meta(ix, cmeta, keep_s8);
     if (labels) memcpy(ix->labels + ix->last_id, labels, rows * sizeof(double));
-    memcpy(ix->cmeta, cmeta, sizeof(cmeta));
     ix->nblk = nb1;
     ix->m = m1;
     ix->last_id = id1;
-    for (size_t b = 0; b < nb1; b++) {
-        ix->cbase[b] = b * ix->cap;
-        ix->cnc[b] = m1 - ix->cbase[b] < ix->cap ? m1 - ix->cbase[b] : ix->cap;
-    }
+    set_counts(ix);
     return KNN_OK;
 }
 
@@ -862,69 +827,46 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
  * built again in a fresh, zeroed buffer by one gather a run (and one of the
  * byte rows where the index has byte blocks), its meta the max of the blocks
  * it drew from.  Old and new buffers are resident together until the one wait
- * at the end; on success the new ones are in nblk[] / ns8[] / nhm (entries
- * b0 .. nb1-1), on failure everything made here is freed. */
-static int remove_move(knn_index_t *ix, const knn_rm_plan_t *pl, void **nblk, void **ns8, double *nhm)
+ * at the end; on success the new ones are in g (entries b0 .. nb1-1), on
+ * failure everything made here is freed. */
+static int remove_move(knn_index_t *ix, const knn_rm_plan_t *pl, blocks_t *g)
 {
     const size_t n = ix->n, cap = ix->cap, b0 = pl->b0, nb1 = pl->nb1;
-    const size_t ebytes = knn_block_bytes_dt(cap, n, ix->dtype), sbytes = knn_s8_bytes(cap, n);
     int32_t *d_list = NULL;
-    double *hm = (double *)calloc(2 * (nb1 - b0) * KNN_META_DOUBLES, sizeof(double));   /* staged until the wait */
-    int rc = hm ? KNN_OK : KNN_ERR_NOMEM;
-    for (size_t b = b0; b < nb1 && !rc; b++) {
-        if (hipMalloc(&nblk[b], ebytes) != hipSuccess) rc = KNN_ERR_NOMEM;
-        else if (hipMemsetAsync(nblk[b], 0, ebytes, NULL) != hipSuccess) rc = KNN_ERR_HIP;
-        if (rc || !ix->have_s8) continue;
-        if (hipMalloc(&ns8[b], sbytes) != hipSuccess) rc = KNN_ERR_NOMEM;
-        else if (hipMemsetAsync(ns8[b], 0, sbytes, NULL) != hipSuccess) rc = KNN_ERR_HIP;
-    }
+    double *stage = (double *)calloc(2 * (nb1 - b0) * KNN_META_DOUBLES, sizeof(double));   /* until the wait */
+    int rc = stage ? fresh_blocks(ix, cap, b0, nb1, g->blk, g->s8, 1) : KNN_ERR_NOMEM;
     /* the runs' lists, one array */
     if (!rc && hipMalloc((void **)&d_list, pl->nlist * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
     if (!rc && hipMemcpyAsync(d_list, pl->list, pl->nlist * sizeof(int32_t), hipMemcpyHostToDevice, NULL) != hipSuccess)
         rc = KNN_ERR_HIP;
     for (size_t r = 0; r < pl->nruns && !rc; r++) {
         const knn_rm_run_t *run = &pl->runs[r];
-        rc = knn_block_gather_dt(nblk[run->nb], cap, run->dst0, ix->blk[run->ob], cap, d_list + run->list0, run->rows,
-                                 n, ix->dtype, NULL);
+        rc = knn_block_gather_dt(g->blk[run->nb], cap, run->dst0, ix->b.blk[run->ob], cap, d_list + run->list0,
+                                 run->rows, n, ix->dtype, NULL);
         if (!rc && ix->have_s8)
-            rc = knn_block_gather_s8(ns8[run->nb], cap, run->dst0, ix->s8[run->ob], cap, d_list + run->list0,
+            rc = knn_block_gather_s8(g->s8[run->nb], cap, run->dst0, ix->b.s8[run->ob], cap, d_list + run->list0,
                                      run->rows, n, NULL);
-        meta_max(nhm + run->nb * KNN_META_DOUBLES, ix->chm + run->ob * KNN_META_DOUBLES, 1);
+        meta_max(g->chm + run->nb * KNN_META_DOUBLES, ix->b.chm + run->ob * KNN_META_DOUBLES, 1);
     }
-    /* the trailing meta words, as index_reblock writes them (a later append
-     * takes its atomicMax into them) */
     for (size_t b = b0; b < nb1 && !rc; b++) {
-        double *e = hm + 2 * (b - b0) * KNN_META_DOUBLES, *s = e + KNN_META_DOUBLES;
-        memcpy(e, nhm + b * KNN_META_DOUBLES, KNN_META_DOUBLES * sizeof(double));
-        e[KNN_META_S8] = 0.0;
-        if (hipMemcpyAsync((char *)nblk[b] + knn_block_meta_offset_dt(cap, n, ix->dtype), e,
-                           KNN_META_DOUBLES * sizeof(double), hipMemcpyHostToDevice, NULL) != hipSuccess)
-            rc = KNN_ERR_HIP;
-        if (rc || !ix->have_s8) continue;
-        memcpy(s, e, KNN_META_DOUBLES * sizeof(double));
-        s[KNN_META_S8] = 1.0;
-        if (hipMemcpyAsync((char *)ns8[b] + knn_s8_meta_offset(cap, n), s, KNN_META_DOUBLES * sizeof(double),
-                           hipMemcpyHostToDevice, NULL) != hipSuccess)
-            rc = KNN_ERR_HIP;
+        const double *hm = g->chm + b * KNN_META_DOUBLES;
+        double *st = stage + 2 * (b - b0) * KNN_META_DOUBLES;
+        rc = write_meta_words((char *)g->blk[b] + knn_block_meta_offset_dt(cap, n, ix->dtype), hm, 0, st);
+        if (!rc && ix->have_s8)
+            rc = write_meta_words((char *)g->s8[b] + knn_s8_meta_offset(cap, n), hm, 1, st + KNN_META_DOUBLES);
     }
     if (!rc) rc = stream_wait();
     else hipStreamSynchronize(NULL);
     hipFree(d_list);
-    free(hm);
-    if (rc)
-        for (size_t b = b0; b < nb1; b++) {
-            hipFree(nblk[b]);
-            hipFree(ns8[b]);
-            nblk[b] = ns8[b] = NULL;
-        }
+    free(stage);
+    if (rc) blocks_release(g->blk, g->s8, b0, nb1);
     return rc;
 }
 
 int knn_index_remove(knn_index_t *ix, const int32_t *ids, size_t count, int flags, size_t *removed)
 {
     if (!ix || !ids || count == 0 || flags != 0) return KNN_ERR_INVALID;
-    for (size_t i = 0; i < count; i++)
-        if (ids[i] < 1 || (size_t)ids[i] > ix->last_id) return KNN_ERR_INVALID;
+    if (!ids_ok(ix, ids, count)) return KNN_ERR_INVALID;
     /* the plan, on the host alone (knn_remove_plan.h) */
     int32_t *pos = (int32_t *)malloc(count * sizeof(int32_t));
     if (!pos) return KNN_ERR_NOMEM;
@@ -944,56 +886,45 @@ int knn_index_remove(knn_index_t *ix, const int32_t *ids, size_t count, int flag
     /* the new id map beside the old one, and the moved blocks beside theirs */
     const size_t icap = ix->ids_cap > pl.m1 ? ix->ids_cap : pl.m1;
     int32_t *d_ids = NULL, *h_ids = NULL;
-    void **nblk = (void **)calloc(2 * ix->nblk, sizeof(void *)), **ns8 = nblk ? nblk + ix->nblk : NULL;
-    double *nhm = (double *)calloc(ix->nblk * KNN_META_DOUBLES, sizeof(double));
-    if (!rc && (!nblk || !nhm)) rc = KNN_ERR_NOMEM;
+    blocks_t g = {0};
+    if (!rc) rc = blocks_alloc(&g, ix->nblk);
     if (!rc && !(h_ids = (int32_t *)malloc(icap * sizeof(int32_t)))) rc = KNN_ERR_NOMEM;
     if (!rc && hipMalloc((void **)&d_ids, icap * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
     if (!rc) {
         memcpy(h_ids, pl.ids, pl.m1 * sizeof(int32_t));
         if (hipMemcpy(d_ids, h_ids, pl.m1 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = KNN_ERR_HIP;
     }
-    if (!rc && pl.moves) rc = remove_move(ix, &pl, nblk, ns8, nhm);
+    if (!rc && pl.moves) rc = remove_move(ix, &pl, &g);
     if (rc) {   /* the index answers as before the call */
         hipFree(d_ids);
         free(h_ids);
-        free(nblk);
-        free(nhm);
-        knn_rm_plan_free(&pl);
-        return rc;
-    }
-    /* commit: the moved blocks in place of the old ones, the blocks past the
-     * new count released, then m, cnc, cbase, nblk and the id map.  cmeta
-     * stays: a MAX that has only become too large is conservative. */
-    if (pl.moves)
-        for (size_t b = pl.b0; b < pl.nb1; b++) {
-            hipFree(ix->blk[b]);
-            hipFree(ix->s8[b]);
-            ix->blk[b] = nblk[b];
-            ix->s8[b] = ns8[b];
-            memcpy(ix->chm + b * KNN_META_DOUBLES, nhm + b * KNN_META_DOUBLES, KNN_META_DOUBLES * sizeof(double));
+    } else {
+        /* commit: the moved blocks in place of the old ones, the blocks past
+         * the new count released, then m, cnc, cbase, nblk and the id map.
+         * cmeta stays: a MAX that has only become too large is conservative. */
+        if (pl.moves) {
+            blocks_release(ix->b.blk, ix->b.s8, pl.b0, pl.nb1);
+            for (size_t b = pl.b0; b < pl.nb1; b++) {
+                ix->b.blk[b] = g.blk[b];
+                ix->b.s8[b] = g.s8[b];
+            }
+            memcpy(ix->b.chm + pl.b0 * KNN_META_DOUBLES, g.chm + pl.b0 * KNN_META_DOUBLES,
+                   (pl.nb1 - pl.b0) * META_BYTES);
         }
-    for (size_t b = pl.nb1; b < ix->nblk; b++) {
-        hipFree(ix->blk[b]);
-        hipFree(ix->s8[b]);
-        ix->blk[b] = ix->s8[b] = NULL;
+        blocks_release(ix->b.blk, ix->b.s8, pl.nb1, ix->nblk);
+        ix->m = pl.m1;
+        ix->nblk = pl.nb1;
+        set_counts(ix);
+        hipFree(ix->d_ids);
+        free(ix->ids);
+        ix->ids = h_ids;
+        ix->d_ids = d_ids;
+        ix->ids_cap = icap;
+        if (removed) *removed = pl.removed;
     }
-    ix->m = pl.m1;
-    ix->nblk = pl.nb1;
-    for (size_t b = 0; b < ix->nblk; b++) {
-        ix->cbase[b] = b * ix->cap;
-        ix->cnc[b] = ix->m - ix->cbase[b] < ix->cap ? ix->m - ix->cbase[b] : ix->cap;
-    }
-    hipFree(ix->d_ids);
-    free(ix->ids);
-    ix->ids = h_ids;
-    ix->d_ids = d_ids;
-    ix->ids_cap = icap;
-    if (removed) *removed = pl.removed;
-    free(nblk);
-    free(nhm);
+    blocks_free_arrays(&g);
     knn_rm_plan_free(&pl);
-    return KNN_OK;
+    return rc;
 }
 
 /* --------------------------------------------------------------- update */
@@ -1009,15 +940,12 @@ static int update_rows(knn_index_t *ix, const knn_up_plan_t *pl, const int32_t *
     for (size_t r = 0; r < pl->nruns; r++) {
         const knn_up_run_t *run = &pl->runs[r];
         const int32_t *pos = d_list + run->list0, *srow = d_list + count + run->list0;
-        void *blk = s8 ? ix->s8[run->blk] : ix->blk[run->blk];
+        void *blk = s8 ? ix->b.s8[run->blk] : ix->b.blk[run->blk];
         RCHK(s8 ? knn_block_scatter_s8(blk, ix->dtype, cap, pos, srow, run->rows, n, d_X, count, src_dtype, ld, layout,
                                        NULL)
                 : knn_block_scatter_dt(blk, ix->dtype, cap, pos, srow, run->rows, n, d_X, count, src_dtype, ld, layout,
                                        NULL));
-        if (!s8 && hipMemcpyAsync(ix->chm + run->blk * KNN_META_DOUBLES,
-                                  (const char *)blk + knn_block_meta_offset_dt(cap, n, ix->dtype),
-                                  KNN_META_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, NULL) != hipSuccess)
-            return KNN_ERR_HIP;
+        if (!s8) RCHK(read_meta(ix, blk, cap, ix->b.chm + run->blk * KNN_META_DOUBLES));
     }
     return KNN_OK;
 }
@@ -1027,11 +955,10 @@ int knn_index_update(knn_index_t *ix, const int32_t *ids, size_t count, const vo
 {
     if (!ix || !ids || !X || count == 0) return KNN_ERR_INVALID;
     if (!knn_src_esize(src_dtype)) return KNN_ERR_UNSUPPORTED;
-    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (!layout_ok(layout)) return KNN_ERR_INVALID;
     if (flags & ~KNN_INDEX_DEVICE_SRC) return KNN_ERR_INVALID;
     if (count > ix->m || (labels && !ix->labels)) return KNN_ERR_INVALID;   /* (more ids than live rows: a repeat) */
-    for (size_t i = 0; i < count; i++)
-        if (ids[i] < 1 || (size_t)ids[i] > ix->last_id) return KNN_ERR_INVALID;
+    if (!ids_ok(ix, ids, count)) return KNN_ERR_INVALID;
     /* the plan, on the host alone (knn_update_plan.h) */
     knn_up_plan_t pl;
     const int prc = knn_up_plan(&pl, ix->ids, ix->m, ix->cap, ids, count);
@@ -1039,56 +966,40 @@ int knn_index_update(knn_index_t *ix, const int32_t *ids, size_t count, const vo
     /* every allocation and upload in front of the first overwritten row: up
      * to there a failure leaves the index as it was */
     int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
-    void *d_X = NULL;
+    dev_src_t x = {0};
     int32_t *d_list = NULL;
-    if (!rc && !(flags & KNN_INDEX_DEVICE_SRC)) rc = upload(&d_X, X, count * ix->n * knn_src_esize(src_dtype));
+    if (!rc) rc = dev_src(&x, X, count * ix->n * knn_src_esize(src_dtype), flags);
     if (!rc && hipMalloc((void **)&d_list, 2 * count * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
     if (!rc && (hipMemcpy(d_list, pl.pos, count * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
                 hipMemcpy(d_list + count, pl.srow, count * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess))
         rc = KNN_ERR_HIP;
-    if (rc) {
-        hipFree(d_X);
-        hipFree(d_list);
-        knn_up_plan_free(&pl);
-        return rc;
-    }
-    const void *src = (flags & KNN_INDEX_DEVICE_SRC) ? X : d_X;
-    /* knn_index_add's two parts for the listed rows: the element rows and the
-     * touched blocks' meta, one wait, the corpus meta, the byte rows while it
-     * still allows them.  From here on a failure leaves rows half written:
-     * KNN_ERR_HIP, and the index is fit only for knn_index_destroy. */
-    rc = update_rows(ix, &pl, d_list, src, layout, src_dtype, 0);
-    if (!rc) rc = stream_wait();
+    /* From here on a failure leaves rows half written: KNN_ERR_HIP, and the
+     * index is fit only for knn_index_destroy. */
     double cmeta[KNN_META_DOUBLES];
     memcpy(cmeta, ix->cmeta, sizeof(cmeta));
     int keep_s8 = 0;
     if (!rc) {
-        for (size_t r = 0; r < pl.nruns; r++) meta_max(cmeta, ix->chm + pl.runs[r].blk * KNN_META_DOUBLES, 1);
-        keep_s8 = ix->have_s8 && knn_s8_spec_ok(cmeta, ix->n, ix->dtype);
-        if (keep_s8) rc = update_rows(ix, &pl, d_list, src, layout, src_dtype, 1);
-    }
-    /* the scatters have read the source and the lists before the call returns */
-    if (!rc) rc = stream_wait();
-    else hipStreamSynchronize(NULL);
-    hipFree(d_X);
-    hipFree(d_list);
-    if (rc) {
-        knn_up_plan_free(&pl);
-        return KNN_ERR_HIP;
-    }
-    if (ix->have_s8 && !keep_s8) {
-        /* a value outside the byte image arrived: the element path from now on */
-        for (size_t b = 0; b < ix->nblk; b++) {
-            hipFree(ix->s8[b]);
-            ix->s8[b] = NULL;
+        rc = update_rows(ix, &pl, d_list, x.src, layout, src_dtype, 0);
+        if (!rc) rc = stream_wait();
+        if (!rc) {
+            for (size_t r = 0; r < pl.nruns; r++) meta_max(cmeta, ix->b.chm + pl.runs[r].blk * KNN_META_DOUBLES, 1);
+            keep_s8 = s8_stays(ix, cmeta);
+            if (keep_s8) rc = update_rows(ix, &pl, d_list, x.src, layout, src_dtype, 1);
         }
-        ix->have_s8 = 0;
+        /* the scatters have read the source and the lists before the call returns */
+        if (!rc) rc = stream_wait();
+        else hipStreamSynchronize(NULL);
+        if (rc) rc = KNN_ERR_HIP;
     }
-    if (labels)
-        for (size_t i = 0; i < count; i++) ix->labels[ids[i] - 1] = labels[i];
-    memcpy(ix->cmeta, cmeta, sizeof(cmeta));
+    dev_src_free(&x);
+    hipFree(d_list);
+    if (!rc) {
+        commit_meta(ix, cmeta, keep_s8);
+        if (labels)
+            for (size_t i = 0; i < count; i++) ix->labels[ids[i] - 1] = labels[i];
+    }
     knn_up_plan_free(&pl);
-    return KNN_OK;
+    return rc;
 }
 
 /* ----------------------------------------------------------- neighbours */
@@ -1112,14 +1023,12 @@ int knn_index_update(knn_index_t *ix, const int32_t *ids, size_t count, const vo
  * zeros a pack leaves there: no kernel then computes on stale or never
  * written memory, whatever it does with the result.  The byte tile needs
  * nothing. */
-static int gather_tiles(knn_index_t *ix, const void *const *d_tab, const int32_t *d_pos, size_t mq, int s8)
+static int gather_tiles(knn_index_t *ix, const void *const *d_tab, const int32_t *d_pos, const batch_t *bt, int s8)
 {
     const size_t n = ix->n, es = knn_esize(ix->dtype), np = knn_n_pad_dt(n, ix->dtype);
     const size_t trp = knn_rows_pad(ix->tile_cap);
-    size_t tcap, ntile;
-    tile_shape(ix, mq, &tcap, &ntile);
-    for (size_t t = 0; t < ntile; t++) {
-        const size_t r0 = t * tcap, rows = mq - r0 < tcap ? mq - r0 : tcap;
+    for (size_t t = 0; t < bt->ntile; t++) {
+        const size_t r0 = t * bt->tcap, rows = bt->mq - r0 < bt->tcap ? bt->mq - r0 : bt->tcap;
         const size_t pad = knn_round_up(rows, KNN_TQ) - rows;   /* (round_up(rows, KNN_TQ) <= trp) */
         char *blk = (char *)ix->tblk[t];
         RCHK(knn_block_gather_pos_dt(blk, ix->tile_cap, 0, d_tab, ix->cap, ix->nblk, d_pos + r0, rows, n, ix->dtype,
@@ -1141,12 +1050,10 @@ int knn_index_neighbours(knn_index_t *ix, const int32_t *ids, size_t count, int 
     /* keep-zero: the row itself comes back among its own neighbours and is
      * taken out afterwards, so the engine searches one more */
     const int kz = (flags & KNN_QUERY_KEEP_ZERO) != 0, dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
-    if (k > (ix->dtype == KNN_F32 ? KNN_MAX_K_F32 : KNN_MAX_K) - kz) return KNN_ERR_UNSUPPORTED;
-    const int ke = k + kz;
+    if (k > k_max(ix->dtype) - kz) return KNN_ERR_UNSUPPORTED;
     const size_t mq = ids ? count : ix->m;
     if (mq > 0x7fffffffULL || ix->m + mq > 0x7fffffffULL) return KNN_ERR_INVALID;
-    for (size_t i = 0; i < count; i++)
-        if (ids[i] < 1 || (size_t)ids[i] > ix->last_id) return KNN_ERR_INVALID;
+    if (!ids_ok(ix, ids, count)) return KNN_ERR_INVALID;
     /* the positions, on the host alone (knn_neighbours_plan.h) */
     int32_t *pos = (int32_t *)malloc(mq * sizeof(int32_t));
     if (!pos) return KNN_ERR_NOMEM;
@@ -1154,62 +1061,41 @@ int knn_index_neighbours(knn_index_t *ix, const int32_t *ids, size_t count, int 
         free(pos);
         return KNN_ERR_INVALID;
     }
-    const size_t n = ix->n, cnt = mq * (size_t)k, wide = kz ? mq * (size_t)ke : 0;
+    const size_t cnt = mq * (size_t)k, wide = kz ? mq * (size_t)(k + 1) : 0;
+    const batch_t bt = tile_shape(ix, mq);
     int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
     /* every allocation and upload in front of the span: the positions, the
      * blocks' pointers (element, then byte), the records of a host-out call
      * and behind them the k + 1 wide ones of a keep-zero call */
-    const int use_s8 = ix->have_s8 && knn_s8_spec_ok(ix->cmeta, n, ix->dtype);
+    const int use_s8 = s8_stays(ix, ix->cmeta);
     int32_t *d_pos = NULL;
     void **d_tab = NULL;
     if (!rc) rc = index_out(ix, (dev_out ? 0 : cnt) + wide);
     if (!rc && hipMalloc((void **)&d_pos, mq * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
     if (!rc && hipMalloc((void **)&d_tab, 2 * ix->nblk * sizeof(void *)) != hipSuccess) rc = KNN_ERR_NOMEM;
     if (!rc && (hipMemcpy(d_pos, pos, mq * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_tab, ix->blk, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_tab + ix->nblk, ix->s8, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess))
+                hipMemcpy(d_tab, ix->b.blk, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(d_tab + ix->nblk, ix->b.s8, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess))
         rc = KNN_ERR_HIP;
     free(pos);
-    if (!rc) rc = index_reserve(ix, mq, ke, 1);
-    size_t tcap = 0, ntile = 0;
-    if (!rc) tile_shape(ix, mq, &tcap, &ntile);
-    for (size_t t = 0; t < ntile && !rc && use_s8; t++)
-        if (!ix->ts8[t] && hipMalloc(&ix->ts8[t], knn_s8_bytes(ix->tile_cap, n)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc) rc = index_reserve(ix, &bt, k + kz, 1);
+    if (!rc && use_s8) rc = reserve_ts8(ix, bt.ntile);
+    knn_neighbour_t *d_out = dev_out ? out : ix->d_out;
+    knn_neighbour_t *d_rec = d_out;   /* what the tiles write */
+    if (!rc && kz) d_rec = ix->d_out + (dev_out ? 0 : cnt);
     if (!rc) {
-        knn_neighbour_t *d_out = dev_out ? out : ix->d_out;
-        knn_neighbour_t *d_rec = kz ? ix->d_out + (dev_out ? 0 : cnt) : d_out;   /* what the tiles write */
         hipEventRecord(ix->e0, NULL);
         /* the batch's reduced meta is the corpus's: the queries are corpus
          * rows and cmeta only grows.  No tile meta is read back, so the host
          * does not wait between the gathers and the searches. */
-        memcpy(ix->red, ix->cmeta, KNN_META_DOUBLES * sizeof(double));
-        if (hipMemcpyAsync(ix->d_meta, ix->red, KNN_META_DOUBLES * sizeof(double), hipMemcpyHostToDevice, NULL) !=
-            hipSuccess)
-            rc = KNN_ERR_HIP;
-        if (!rc) rc = gather_tiles(ix, (const void *const *)d_tab, d_pos, mq, use_s8);
+        rc = put_meta(ix, NULL, 0);
+        if (!rc) rc = gather_tiles(ix, (const void *const *)d_tab, d_pos, &bt, use_s8);
         knn_ctx_set_keep_zero(ix->ctx, kz);
-        for (size_t t = 0; t < ntile && !rc; t++) {
-            const size_t r0 = t * tcap, rows = mq - r0 < tcap ? mq - r0 : tcap;
-            rc = query_tile(ix->ctx, ix->nblk, ix->blk, use_s8 ? ix->s8 : NULL, ix->cnc, ix->cbase, ix->tblk[t],
-                            use_s8 ? ix->ts8[t] : NULL, ix->tile_cap, rows, ix->m + r0, ix->d_meta, ix->red,
-                            d_rec + r0 * (size_t)ke);
-        }
-        if (!rc) ix->last_bits = knn_ctx_contraction_bits(ix->ctx);
-        /* keep-zero: the row itself out of its k + 1 records, positions -> ids
-         * in the same pass; else the ids as knn_index_query writes them */
-        if (!rc && kz) rc = knn_launch_drop_self(d_out, d_rec, d_pos, mq, k, ix->ids ? ix->d_ids : NULL, ix->m, NULL);
-        else if (!rc && ix->ids) rc = knn_launch_remap_idx(d_out, cnt, ix->d_ids, ix->m, NULL);
-        if (!rc) rc = span_end(ix);
-        if (!rc && !dev_out && hipMemcpy(out, d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
-            rc = KNN_ERR_HIP;
+        if (!rc) rc = search_tiles(ix, &bt, use_s8, d_rec);
     }
-    if (rc) {   /* nothing of a failed call is kept */
-        hipStreamSynchronize(NULL);
-        free_query_state(ix);
-    }
+    rc = finish_search(ix, rc, out, dev_out, d_out, d_rec, d_pos, mq, k);
     hipFree(d_pos);
     hipFree(d_tab);
-    if (!rc && !dev_out && ix->labels) fill_labels(out, cnt, ix->labels);
     return rc;
 }
 
@@ -1228,7 +1114,7 @@ int knn_index_info(const knn_index_t *ix, size_t *m, size_t *n, int *nblocks, si
     if (nblocks) *nblocks = (int)ix->nblk;
     if (last_bits) *last_bits = ix->last_bits;
     if (device_bytes) {
-        size_t b = ix->nblk * knn_block_bytes_dt(ix->cap, ix->n, ix->dtype) + KNN_META_DOUBLES * sizeof(double);
+        size_t b = ix->nblk * knn_block_bytes_dt(ix->cap, ix->n, ix->dtype) + META_BYTES;
         if (ix->have_s8) b += ix->nblk * knn_s8_bytes(ix->cap, ix->n);
         for (size_t t = 0; t < ix->ntile; t++) {
             if (ix->tblk[t]) b += knn_block_bytes_dt(ix->tile_cap, ix->n, ix->dtype);
@@ -1257,38 +1143,39 @@ int knn_query(const double *X, size_t m, const double *Q, size_t mq, size_t n, i
 {
     if (!X || !Q || !out || m == 0 || mq == 0 || n == 0 || k <= 0) return KNN_ERR_INVALID;
     if (!dtype_ok(dtype)) return KNN_ERR_UNSUPPORTED;
-    if (k > (dtype == KNN_F32 ? KNN_MAX_K_F32 : KNN_MAX_K)) return KNN_ERR_UNSUPPORTED;
-    if (layout != KNN_COLMAJOR && layout != KNN_ROWMAJOR) return KNN_ERR_INVALID;
+    if (k > k_max(dtype)) return KNN_ERR_UNSUPPORTED;
+    if (!layout_ok(layout)) return KNN_ERR_INVALID;
     if (flags & ~KNN_QUERY_KEEP_ZERO) return KNN_ERR_INVALID;
     if (m > 0x7fffffffULL || mq > 0x7fffffffULL || m + mq > 0x7fffffffULL || n > 0x7fffffffULL)
         return KNN_ERR_INVALID;
     knn_index_t *ix = NULL;
     RCHK(index_alloc(&ix, m, n, dtype));
     const size_t cnt = mq * (size_t)k;
-    void *d_X = NULL, *d_Q = NULL;
+    const batch_t bt = tile_shape(ix, mq);
+    dev_src_t x = {0}, q = {0};
     /* every allocation, then the uploads: the span starts behind a copy, with
      * no fresh memory still to be mapped in front of its first kernel */
-    int rc = index_reserve(ix, mq, k, 0);
+    int rc = index_reserve(ix, &bt, k, 0);
     if (!rc) rc = index_out(ix, cnt);
     if (!rc) rc = index_alloc_blocks(ix);
-    if (!rc) rc = upload(&d_X, X, m * n * sizeof(double));
-    if (!rc) rc = upload(&d_Q, Q, mq * n * sizeof(double));
+    if (!rc) rc = dev_src(&x, X, m * n * sizeof(double), 0);
+    if (!rc) rc = dev_src(&q, Q, mq * n * sizeof(double), 0);
     if (!rc) {
         /* every block and tile packed, one wait for their meta, then the byte
          * forms and the searches */
         hipEventRecord(ix->e0, NULL);
-        rc = build_pack(ix, d_X, layout, KNN_F64);
-        if (!rc) rc = run_pack(ix, d_Q, mq, layout, KNN_F64);
+        rc = build_pack(ix, x.src, layout, KNN_F64);
+        if (!rc) rc = run_pack(ix, q.src, &bt, layout, KNN_F64);
         if (!rc) rc = stream_wait();
-        if (!rc) rc = build_finish(ix, d_X, layout, KNN_F64, ix->thm, ix->ntile);
-        if (!rc) rc = run_finish(ix, d_Q, mq, layout, KNN_F64, flags, ix->d_out);
+        if (!rc) rc = build_finish(ix, x.src, layout, KNN_F64, ix->thm, ix->ntile);
+        if (!rc) rc = run_finish(ix, q.src, &bt, layout, KNN_F64, flags, ix->d_out);
         if (!rc) rc = span_end(ix);
     }
     if (!rc && hipMemcpy(out, ix->d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
         rc = KNN_ERR_HIP;
     if (rc) hipStreamSynchronize(NULL);
-    hipFree(d_X);
-    hipFree(d_Q);
+    dev_src_free(&x);
+    dev_src_free(&q);
     index_free(ix);
     if (!rc && labels) fill_labels(out, cnt, labels);
     return rc;

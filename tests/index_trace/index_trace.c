@@ -1,0 +1,950 @@
+/*
+ * index_trace.c -- knn_index.c's device calls, traced on a CPU, and its
+ * failure paths swept.
+ *
+ * A stand-alone program: linked with knn_index.c and knn_blocks.c and nothing
+ * of HIP.  It stubs the hip* calls those files use, the engine boundary they
+ * call (knn_ctx_*, knn_block_pack_*, knn_device_probe) and the knn_launch_*
+ * launchers; the size and predicate helpers (knn_block_bytes_dt,
+ * knn_block_meta_offset_dt, knn_s8_spec_ok) are knn_engine.c's own: that file
+ * is linked behind this one, the definitions here win, and what nothing
+ * references is dropped (test_index_trace.py has the link line).
+ *
+ * hipMalloc returns zeroed host memory, entered in a live set under an
+ * ordinal name (A1, A2, ...; pinned memory P, events E, the caller's own
+ * device buffers U); hipFree of a pointer that is neither live nor NULL ends
+ * the program.  The copies and memsets copy and set, checked against the live
+ * set.  The pack, append and scatter stubs write the meta the step chose into
+ * the block's meta words -- 8-bit integer data (knn_s8_spec_ok holds) or real
+ * data -- and knn_ctx_end reports the unresolved count the step chose, so the
+ * index decides its paths as on a device.  Every stub appends one line to the
+ * trace: its name and its arguments, pointers as name+offset ("H": host
+ * memory, "0": NULL).
+ *
+ *   index_trace             every scenario's trace ("## name" opens one,
+ *                           "# ..." marks each call into the index)
+ *   index_trace NAME...     the named ones
+ *   index_trace --sweep     the fault sweep; exit status 1 on a violation
+ *
+ * The sweep: the stubs count every call whose failure the index can see
+ * (hipMalloc, hipHostMalloc, copies, memsets, launchers, knn_ctx_*), and can
+ * fail the N-th with its natural error.  For every step but a destroy, with C
+ * its count on a clean run, and for N = 1 .. C, the step runs on a rebuilt
+ * pre-state with fault N and must: return non-zero; free nothing twice; leave
+ * knn_index_info's m and block count and knn_index_last_id as they were (the
+ * block count may be the reblocked one when an add failed behind its
+ * reblock); leave live exactly the device bytes knn_index_info accounts for
+ * -- the blocks, the id map, and whatever query state the index still owns
+ * (a failed search may drop it; record buffer and id map may have grown);
+ * succeed on a clean retry whose trace from the first enqueue on (allocations
+ * aside, names in order of appearance) is that of a first clean run, or its
+ * end where the failed call's reblock stayed; and leave nothing live behind
+ * knn_index_destroy.  A knn_index_update that failed behind its first
+ * enqueued scatter is fit only for destroy: return value, frees and the
+ * empty live set alone are checked.
+ */
+#include <hip/hip_runtime_api.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "knn_internal.h"
+
+#define DIE(...)                                  \
+    do {                                          \
+        fprintf(stderr, "index_trace: " __VA_ARGS__); \
+        fprintf(stderr, "\n");                    \
+        exit(2);                                  \
+    } while (0)
+
+/* ---- the trace ---------------------------------------------------------- */
+
+#define MAX_LINES 8192
+static char *g_line[MAX_LINES];
+static int g_nline, g_echo;
+
+static void L(const char *fmt, ...)
+{
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    if (g_echo) puts(buf);
+    if (g_nline == MAX_LINES) DIE("trace too long");
+    if (!(g_line[g_nline++] = strdup(buf))) DIE("out of memory");
+}
+
+static void lines_clear(void)
+{
+    for (int i = 0; i < g_nline; i++) free(g_line[i]);
+    g_nline = 0;
+}
+
+/* ---- the live set ------------------------------------------------------- */
+
+#define MAX_LIVE 1024
+static struct {
+    char *base;
+    size_t size;
+    int ord;
+    char kind;   /* A: hipMalloc, P: hipHostMalloc, U: the caller's buffers */
+} g_live[MAX_LIVE];
+static int g_nlive, g_ord[128];
+
+static int live_find(const void *p)
+{
+    for (int i = 0; i < g_nlive; i++)
+        if ((const char *)p >= g_live[i].base && (const char *)p < g_live[i].base + g_live[i].size) return i;
+    return -1;
+}
+
+static void *live_new(size_t size, char kind)
+{
+    if (g_nlive == MAX_LIVE) DIE("live set full");
+    char *p = (char *)calloc(size ? size : 1, 1);
+    if (!p) DIE("out of memory");
+    g_live[g_nlive].base = p;
+    g_live[g_nlive].size = size ? size : 1;
+    g_live[g_nlive].ord = ++g_ord[(int)kind];
+    g_live[g_nlive++].kind = kind;
+    return p;
+}
+
+static void live_free(void *p, const char *who)
+{
+    const int i = live_find(p);
+    if (i < 0 || g_live[i].base != (char *)p) DIE("%s of a pointer that is not live", who);
+    free(p);
+    g_live[i] = g_live[--g_nlive];
+}
+
+static size_t live_bytes(char kind)
+{
+    size_t b = 0;
+    for (int i = 0; i < g_nlive; i++)
+        if (g_live[i].kind == kind) b += g_live[i].size;
+    return b;
+}
+
+/* a pointer's name (up to 8 of them in one line) */
+static const char *N(const void *p)
+{
+    static char buf[8][48];
+    static int at;
+    char *s = buf[at++ % 8];
+    const int i = p ? live_find(p) : -1;
+    if (!p) return "0";
+    if (i < 0) return "H";
+    const size_t off = (size_t)((const char *)p - g_live[i].base);
+    if (off) snprintf(s, 48, "%c%d+%zu", g_live[i].kind, g_live[i].ord, off);
+    else snprintf(s, 48, "%c%d", g_live[i].kind, g_live[i].ord);
+    return s;
+}
+
+/* [p, p + bytes) lies in one live allocation */
+static void need(const void *p, size_t bytes, const char *who)
+{
+    const int i = p ? live_find(p) : -1;
+    if (i < 0 || (const char *)p + bytes > g_live[i].base + g_live[i].size)
+        DIE("%s: %zu bytes at %s are not inside a live allocation", who, bytes, N(p));
+}
+
+/* ---- the fault knob ----------------------------------------------------- */
+
+static long g_calls, g_fail_at;
+static int g_scattered, g_fault_behind_scatter;
+
+#define FALLIBLE(name, err)                           \
+    do {                                              \
+        if (++g_calls == g_fail_at) {                 \
+            g_fault_behind_scatter = g_scattered;     \
+            L("! %s", name);                          \
+            return err;                               \
+        }                                             \
+    } while (0)
+
+/* ---- HIP ---------------------------------------------------------------- */
+
+static int g_nevents;
+
+hipError_t hipSetDevice(int d) { L("hipSetDevice %d", d); return hipSuccess; }
+
+hipError_t hipMalloc(void **p, size_t size)
+{
+    FALLIBLE("hipMalloc", hipErrorOutOfMemory);
+    *p = live_new(size, 'A');
+    L("hipMalloc %s %zu", N(*p), size);
+    return hipSuccess;
+}
+
+hipError_t hipFree(void *p)
+{
+    if (!p) return hipSuccess;
+    L("hipFree %s", N(p));
+    live_free(p, "hipFree");
+    return hipSuccess;
+}
+
+hipError_t hipHostMalloc(void **p, size_t size, unsigned int flags)
+{
+    (void)flags;
+    FALLIBLE("hipHostMalloc", hipErrorOutOfMemory);
+    *p = live_new(size, 'P');
+    L("hipHostMalloc %s %zu", N(*p), size);
+    return hipSuccess;
+}
+
+hipError_t hipHostFree(void *p)
+{
+    L("hipHostFree %s", N(p));
+    live_free(p, "hipHostFree");
+    return hipSuccess;
+}
+
+static void copy(const char *who, void *dst, const void *src, size_t n, hipMemcpyKind kind)
+{
+    if (kind != hipMemcpyDeviceToHost) need(dst, n, who);
+    if (kind != hipMemcpyHostToDevice) need(src, n, who);
+    memmove(dst, src, n);
+}
+
+hipError_t hipMemcpy(void *dst, const void *src, size_t n, hipMemcpyKind kind)
+{
+    FALLIBLE("hipMemcpy", hipErrorInvalidValue);
+    L("hipMemcpy %s %s %zu %d", N(dst), N(src), n, (int)kind);
+    copy("hipMemcpy", dst, src, n, kind);
+    return hipSuccess;
+}
+
+hipError_t hipMemcpyAsync(void *dst, const void *src, size_t n, hipMemcpyKind kind, hipStream_t s)
+{
+    FALLIBLE("hipMemcpyAsync", hipErrorInvalidValue);
+    L("hipMemcpyAsync %s %s %zu %d %s", N(dst), N(src), n, (int)kind, N(s));
+    copy("hipMemcpyAsync", dst, src, n, kind);
+    return hipSuccess;
+}
+
+hipError_t hipMemsetAsync(void *dst, int v, size_t n, hipStream_t s)
+{
+    FALLIBLE("hipMemsetAsync", hipErrorInvalidValue);
+    L("hipMemsetAsync %s %d %zu %s", N(dst), v, n, N(s));
+    need(dst, n, "hipMemsetAsync");
+    memset(dst, v, n);
+    return hipSuccess;
+}
+
+hipError_t hipStreamSynchronize(hipStream_t s) { L("hipStreamSynchronize %s", N(s)); return hipSuccess; }
+
+/* an event: its ordinal */
+static const char *EV(hipEvent_t e)
+{
+    static char buf[4][16];
+    static int at;
+    char *s = buf[at++ % 4];
+    snprintf(s, 16, "E%d", *(int *)e);
+    return s;
+}
+
+hipError_t hipEventCreate(hipEvent_t *e)
+{
+    int *p = (int *)malloc(sizeof(int));
+    if (!p) DIE("out of memory");
+    *p = ++g_ord['E'];
+    g_nevents++;
+    *e = (hipEvent_t)p;
+    L("hipEventCreate %s", EV(*e));
+    return hipSuccess;
+}
+hipError_t hipEventDestroy(hipEvent_t e) { L("hipEventDestroy %s", EV(e)); free(e); g_nevents--; return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { L("hipEventRecord %s %s", EV(e), N(s)); return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t e) { L("hipEventSynchronize %s", EV(e)); return hipSuccess; }
+hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b)
+{
+    L("hipEventElapsedTime %s %s", EV(a), EV(b));
+    *ms = 0.f;
+    return hipSuccess;
+}
+
+/* ---- the engine boundary ------------------------------------------------ */
+
+enum { INT8, REAL };   /* the data a step's packs, appends and scatters see */
+static int g_kind;
+static size_t g_unres_end, g_unres_research;
+
+/* a writer's meta into the block's meta words: set (a pack) or MAX-ed in */
+static void write_meta(void *blk, size_t off, size_t n, int s8, int set, const char *who)
+{
+    double v[KNN_META_DOUBLES] = {0};
+    need(blk, off + sizeof(v), who);
+    if (g_kind == INT8) {   /* integers in [0, 255] */
+        v[KNN_META_MAXABS] = v[KNN_META_MAXPOS] = 255.0;
+        v[KNN_META_MAXNORM] = 255.0 * 255.0 * (double)n;
+    } else {                /* real values in (-1, 1) */
+        v[KNN_META_MAXABS] = v[KNN_META_MAXPOS] = v[KNN_META_MAXNEG] = 0.75;
+        v[KNN_META_MAXNORM] = (double)n;
+        v[KNN_META_NONINT] = 1.0;
+    }
+    v[KNN_META_S8] = s8;
+    double *m = (double *)((char *)blk + off);
+    for (int j = 0; j < KNN_META_DOUBLES; j++)
+        if (set || v[j] > m[j]) m[j] = v[j];
+}
+
+int knn_device_probe(int device, int *cus)
+{
+    L("knn_device_probe %d", device);
+    if (cus) *cus = 256;
+    return KNN_OK;
+}
+
+void knn_set_last_search_seconds(double s) { L("knn_set_last_search_seconds %g", s); }
+
+int knn_block_pack_dt(void *blk, int dtype, size_t cap, size_t rows, size_t n, const void *src, int src_dtype,
+                      size_t ld, int layout, void *stream)
+{
+    FALLIBLE("knn_block_pack_dt", KNN_ERR_HIP);
+    L("knn_block_pack_dt %s %d %zu %zu %zu %s %d %zu %d %s", N(blk), dtype, cap, rows, n, N(src), src_dtype, ld, layout,
+      N(stream));
+    write_meta(blk, knn_block_meta_offset_dt(cap, n, dtype), n, 0, 1, "knn_block_pack_dt");
+    return KNN_OK;
+}
+
+int knn_block_pack_s8(void *blk, int dtype, size_t cap, size_t rows, size_t n, const void *src, int src_dtype,
+                      size_t ld, int layout, void *stream)
+{
+    FALLIBLE("knn_block_pack_s8", KNN_ERR_HIP);
+    L("knn_block_pack_s8 %s %d %zu %zu %zu %s %d %zu %d %s", N(blk), dtype, cap, rows, n, N(src), src_dtype, ld, layout,
+      N(stream));
+    write_meta(blk, knn_s8_meta_offset(cap, n), n, 1, 1, "knn_block_pack_s8");
+    return KNN_OK;
+}
+
+int knn_launch_append(void *blk, int dtype, size_t cap, size_t row0, size_t rows, size_t n, const void *src,
+                      int src_dtype, size_t ld, int layout, void *stream)
+{
+    FALLIBLE("knn_launch_append", KNN_ERR_HIP);
+    L("knn_launch_append %s %d %zu %zu %zu %zu %s %d %zu %d %s", N(blk), dtype, cap, row0, rows, n, N(src), src_dtype,
+      ld, layout, N(stream));
+    write_meta(blk, knn_block_meta_offset_dt(cap, n, dtype), n, 0, 0, "knn_launch_append");
+    return KNN_OK;
+}
+
+int knn_launch_append_s8(void *blk, int dtype, size_t cap, size_t row0, size_t rows, size_t n, const void *src,
+                         int src_dtype, size_t ld, int layout, void *stream)
+{
+    FALLIBLE("knn_launch_append_s8", KNN_ERR_HIP);
+    L("knn_launch_append_s8 %s %d %zu %zu %zu %zu %s %d %zu %d %s", N(blk), dtype, cap, row0, rows, n, N(src),
+      src_dtype, ld, layout, N(stream));
+    write_meta(blk, knn_s8_meta_offset(cap, n), n, 1, 0, "knn_launch_append_s8");
+    return KNN_OK;
+}
+
+int knn_launch_scatter(void *blk, int dtype, size_t cap, const int32_t *pos, const int32_t *srow, size_t rows,
+                       size_t n, const void *src, size_t src_rows, int src_dtype, size_t ld, int layout, void *stream)
+{
+    FALLIBLE("knn_launch_scatter", KNN_ERR_HIP);
+    L("knn_launch_scatter %s %d %zu %s %s %zu %zu %s %zu %d %zu %d %s", N(blk), dtype, cap, N(pos), N(srow), rows, n,
+      N(src), src_rows, src_dtype, ld, layout, N(stream));
+    need(pos, rows * sizeof(int32_t), "knn_launch_scatter");
+    write_meta(blk, knn_block_meta_offset_dt(cap, n, dtype), n, 0, 0, "knn_launch_scatter");
+    g_scattered = 1;
+    return KNN_OK;
+}
+
+int knn_launch_scatter_s8(void *blk, int dtype, size_t cap, const int32_t *pos, const int32_t *srow, size_t rows,
+                          size_t n, const void *src, size_t src_rows, int src_dtype, size_t ld, int layout,
+                          void *stream)
+{
+    FALLIBLE("knn_launch_scatter_s8", KNN_ERR_HIP);
+    L("knn_launch_scatter_s8 %s %d %zu %s %s %zu %zu %s %zu %d %zu %d %s", N(blk), dtype, cap, N(pos), N(srow), rows, n,
+      N(src), src_rows, src_dtype, ld, layout, N(stream));
+    need(pos, rows * sizeof(int32_t), "knn_launch_scatter_s8");
+    write_meta(blk, knn_s8_meta_offset(cap, n), n, 1, 0, "knn_launch_scatter_s8");
+    g_scattered = 1;
+    return KNN_OK;
+}
+
+int knn_launch_gather(void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap, const int32_t *list,
+                      size_t rows, size_t n, int dtype, void *stream)
+{
+    FALLIBLE("knn_launch_gather", KNN_ERR_HIP);
+    L("knn_launch_gather %s %zu %zu %s %zu %s %zu %zu %d %s", N(dst), dst_cap, row0, N(src), src_cap, N(list), rows, n,
+      dtype, N(stream));
+    need(dst, knn_block_bytes_dt(dst_cap, n, dtype), "knn_launch_gather");
+    need(src, knn_block_bytes_dt(src_cap, n, dtype), "knn_launch_gather");
+    need(list, rows * sizeof(int32_t), "knn_launch_gather");
+    return KNN_OK;
+}
+
+int knn_launch_gather_rows8(void *dst, size_t dst_cap, size_t row0, const void *src, size_t src_cap,
+                            const int32_t *list, size_t rows, size_t n, void *stream)
+{
+    FALLIBLE("knn_launch_gather_rows8", KNN_ERR_HIP);
+    L("knn_launch_gather_rows8 %s %zu %zu %s %zu %s %zu %zu %s", N(dst), dst_cap, row0, N(src), src_cap, N(list), rows,
+      n, N(stream));
+    need(dst, knn_s8_bytes(dst_cap, n), "knn_launch_gather_rows8");
+    need(src, knn_s8_bytes(src_cap, n), "knn_launch_gather_rows8");
+    need(list, rows * sizeof(int32_t), "knn_launch_gather_rows8");
+    return KNN_OK;
+}
+
+int knn_launch_gather_pos(void *dst, size_t dst_cap, size_t row0, const void *const *tab, size_t src_cap, size_t nblk,
+                          const int32_t *pos, size_t rows, size_t n, int dtype, void *stream)
+{
+    FALLIBLE("knn_launch_gather_pos", KNN_ERR_HIP);
+    L("knn_launch_gather_pos %s %zu %zu %s %zu %zu %s %zu %zu %d %s", N(dst), dst_cap, row0, N(tab), src_cap, nblk,
+      N(pos), rows, n, dtype, N(stream));
+    need(dst, knn_block_bytes_dt(dst_cap, n, dtype), "knn_launch_gather_pos");
+    need(tab, nblk * sizeof(void *), "knn_launch_gather_pos");
+    need(pos, rows * sizeof(int32_t), "knn_launch_gather_pos");
+    return KNN_OK;
+}
+
+int knn_launch_gather_pos8(void *dst, size_t dst_cap, size_t row0, const void *const *tab, size_t src_cap,
+                           size_t nblk, const int32_t *pos, size_t rows, size_t n, void *stream)
+{
+    FALLIBLE("knn_launch_gather_pos8", KNN_ERR_HIP);
+    L("knn_launch_gather_pos8 %s %zu %zu %s %zu %zu %s %zu %zu %s", N(dst), dst_cap, row0, N(tab), src_cap, nblk, N(pos),
+      rows, n, N(stream));
+    need(dst, knn_s8_bytes(dst_cap, n), "knn_launch_gather_pos8");
+    need(tab, nblk * sizeof(void *), "knn_launch_gather_pos8");
+    need(pos, rows * sizeof(int32_t), "knn_launch_gather_pos8");
+    return KNN_OK;
+}
+
+int knn_launch_shadow8(void *dst, const void *blk, int dtype, size_t rows_pad, size_t n, const double *meta,
+                       void *stream)
+{
+    FALLIBLE("knn_launch_shadow8", KNN_ERR_HIP);
+    L("knn_launch_shadow8 %s %s %d %zu %zu %s %s", N(dst), N(blk), dtype, rows_pad, n, N(meta), N(stream));
+    need(dst, rows_pad * knn_s8_rs(n) + rows_pad * 8, "knn_launch_shadow8");
+    return KNN_OK;
+}
+
+int knn_launch_remap_idx(knn_neighbour_t *nb, size_t cnt, const int32_t *ids, size_t nids, void *stream)
+{
+    FALLIBLE("knn_launch_remap_idx", KNN_ERR_HIP);
+    L("knn_launch_remap_idx %s %zu %s %zu %s", N(nb), cnt, N(ids), nids, N(stream));
+    need(nb, cnt * sizeof(*nb), "knn_launch_remap_idx");
+    need(ids, nids * sizeof(int32_t), "knn_launch_remap_idx");
+    return KNN_OK;
+}
+
+int knn_launch_drop_self(knn_neighbour_t *out, const knn_neighbour_t *in, const int32_t *pos, size_t nq, int k,
+                         const int32_t *ids, size_t nids, void *stream)
+{
+    FALLIBLE("knn_launch_drop_self", KNN_ERR_HIP);
+    L("knn_launch_drop_self %s %s %s %zu %d %s %zu %s", N(out), N(in), N(pos), nq, k, N(ids), nids, N(stream));
+    need(out, nq * (size_t)k * sizeof(*out), "knn_launch_drop_self");
+    need(in, nq * (size_t)(k + 1) * sizeof(*in), "knn_launch_drop_self");
+    return KNN_OK;
+}
+
+/* the context: one device buffer, and the form of its last begin */
+struct knn_ctx {
+    void *buf;
+    int s8;
+};
+#define CTX_BYTES 4096
+static int g_nctx;
+
+int knn_ctx_create_dt(knn_ctx_t **out, int device, size_t nq, size_t n, size_t block_cap, int k, int dtype)
+{
+    FALLIBLE("knn_ctx_create_dt", KNN_ERR_NOMEM);
+    knn_ctx_t *c = (knn_ctx_t *)calloc(1, sizeof(*c));
+    if (!c) DIE("out of memory");
+    c->buf = live_new(CTX_BYTES, 'A');
+    g_nctx++;
+    L("knn_ctx_create_dt %s %d %zu %zu %zu %d %d", N(c->buf), device, nq, n, block_cap, k, dtype);
+    *out = c;
+    return KNN_OK;
+}
+
+int knn_ctx_destroy(knn_ctx_t *c)
+{
+    if (!c) return KNN_ERR_INVALID;
+    L("knn_ctx_destroy %s", N(c->buf));
+    live_free(c->buf, "knn_ctx_destroy");
+    free(c);
+    g_nctx--;
+    return KNN_OK;
+}
+
+size_t knn_ctx_device_bytes(const knn_ctx_t *c) { return c ? CTX_BYTES : 0; }
+int knn_ctx_contraction_bits(const knn_ctx_t *c) { return c->s8 ? 8 : 64; }
+
+int knn_ctx_set_keep_zero(knn_ctx_t *c, int on)
+{
+    L("knn_ctx_set_keep_zero %s %d", N(c->buf), on);
+    return KNN_OK;
+}
+
+int knn_ctx_set_rows(knn_ctx_t *c, size_t rows)
+{
+    FALLIBLE("knn_ctx_set_rows", KNN_ERR_INVALID);
+    L("knn_ctx_set_rows %s %zu", N(c->buf), rows);
+    return KNN_OK;
+}
+
+int knn_ctx_begin_s8(knn_ctx_t *c, const void *qs8, size_t q_cap, size_t q_base, const double *d_meta,
+                     const double *h_meta, void *stream)
+{
+    FALLIBLE("knn_ctx_begin_s8", KNN_ERR_HIP);
+    L("knn_ctx_begin_s8 %s %s %zu %zu %s %s %s", N(c->buf), N(qs8), q_cap, q_base, N(d_meta), N(h_meta), N(stream));
+    c->s8 = 1;
+    return KNN_OK;
+}
+
+int knn_ctx_begin_meta(knn_ctx_t *c, const void *qblk, size_t q_cap, size_t q_base, const double *d_meta,
+                       const double *h_meta, void *stream)
+{
+    FALLIBLE("knn_ctx_begin_meta", KNN_ERR_HIP);
+    L("knn_ctx_begin_meta %s %s %zu %zu %s %s %s", N(c->buf), N(qblk), q_cap, q_base, N(d_meta), N(h_meta), N(stream));
+    c->s8 = 0;
+    return KNN_OK;
+}
+
+static void log_blocks(const char *name, knn_ctx_t *c, int nblk, const void *const *blk, const size_t *nc,
+                       const size_t *base, const void *d_out, void *stream)
+{
+    char buf[900];
+    int at = snprintf(buf, sizeof(buf), "%s %s %s %s blocks %d", name, N(c->buf), N(d_out), N(stream), nblk);
+    for (int b = 0; b < nblk && at < (int)sizeof(buf) - 64; b++)
+        at += snprintf(buf + at, sizeof(buf) - (size_t)at, " [ %s %zu %zu ]", N(blk[b]), nc[b], base[b]);
+    L("%s", buf);
+}
+
+int knn_ctx_step_n(knn_ctx_t *c, int nblk, const void *const *blk, const size_t *nc, const size_t *base, void *stream)
+{
+    FALLIBLE("knn_ctx_step_n", KNN_ERR_HIP);
+    log_blocks("knn_ctx_step_n", c, nblk, blk, nc, base, NULL, stream);
+    return KNN_OK;
+}
+
+int knn_ctx_step_shadow_n(knn_ctx_t *c, int nblk, const void *const *blk, const size_t *nc, const size_t *base,
+                          void *stream)
+{
+    FALLIBLE("knn_ctx_step_shadow_n", KNN_ERR_HIP);
+    log_blocks("knn_ctx_step_shadow_n", c, nblk, blk, nc, base, NULL, stream);
+    return KNN_OK;
+}
+
+int knn_ctx_end(knn_ctx_t *c, knn_neighbour_t *d_out, size_t *unresolved, void *stream)
+{
+    FALLIBLE("knn_ctx_end", KNN_ERR_HIP);
+    L("knn_ctx_end %s %s %s -> %zu", N(c->buf), N(d_out), N(stream), g_unres_end);
+    *unresolved = g_unres_end;
+    return KNN_OK;
+}
+
+int knn_ctx_attach_qblock(knn_ctx_t *c, const void *qblk, size_t q_cap)
+{
+    FALLIBLE("knn_ctx_attach_qblock", KNN_ERR_INVALID);
+    L("knn_ctx_attach_qblock %s %s %zu", N(c->buf), N(qblk), q_cap);
+    return KNN_OK;
+}
+
+int knn_ctx_research_blocks(knn_ctx_t *c, int nblk, const void *const *blk, const size_t *nc, const size_t *base,
+                            knn_neighbour_t *d_out, size_t *unresolved, void *stream)
+{
+    FALLIBLE("knn_ctx_research_blocks", KNN_ERR_HIP);
+    log_blocks("knn_ctx_research_blocks", c, nblk, blk, nc, base, d_out, stream);
+    *unresolved = g_unres_research;
+    return KNN_OK;
+}
+
+int knn_ctx_rescan_step(knn_ctx_t *c, const void *blk, size_t nc, size_t base, void *stream)
+{
+    FALLIBLE("knn_ctx_rescan_step", KNN_ERR_HIP);
+    L("knn_ctx_rescan_step %s %s %zu %zu %s", N(c->buf), N(blk), nc, base, N(stream));
+    return KNN_OK;
+}
+
+int knn_ctx_rescan_end(knn_ctx_t *c, knn_neighbour_t *d_out, void *stream)
+{
+    FALLIBLE("knn_ctx_rescan_end", KNN_ERR_HIP);
+    L("knn_ctx_rescan_end %s %s %s", N(c->buf), N(d_out), N(stream));
+    return KNN_OK;
+}
+
+/* ---- the scenarios ------------------------------------------------------ */
+
+#define DIMS 16
+#define MAX_ROWS 2048
+#define MAX_RECS (1 << 15)
+#define MAX_IDS 128
+#define SRC (KNN_INDEX_DEVICE_SRC)
+#define OUT (KNN_INDEX_DEVICE_OUT)
+#define KZ (KNN_QUERY_KEEP_ZERO)
+
+enum { CREATE, QUERY, ADD, REMOVE, UPDATE, NEIGHBOURS, ONECALL, DESTROY };
+static const char *const op_name[] = {"create", "query", "add", "remove", "update", "neighbours", "knn_query", "destroy"};
+
+typedef struct {
+    int op;
+    size_t rows;             /* rows, queries or listed ids (neighbours, 0: the whole corpus) */
+    int k, flags, kind;
+    size_t unres, unres2;    /* what knn_ctx_end and the re-search report */
+    const char *tile;        /* KNN_QUERY_TILE */
+    int id0, idstep;         /* the ids id0, id0 + idstep, ... */
+    int may_reblock;         /* an add whose reblock may outlive its failure */
+} step_t;
+
+typedef struct {
+    const char *name;
+    const char *block;       /* KNN_QUERY_BLOCK */
+    int f32, labels;
+    step_t s[8];             /* up to the destroy */
+} scn_t;
+
+static const scn_t g_scn[] = {
+    {"create_int8", "256", 0, 1, {{.op = CREATE, .rows = 600, .kind = INT8}, {.op = DESTROY}}},
+    {"create_real_f32", "256", 1, 0, {{.op = CREATE, .rows = 600, .kind = REAL}, {.op = DESTROY}}},
+    {"create_device_src", "256", 0, 0, {{.op = CREATE, .rows = 300, .kind = INT8, .flags = SRC}, {.op = DESTROY}}},
+    {"query_host", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = QUERY, .rows = 100, .k = 5, .kind = INT8},
+      {.op = QUERY, .rows = 100, .k = 5, .kind = INT8, .flags = KZ},
+      {.op = QUERY, .rows = 100, .k = 5, .kind = REAL},   /* a batch off the byte image */
+      {.op = DESTROY}}},
+    {"query_device", "256", 0, 0,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = QUERY, .rows = 100, .k = 5, .kind = INT8, .flags = SRC | OUT | KZ},
+      {.op = QUERY, .rows = 100, .k = 5, .kind = INT8, .flags = SRC},
+      {.op = QUERY, .rows = 100, .k = 5, .kind = INT8, .flags = OUT},
+      {.op = DESTROY}}},
+    {"query_two_tiles", "256", 0, 0,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = QUERY, .rows = 100, .k = 5, .kind = INT8, .tile = "64"},
+      {.op = QUERY, .rows = 100, .k = 5, .kind = INT8, .tile = "64", .unres = 3},             /* re-search */
+      {.op = QUERY, .rows = 100, .k = 5, .kind = INT8, .tile = "64", .unres = 3, .unres2 = 1}, /* and rescan */
+      {.op = DESTROY}}},
+    {"query_real", "256", 1, 0,
+     {{.op = CREATE, .rows = 600, .kind = REAL},
+      {.op = QUERY, .rows = 100, .k = 40, .kind = REAL},
+      {.op = QUERY, .rows = 100, .k = 40, .kind = REAL, .unres = 2},   /* rescan */
+      {.op = DESTROY}}},
+    {"query_reuse", "256", 0, 0,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = QUERY, .rows = 300, .k = 5, .kind = INT8},
+      {.op = QUERY, .rows = 50, .k = 5, .kind = INT8},    /* the tile buffers again */
+      {.op = QUERY, .rows = 50, .k = 7, .kind = INT8},    /* another k: another context */
+      {.op = QUERY, .rows = 700, .k = 7, .kind = INT8},   /* past the tile capacity */
+      {.op = DESTROY}}},
+    {"add_fill_open", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = QUERY, .rows = 20, .k = 5, .kind = INT8},
+      {.op = ADD, .rows = 100, .kind = INT8},                 /* inside the last block */
+      {.op = ADD, .rows = 400, .kind = INT8, .flags = SRC},   /* fills it and opens two */
+      {.op = QUERY, .rows = 20, .k = 5, .kind = INT8},
+      {.op = DESTROY}}},
+    {"add_drop_s8", "256", 0, 0,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = ADD, .rows = 300, .kind = REAL},
+      {.op = QUERY, .rows = 20, .k = 5, .kind = INT8},
+      {.op = ADD, .rows = 10, .kind = INT8},
+      {.op = DESTROY}}},
+    {"add_reblock", NULL, 0, 1,
+     {{.op = CREATE, .rows = 200, .kind = INT8},
+      {.op = ADD, .rows = 1300, .kind = INT8},   /* 8 blocks of 200 */
+      {.op = QUERY, .rows = 20, .k = 5, .kind = INT8},
+      {.op = ADD, .rows = 300, .kind = INT8, .may_reblock = 1},   /* a ninth: blocks of 400 */
+      {.op = QUERY, .rows = 20, .k = 5, .kind = INT8},
+      {.op = DESTROY}}},
+    {"add_reblock_real", NULL, 1, 0,
+     {{.op = CREATE, .rows = 200, .kind = REAL},
+      {.op = ADD, .rows = 1500, .kind = REAL, .may_reblock = 1},
+      {.op = DESTROY}}},
+    {"add_after_remove", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = REMOVE, .rows = 2, .id0 = 5, .idstep = 295},
+      {.op = ADD, .rows = 100, .kind = INT8},   /* the id map grows */
+      {.op = QUERY, .rows = 20, .k = 5, .kind = INT8},
+      {.op = ADD, .rows = 10, .kind = INT8},
+      {.op = DESTROY}}},
+    {"remove_last_block", "256", 0, 0,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = QUERY, .rows = 20, .k = 5, .kind = INT8},
+      {.op = REMOVE, .rows = 6, .id0 = 590, .idstep = 1},
+      {.op = REMOVE, .rows = 4, .id0 = 597, .idstep = 1},   /* the last rows: nothing moves */
+      {.op = QUERY, .rows = 20, .k = 5, .kind = INT8},
+      {.op = DESTROY}}},
+    {"remove_first_block", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = REMOVE, .rows = 2, .id0 = 3, .idstep = 257},
+      {.op = REMOVE, .rows = 100, .id0 = 1, .idstep = 2},   /* a block fewer */
+      {.op = QUERY, .rows = 20, .k = 5, .kind = INT8},
+      {.op = DESTROY}}},
+    {"remove_real", "256", 1, 0,
+     {{.op = CREATE, .rows = 600, .kind = REAL}, {.op = REMOVE, .rows = 3, .id0 = 100, .idstep = 200}, {.op = DESTROY}}},
+    {"remove_not_live", "256", 0, 0,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = REMOVE, .rows = 1, .id0 = 5},
+      {.op = REMOVE, .rows = 1, .id0 = 5},
+      {.op = DESTROY}}},
+    {"update", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = UPDATE, .rows = 3, .id0 = 10, .idstep = 290, .kind = INT8},   /* every block */
+      {.op = REMOVE, .rows = 1, .id0 = 7},
+      {.op = UPDATE, .rows = 2, .id0 = 10, .idstep = 290, .kind = INT8, .flags = SRC},
+      {.op = UPDATE, .rows = 2, .id0 = 10, .idstep = 290, .kind = REAL},   /* drops the byte blocks */
+      {.op = QUERY, .rows = 20, .k = 5, .kind = INT8},
+      {.op = DESTROY}}},
+    {"neighbours", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = NEIGHBOURS, .rows = 3, .id0 = 1, .idstep = 299, .k = 5},
+      {.op = NEIGHBOURS, .rows = 0, .k = 5, .flags = KZ, .tile = "512", .unres = 2},
+      {.op = NEIGHBOURS, .rows = 3, .id0 = 1, .idstep = 299, .k = 5, .flags = KZ | OUT},
+      {.op = REMOVE, .rows = 1, .id0 = 7},
+      {.op = NEIGHBOURS, .rows = 0, .k = 5},
+      {.op = NEIGHBOURS, .rows = 3, .id0 = 1, .idstep = 299, .k = 5, .flags = KZ},
+      {.op = DESTROY}}},
+    {"neighbours_real", "256", 1, 0,
+     {{.op = CREATE, .rows = 300, .kind = REAL},
+      {.op = NEIGHBOURS, .rows = 0, .k = 5, .flags = OUT},
+      {.op = NEIGHBOURS, .rows = 2, .id0 = 2, .idstep = 270, .k = 5, .flags = KZ, .unres = 1},
+      {.op = DESTROY}}},
+    {"knn_query", "256", 0, 1,
+     {{.op = ONECALL, .rows = 100, .k = 5, .kind = INT8, .flags = KZ},
+      {.op = ONECALL, .rows = 100, .k = 5, .kind = INT8, .tile = "64", .unres = 2, .unres2 = 1},
+      {.op = ONECALL, .rows = 100, .k = 5, .kind = REAL},
+      {.op = DESTROY}}},
+};
+#define NSCN ((int)(sizeof(g_scn) / sizeof(g_scn[0])))
+#define ONECALL_M 600   /* knn_query's corpus rows */
+
+static double g_X[MAX_ROWS * DIMS], g_lab[MAX_ROWS];
+static knn_neighbour_t g_out[MAX_RECS];
+
+static void *user_alloc(size_t bytes) { return live_new(bytes, 'U'); }
+
+static void user_free_all(void)
+{
+    for (int i = g_nlive - 1; i >= 0; i--)
+        if (g_live[i].kind == 'U') live_free(g_live[i].base, "user_free_all");
+    g_ord['U'] = 0;
+}
+
+/* one call into the index; "# info ..." behind it when it left one */
+static int run_step(const scn_t *sc, knn_index_t **ix, const step_t *s)
+{
+    const int dt = sc->f32 ? KNN_F32 : KNN_F64, lay = KNN_ROWMAJOR;
+    const int dev = s->flags & (SRC | OUT), flags = s->op == CREATE || s->op == ADD || s->op == UPDATE
+                                                        ? s->flags & SRC
+                                                        : s->flags;
+    int32_t ids[MAX_IDS];
+    g_kind = s->kind;
+    g_unres_end = s->unres;
+    g_unres_research = s->unres2;
+    if (s->tile) setenv("KNN_QUERY_TILE", s->tile, 1);
+    else unsetenv("KNN_QUERY_TILE");
+    if (s->rows > MAX_ROWS || (s->op >= REMOVE && s->op <= NEIGHBOURS && s->rows > MAX_IDS)) DIE("step too large");
+    for (size_t i = 0; i < s->rows && i < MAX_IDS; i++) ids[i] = s->id0 + (int32_t)i * s->idstep;
+    L("# %s %zu k %d flags %d", op_name[s->op], s->rows, s->k, s->flags);
+    size_t mq = s->rows;
+    if (s->op == NEIGHBOURS && !mq) knn_index_info(*ix, &mq, NULL, NULL, NULL, NULL);
+    if (mq * (size_t)(s->k ? s->k : 1) > MAX_RECS) DIE("step too large");
+    const void *src = (dev & SRC) ? user_alloc(s->rows * DIMS * sizeof(double)) : (void *)g_X;
+    knn_neighbour_t *out = (dev & OUT) ? (knn_neighbour_t *)user_alloc(mq * (size_t)s->k * sizeof(*out)) : g_out;
+    const double *lab = sc->labels ? g_lab : NULL;
+    size_t removed = 0;
+    int rc = KNN_OK;
+    switch (s->op) {
+    case CREATE: rc = knn_index_create(ix, src, s->rows, DIMS, lay, dt, lab, dt, flags); break;
+    case QUERY: rc = knn_index_query(*ix, src, s->rows, lay, dt, s->k, flags, out); break;
+    case ADD: rc = knn_index_add(*ix, src, s->rows, lay, dt, lab, flags); break;
+    case REMOVE:
+        rc = knn_index_remove(*ix, ids, s->rows, 0, &removed);
+        if (!rc) L("# removed %zu", removed);
+        break;
+    case UPDATE: rc = knn_index_update(*ix, ids, s->rows, src, lay, dt, lab, flags); break;
+    case NEIGHBOURS: rc = knn_index_neighbours(*ix, s->rows ? ids : NULL, s->rows, s->k, flags, out); break;
+    case ONECALL: rc = knn_query(g_X, ONECALL_M, g_X, s->rows, DIMS, lay, lab, s->k, dt, flags, g_out); break;
+    default:
+        if (*ix) rc = knn_index_destroy(*ix);
+        *ix = NULL;
+    }
+    user_free_all();
+    if (rc) L("# -> %d", rc);
+    else if (*ix) {
+        size_t m = 0, last = 0, bytes = 0;
+        int nblk = 0, bits = 0;
+        knn_index_info(*ix, &m, NULL, &nblk, &bytes, &bits);
+        knn_index_last_id(*ix, &last);
+        L("# info m %zu blocks %d last_id %zu bytes %zu bits %d", m, nblk, last, bytes, bits);
+        if (bytes != live_bytes('A')) DIE("%s: the index accounts for %zu bytes, %zu are live", sc->name, bytes, live_bytes('A'));
+    }
+    return rc;
+}
+
+static void scn_open(const scn_t *sc)
+{
+    if (g_nlive || g_nevents || g_nctx) DIE("%s: something is live in front of it", sc->name);
+    memset(g_ord, 0, sizeof(g_ord));
+    if (sc->block) setenv("KNN_QUERY_BLOCK", sc->block, 1);
+    else unsetenv("KNN_QUERY_BLOCK");
+}
+
+static int nsteps(const scn_t *sc)
+{
+    int i = 0;
+    while (sc->s[i].op != DESTROY) i++;
+    return i + 1;
+}
+
+static void trace(const scn_t *sc)
+{
+    knn_index_t *ix = NULL;
+    scn_open(sc);
+    printf("## %s\n", sc->name);
+    g_echo = 1;
+    for (int i = 0; i < nsteps(sc); i++)
+        if (run_step(sc, &ix, &sc->s[i])) DIE("%s: step %d failed", sc->name, i);
+    g_echo = 0;
+    lines_clear();
+    if (g_nlive || g_nevents || g_nctx) DIE("%s: something is live behind it", sc->name);
+}
+
+/* ---- the sweep ---------------------------------------------------------- */
+
+static int g_violations;
+
+static void violation(const scn_t *sc, int step, long n, const char *what)
+{
+    printf("VIOLATION %s step %d (%s) fault %ld: %s\n", sc->name, step, op_name[sc->s[step].op], n, what);
+    g_violations++;
+}
+
+static int starts(const char *s, const char *p) { return !strncmp(s, p, strlen(p)); }
+
+/* The step's lines from its first enqueue on, without marks and allocations,
+ * as one string, the last `keep` of them (0: all) with their names numbered in
+ * order of appearance.  *cnt: how many lines there are. */
+static char *tail_of(char **line, int nline, int keep, int *cnt)
+{
+    static const char *const first[] = {"hipEventRecord", "hipMemcpyAsync", "hipMemsetAsync", "knn_launch_", "knn_block_"};
+    int at = nline, n = 0;
+    for (int i = 0; i < nline && at == nline; i++)
+        for (size_t f = 0; f < sizeof(first) / sizeof(first[0]); f++)
+            if (starts(line[i], first[f])) at = i;
+    int *sel = (int *)malloc((size_t)(nline + 1) * sizeof(int));
+    size_t len = 1;
+    for (int i = at; i < nline; i++)
+        if (line[i][0] != '#' && !starts(line[i], "hipMalloc") && !starts(line[i], "hipFree")) {
+            sel[n++] = i;
+            len += strlen(line[i]) + 1;
+        }
+    *cnt = n;
+    char *out = (char *)calloc(3 * len + 16, 1), *o = out;   /* (a name grows by a character or two) */
+    char seen[256][16];
+    int nseen = 0;
+    for (int j = keep && keep < n ? n - keep : 0; j < n; j++) {
+        for (const char *p = line[sel[j]]; *p;) {
+            const int name = (p == line[sel[j]] || p[-1] == ' ') && strchr("APE", *p) && p[1] >= '0' && p[1] <= '9';
+            if (!name) {
+                *o++ = *p++;
+                continue;
+            }
+            char tok[16] = {*p++};
+            int tl = 1, id = -1;
+            while (*p >= '0' && *p <= '9' && tl < 15) tok[tl++] = *p++;
+            for (int q = 0; q < nseen; q++)
+                if (!strcmp(seen[q], tok)) id = q;
+            if (id < 0 && nseen < 256) strcpy(seen[id = nseen++], tok);
+            o += sprintf(o, "%c#%d", tok[0], id);
+        }
+        *o++ = '\n';
+    }
+    free(sel);
+    return out;
+}
+
+static void sweep_step(const scn_t *sc, int step, long *faults)
+{
+    const step_t *s = &sc->s[step];
+    knn_index_t *ix = NULL;
+    char **clean = NULL;
+    int nclean = 0;
+    long count = 0;
+    for (long n = 0; n <= count; n++) {   /* n = 0: the clean run that counts */
+        scn_open(sc);
+        for (int i = 0; i < step; i++)
+            if (run_step(sc, &ix, &sc->s[i])) DIE("%s: step %d failed", sc->name, i);
+        size_t m0 = 0, last0 = 0, m1 = 0, last1 = 0, bytes = 0;
+        int nblk0 = 0, nblk1 = 0;
+        if (ix) {
+            knn_index_info(ix, &m0, NULL, &nblk0, NULL, NULL);
+            knn_index_last_id(ix, &last0);
+        }
+        lines_clear();
+        g_calls = g_scattered = g_fault_behind_scatter = 0;
+        g_fail_at = n;
+        int rc = run_step(sc, &ix, s);
+        g_fail_at = 0;
+        if (n == 0) {
+            if (rc) DIE("%s: step %d failed", sc->name, step);
+            count = g_calls;
+            nclean = g_nline;
+            clean = (char **)malloc((size_t)nclean * sizeof(char *));
+            memcpy(clean, g_line, (size_t)nclean * sizeof(char *));
+            g_nline = 0;
+        } else {
+            ++*faults;
+            if (!rc) violation(sc, step, n, "the call succeeded");
+            const int ruined = s->op == UPDATE && g_fault_behind_scatter;
+            if ((s->op == CREATE || s->op == ONECALL) && ix) violation(sc, step, n, "an index came out of a failed create");
+            if (ix && !ruined) {
+                knn_index_info(ix, &m1, NULL, &nblk1, &bytes, NULL);
+                knn_index_last_id(ix, &last1);
+                if (m1 != m0 || last1 != last0 || (s->may_reblock ? nblk1 > nblk0 : nblk1 != nblk0))
+                    violation(sc, step, n, "m, the block count or the last id changed");
+                if (bytes != live_bytes('A')) violation(sc, step, n, "live device memory is not what the index accounts for");
+            } else if (!ix && live_bytes('A') + live_bytes('P')) {
+                violation(sc, step, n, "a failed create left memory behind");
+            }
+            if (!ruined) {
+                lines_clear();
+                int nr = 0, nc = 0;
+                if (run_step(sc, &ix, s)) {
+                    violation(sc, step, n, "the clean retry failed");
+                } else {
+                    char *r = tail_of(g_line, g_nline, 0, &nr), *c = tail_of(clean, nclean, nr, &nc);
+                    if (nr == 0 ? nc != 0 : (strcmp(r, c) || (nr != nc && !s->may_reblock)))
+                        violation(sc, step, n, "the clean retry's trace differs");
+                    free(r);
+                    free(c);
+                }
+            }
+        }
+        if (ix) knn_index_destroy(ix);
+        ix = NULL;
+        lines_clear();
+        if (g_nlive || g_nevents || g_nctx) {
+            violation(sc, step, n, "something is live behind knn_index_destroy");
+            while (g_nlive) live_free(g_live[0].base, "sweep");
+            g_nevents = g_nctx = 0;
+        }
+    }
+    for (int i = 0; i < nclean; i++) free(clean[i]);
+    free(clean);
+}
+
+int main(int argc, char **argv)
+{
+    if (argc == 2 && !strcmp(argv[1], "--sweep")) {
+        long faults = 0;
+        int steps = 0;
+        for (int i = 0; i < NSCN; i++)
+            for (int st = 0; g_scn[i].s[st].op != DESTROY; st++, steps++) sweep_step(&g_scn[i], st, &faults);
+        printf("sweep: %d steps, %ld faults, %d violations\n", steps, faults, g_violations);
+        return g_violations != 0;
+    }
+    for (int i = 0; i < NSCN; i++) {
+        int wanted = argc < 2;
+        for (int a = 1; a < argc; a++) wanted |= !strcmp(argv[a], g_scn[i].name);
+        if (wanted) trace(&g_scn[i]);
+    }
+    return 0;
+}
