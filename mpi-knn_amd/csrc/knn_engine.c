@@ -30,6 +30,14 @@
 #define KNN_PSETS 4       /* partial-list sets: step s uses set s % 4   */
 #define KNN_PROF_STEPS 64 /* steps timed between two knn_ctx_end calls */
 
+/* A device buffer the context owns: its pointer and its bytes.  Allocated,
+ * grown and released only by the buf_* functions below, which keep the
+ * context's byte count (dev_bytes) in step. */
+typedef struct {
+    void *p;
+    size_t bytes;
+} knn_buf_t;
+
 struct knn_ctx {
     int device;
     int dtype;          /* element type of the packed blocks (KNN_F64 / KNN_F32) */
@@ -41,17 +49,39 @@ struct knn_ctx {
     int h16;            /* this search's contraction runs on fp16 MFMA (exact) */
     int i8;             /* ... on int8 MFMA over byte blocks (knn_i8.hip, exact) */
     int shadow;         /* step_shadow form: 0 none, 1 fp16 shadow rows, 2 byte blocks */
-    void *qsh, *csh[KNN_PSETS];
-    size_t qsh_bytes, csh_bytes;
-    void *qs8, *cs8[KNN_PSETS];   /* byte blocks: the queries, converted corpus blocks */
-    const void *q8;               /* the query byte block the kernels read: qs8 or the caller's (begin_s8) */
-    size_t qs8_bytes;
+    const void *q8;     /* the query byte block the kernels read: b.qs8 or the caller's (begin_s8) */
     int split;          /* this search filters with the split fp16 contraction (fp32 GEMM mode) */
     float sscale;       /* its power-of-two pre-scale S */
-    void *qsp, *csp[KNN_PSETS];   /* split shadow rows: the queries, converted corpus blocks */
-    size_t qsp_bytes, csp_bytes;
-    void *cspm[KNN_PSETS];        /* a fused GEMM step's blocks in split form, side by side */
-    size_t cspm_bytes[KNN_PSETS];
+    size_t csp_bytes;   /* the size the b.csp sets are allocated with */
+    /* Every device buffer the context owns, and nothing else: ctx_free_buffers
+     * releases the members of this struct as one array, and dev_bytes counts
+     * them.  A new buffer is one more member; a member of another type does
+     * not belong here (ctx_free_buffers asserts the size). */
+    struct {
+        /* the int8 re-search's (research8_run): the gathered queries' byte
+         * block, their records and flags; the re-search's fail list */
+        knn_buf_t sub_q8, sub_out, sub_flag, fail_list2;
+        /* partial lists: sets 2j and 2j+1 share one allocation, the odd set
+         * right behind the even one, so a k_merge can read both steps' lists
+         * as one array */
+        knn_buf_t pp_d[KNN_PSETS / 2], pp_i[KNN_PSETS / 2], pp_T[KNN_PSETS / 2];
+        knn_buf_t qsh, csh[KNN_PSETS];   /* fp16 shadow rows: the queries, converted corpus blocks */
+        knn_buf_t qs8, cs8[KNN_PSETS];   /* byte blocks */
+        knn_buf_t qsp, csp[KNN_PSETS];   /* split shadow rows */
+        knn_buf_t cspm[KNN_PSETS];       /* a fused GEMM step's blocks in split form, side by side */
+        knn_buf_t qthr;                  /* per-query filter bound shared by all splits and ring steps */
+        knn_buf_t qsum;                  /* int8 kernel: per query 4 cross-split summary slots (k_dist_topk_i8) */
+        /* the GEMM-mode merge's query order (knn_order.hip), found once a
+         * search from its first merged lists */
+        knn_buf_t ord_lab, ord_keys, ord_iota, ord_perm, ord_tmp;
+        /* running state per query: KNN_KP x (approx d^2, exact S, idx), T pair */
+        knn_buf_t st_d, st_x, st_T, st_i;
+        /* unresolved queries: [0] their count, [1] the mode (mode_dev); their
+         * list; per query the rescan bound on the k-th key (k_finalize) */
+        knn_buf_t fail_count, fail_list, fbound;
+        knn_buf_t rs_d, rs_i;            /* the exact rescan's lists */
+    } b;
+    size_t dev_bytes;   /* bytes of b */
     int lpq, klx;       /* partial lists of the active kernel: lpq per query and split, klx long */
     int i8_wgpc;        /* int8 distance workgroups a CU (2: the half-tile kernel) */
     int cus;
@@ -61,12 +91,7 @@ struct knn_ctx {
     double *part_d[KNN_PSETS];        /* set pointers into the pair buffers */
     int *part_i[KNN_PSETS];
     double *part_T[KNN_PSETS];
-    /* sets 2j and 2j+1 share one allocation, the odd set right behind the
-     * even one, so a k_merge can read both steps' lists as one array */
-    double *pp_d[KNN_PSETS / 2];
-    int *pp_i[KNN_PSETS / 2];
-    double *pp_T[KNN_PSETS / 2];
-    int pp_cap[KNN_PSETS / 2];        /* splits per pair allocation */
+    int pp_cap[KNN_PSETS / 2];        /* splits per pair allocation (b.pp_*) */
     size_t pp_per[KNN_PSETS / 2];     /* list entries per split it was sized for */
     /* The merge that waits: the lists of `sets` consecutive partial sets from
      * `set` on, `nsplit` splits in all.  One set: an even step whose merge the
@@ -87,22 +112,11 @@ struct knn_ctx {
     hipStream_t ds[2], ms;
     hipEvent_t ev_in, ev_m[KNN_PSETS], ev_ds[KNN_PSETS], ev_end;
     int nstep;
-    /* per-query filter bound shared by all splits and ring steps */
-    double *qthr;
-    /* int8 kernel: per query 4 cross-split summary slots (k_dist_topk_i8) */
-    unsigned long long *qsum;
-    /* running state per query: KNN_KP x (approx d^2, exact S, idx), T pair */
-    double *st_d, *st_x, *st_T;
-    int *st_i;
-    /* unresolved queries */
-    int *fail_count, *fail_list, *mode_dev;
+    int *mode_dev;      /* b.fail_count's second word */
     /* the pair's host copy (pinned, mapped): k_count_out writes it behind
      * the last merge, so knn_ctx_end's read-back is no blit */
     int *h_count, *h_count_dev;
-    double *fbound;     /* per query: rescan bound on the k-th key (k_finalize) */
-    double *rs_d;
-    int *rs_i;
-    size_t rs_cap;
+    size_t rs_cap;      /* list sets b.rs_d and b.rs_i hold */
     /* current search */
     const void *qblk;
     size_t q_base, q_rows_pad;
@@ -140,15 +154,7 @@ struct knn_ctx {
     size_t step0_nc, step0_cbase;
     struct knn_ctx *sub;
     size_t sub_cap;
-    void *sub_q8;
-    knn_neighbour_t *sub_out;
-    unsigned char *sub_flag;
-    int *fail_list2;
-    /* the GEMM-mode merge's query order (knn_order.hip), found once a
-     * search from its first merged lists */
-    int *ord_lab, *ord_keys, *ord_iota, *ord_perm;
-    void *ord_tmp;
-    size_t ord_cap, ord_tmp_bytes;
+    size_t ord_cap, ord_tmp_bytes;    /* queries the b.ord_* buffers serve; the scratch the order kernel gets */
     int ord_ready;
     /* kernel timing (knn_ctx_profile): 3 events per step bracket
      * k_dist_topk and k_merge */
@@ -312,52 +318,79 @@ int knn_block_pack(void *d_block, size_t cap, size_t rows, size_t n, const doubl
     return knn_block_pack_dt(d_block, KNN_F64, cap, rows, n, d_src, KNN_F64, ld, layout, stream);
 }
 
-static void ctx_free_buffers(knn_ctx_t *c)
+/* ---- the context's device memory ----------------------------------------- */
+
+static void buf_release(knn_ctx_t *c, knn_buf_t *b)
+{
+    hipFree(b->p);
+    c->dev_bytes -= b->bytes;
+    b->p = NULL;
+    b->bytes = 0;
+}
+
+/* The n empty buffers of g[] with bytes[] bytes each: all of them or, with
+ * KNN_ERR_NOMEM, none. */
+static int buf_alloc(knn_ctx_t *c, int n, knn_buf_t *const *g, const size_t *bytes)
+{
+    for (int i = 0; i < n; i++) {
+        if (hipMalloc(&g[i]->p, bytes[i]) != hipSuccess) {
+            g[i]->p = NULL;
+            while (i-- > 0) buf_release(c, g[i]);
+            return KNN_ERR_NOMEM;
+        }
+        g[i]->bytes = bytes[i];
+        c->dev_bytes += bytes[i];
+    }
+    return KNN_OK;
+}
+
+static int buf_alloc1(knn_ctx_t *c, knn_buf_t *b, size_t bytes) { return buf_alloc(c, 1, &b, &bytes); }
+
+/* At least `need` bytes in b; its old memory is freed once `stream`, where its
+ * last reader runs, has drained. */
+static int buf_grow(knn_ctx_t *c, knn_buf_t *b, size_t need, hipStream_t stream)
+{
+    if (need <= b->bytes) return KNN_OK;
+    HIPCHK(hipStreamSynchronize(stream));
+    buf_release(c, b);
+    return buf_alloc1(c, b, need);
+}
+
+/* the n buffers of g[] */
+static void buf_release_n(knn_ctx_t *c, int n, knn_buf_t *const *g)
+{
+    for (int i = 0; i < n; i++) buf_release(c, g[i]);
+}
+
+/* the re-search's sub-context and the three buffers sized with it */
+static void research8_free(knn_ctx_t *c)
 {
     if (c->sub) knn_ctx_destroy(c->sub);
-    hipFree(c->sub_q8);
-    hipFree(c->sub_out);
-    hipFree(c->sub_flag);
-    hipFree(c->fail_list2);
+    c->sub = NULL;
+    c->sub_cap = 0;
+    knn_buf_t *const g[] = {&c->b.sub_q8, &c->b.sub_out, &c->b.sub_flag};
+    buf_release_n(c, 3, g);
+}
+
+static void ctx_free_buffers(knn_ctx_t *c)
+{
+    research8_free(c);
+    /* (c->b holds knn_buf_t members only: released as the array it is laid out as) */
+    _Static_assert(sizeof(c->b) % sizeof(knn_buf_t) == 0, "knn_ctx.b: knn_buf_t members only");
+    for (size_t i = 0; i < sizeof(c->b) / sizeof(knn_buf_t); i++) buf_release(c, (knn_buf_t *)&c->b + i);
     for (int b = 0; b < KNN_PSETS; b++) {
         if (c->ev_m[b]) hipEventDestroy(c->ev_m[b]);
         if (c->ev_ds[b]) hipEventDestroy(c->ev_ds[b]);
     }
-    for (int b = 0; b < KNN_PSETS / 2; b++) {
-        hipFree(c->pp_d[b]);
-        hipFree(c->pp_i[b]);
-        hipFree(c->pp_T[b]);
-    }
     for (int b = 0; b < 2; b++) {
         if (c->ds[b]) hipStreamDestroy(c->ds[b]);
     }
+    /* (a search abandoned behind its solo step: c->ms is the caller's stream) */
+    if (c->solo_on) c->ms = c->ms_keep;
     if (c->ms) hipStreamDestroy(c->ms);
-    hipFree(c->qsh);
-    for (int b = 0; b < KNN_PSETS; b++) hipFree(c->csh[b]);
-    hipFree(c->qs8);
-    for (int b = 0; b < KNN_PSETS; b++) hipFree(c->cs8[b]);
-    hipFree(c->qsp);
-    for (int b = 0; b < KNN_PSETS; b++) hipFree(c->csp[b]);
-    for (int b = 0; b < KNN_PSETS; b++) hipFree(c->cspm[b]);
     if (c->ev_in) hipEventDestroy(c->ev_in);
     if (c->ev_end) hipEventDestroy(c->ev_end);
-    hipFree(c->qthr);
-    hipFree(c->qsum);
-    hipFree(c->ord_lab);
-    hipFree(c->ord_keys);
-    hipFree(c->ord_iota);
-    hipFree(c->ord_perm);
-    hipFree(c->ord_tmp);
-    hipFree(c->st_d);
-    hipFree(c->st_x);
-    hipFree(c->st_T);
-    hipFree(c->st_i);
-    hipFree(c->fail_count);
     if (c->h_count) hipHostFree(c->h_count);
-    hipFree(c->fail_list);
-    hipFree(c->fbound);
-    hipFree(c->rs_d);
-    hipFree(c->rs_i);
     for (int i = 0; i < 3 * KNN_PROF_STEPS; i++)
         if (c->prof_ev[i]) hipEventDestroy(c->prof_ev[i]);
     for (int i = 0; i < 2 * KNN_PROF_STEPS; i++)
@@ -528,17 +561,16 @@ int knn_ctx_create_dt(knn_ctx_t **out, int device, size_t nq, size_t n, size_t b
 
     const size_t np = c->nq_pad;
     int ok = 1;
-    ok &= hipMalloc((void **)&c->qthr, np * sizeof(double)) == hipSuccess;
-    ok &= hipMalloc((void **)&c->qsum, np * 4 * sizeof(unsigned long long)) == hipSuccess;
-    ok &= hipMalloc((void **)&c->st_d, np * c->kp * sizeof(double)) == hipSuccess;
-    ok &= hipMalloc((void **)&c->st_x, np * c->kp * sizeof(double)) == hipSuccess;
-    ok &= hipMalloc((void **)&c->st_i, np * c->kp * sizeof(int)) == hipSuccess;
-    ok &= hipMalloc((void **)&c->st_T, np * 2 * sizeof(double)) == hipSuccess;
-    /* [0] unresolved queries, [1] mode: one allocation, one read-back */
-    ok &= hipMalloc((void **)&c->fail_count, 2 * sizeof(int)) == hipSuccess;
-    ok &= hipMalloc((void **)&c->fail_list, np * sizeof(int)) == hipSuccess;
-    ok &= hipMalloc((void **)&c->fbound, np * sizeof(double)) == hipSuccess;
-    if (ok) c->mode_dev = c->fail_count + 1;
+    {
+        /* (fail_count: [0] unresolved queries, [1] mode -- one allocation, one read-back) */
+        knn_buf_t *const g[] = {&c->b.qthr, &c->b.qsum, &c->b.st_d, &c->b.st_x, &c->b.st_i,
+                                &c->b.st_T, &c->b.fail_count, &c->b.fail_list, &c->b.fbound};
+        const size_t bytes[] = {np * sizeof(double), np * 4 * sizeof(unsigned long long), np * c->kp * sizeof(double),
+                                np * c->kp * sizeof(double), np * c->kp * sizeof(int), np * 2 * sizeof(double),
+                                2 * sizeof(int), np * sizeof(int), np * sizeof(double)};
+        ok &= buf_alloc(c, 9, g, bytes) == KNN_OK;
+    }
+    if (ok) c->mode_dev = (int *)c->b.fail_count.p + 1;
     /* mapped: [0] unresolved, [1] mode, then (at byte 16) the search's 8
      * meta doubles as its kernels read them (knn_ctx_search_meta) */
     ok &= hipHostMalloc((void **)&c->h_count, 16 + KNN_META_DOUBLES * sizeof(double), hipHostMallocMapped) ==
@@ -593,34 +625,11 @@ int knn_ctx_set_rows(knn_ctx_t *c, size_t rows)
     return KNN_OK;
 }
 
-/* Device bytes the context holds: its per-query state, the conversion
- * buffers, partial lists, rescan lists and query order it has grown so far,
- * and its re-search sub-context.  A restatement of the allocation sizes in
- * this file, not a counter kept at every hipMalloc: an estimate for
- * knn_index_info, to be kept in step with them by hand. */
+/* Device bytes the context holds, its re-search sub-context's among them */
 size_t knn_ctx_device_bytes(const knn_ctx_t *c)
 {
     if (!c) return 0;
-    const size_t np = c->nq_cap;
-    size_t b = np * (sizeof(double) + 4 * sizeof(unsigned long long) + 2 * sizeof(double) + sizeof(int) +
-                     sizeof(double)) +
-               np * c->kp * (2 * sizeof(double) + sizeof(int)) + 2 * sizeof(int);
-    b += c->qsh_bytes + c->qs8_bytes + c->qsp_bytes;
-    for (int s = 0; s < KNN_PSETS; s++) {
-        if (c->csh[s]) b += c->csh_bytes;
-        if (c->cs8[s]) b += knn_s8_bytes(c->block_cap, c->n);
-        if (c->csp[s]) b += c->csp_bytes;
-        b += c->cspm_bytes[s];
-    }
-    for (int pr = 0; pr < KNN_PSETS / 2; pr++)
-        b += (size_t)c->pp_cap[pr] * (c->pp_per[pr] * (sizeof(double) + sizeof(int)) + np * sizeof(double));
-    b += c->rs_cap * c->kp * (sizeof(double) + sizeof(int));
-    b += c->ord_cap * 4 * sizeof(int) + (c->ord_cap ? c->ord_tmp_bytes : 0);
-    if (c->fail_list2) b += np * sizeof(int);
-    if (c->sub)
-        b += knn_ctx_device_bytes(c->sub) + knn_s8_bytes(c->sub_cap, c->n) +
-             c->sub_cap * ((size_t)c->k * sizeof(knn_neighbour_t) + 1);
-    return b;
+    return c->dev_bytes + knn_ctx_device_bytes(c->sub);
 }
 
 int knn_ctx_contraction_bits(const knn_ctx_t *c)
@@ -719,19 +728,6 @@ static float knn_split_scale(const double *meta, size_t n, int dtype)
     return (float)ldexp(1.0, 14 - e);
 }
 
-/* a conversion buffer of at least `need` bytes (its last reader is on `stream`) */
-static int grow_buffer(void **buf, size_t *have, size_t need, void *stream)
-{
-    if (need <= *have) return KNN_OK;
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    hipFree(*buf);
-    *buf = NULL;
-    *have = 0;
-    if (hipMalloc(buf, need) != hipSuccess) return KNN_ERR_NOMEM;
-    *have = need;
-    return KNN_OK;
-}
-
 /* d_s8: the query block as a byte block already (knn_block_pack_s8, valid by
  * knn_s8_spec_ok); d_qblock is then NULL until knn_ctx_attach_qblock */
 static int ctx_begin(knn_ctx_t *c, const void *d_qblock, const void *d_s8, size_t q_cap, size_t q_base,
@@ -800,22 +796,22 @@ static int ctx_begin(knn_ctx_t *c, const void *d_qblock, const void *d_s8, size_
         c->q8 = d_s8;   /* the caller's byte block: no conversion */
     } else if (c->i8) {
         const size_t need = knn_s8_bytes(q_cap, c->n);
-        RCHK(grow_buffer(&c->qs8, &c->qs8_bytes, need, stream));
-        RCHK(knn_launch_shadow8(c->qs8, d_qblock, c->dtype, c->q_rows_pad, c->n, d_meta, stream));
-        c->q8 = c->qs8;
+        RCHK(buf_grow(c, &c->b.qs8, need, (hipStream_t)stream));
+        RCHK(knn_launch_shadow8(c->b.qs8.p, d_qblock, c->dtype, c->q_rows_pad, c->n, d_meta, stream));
+        c->q8 = c->b.qs8.p;
     } else if (c->split) {
         const size_t need = c->q_rows_pad * knn_split_rs(c->n);
-        RCHK(grow_buffer(&c->qsp, &c->qsp_bytes, need, stream));
-        RCHK(knn_launch_shadow_split(c->qsp, d_qblock, c->dtype, c->q_rows_pad, c->n, c->sscale, stream));
+        RCHK(buf_grow(c, &c->b.qsp, need, (hipStream_t)stream));
+        RCHK(knn_launch_shadow_split(c->b.qsp.p, d_qblock, c->dtype, c->q_rows_pad, c->n, c->sscale, stream));
     } else if (c->shadow) {
         const size_t need = c->q_rows_pad * knn_round_up(c->n, 64) * 2;
-        RCHK(grow_buffer(&c->qsh, &c->qsh_bytes, need, stream));
-        RCHK(knn_launch_shadow(c->qsh, d_qblock, c->dtype, c->q_rows_pad, c->n, stream));
+        RCHK(buf_grow(c, &c->b.qsh, need, (hipStream_t)stream));
+        RCHK(knn_launch_shadow(c->b.qsh.p, d_qblock, c->dtype, c->q_rows_pad, c->n, stream));
     }
     /* fail_count and mode_dev are one allocation: one launch resets both,
      * the bounds and (int8: 0x7f7f7f7f, above every int8-mode d^2 -- an
      * empty summary) the cross-split summaries */
-    RCHK(knn_launch_begin_init(c->qthr, c->i8 ? c->qsum : NULL, (int)c->nq_pad, c->fail_count, stream));
+    RCHK(knn_launch_begin_init(c->b.qthr.p, c->i8 ? c->b.qsum.p : NULL, (int)c->nq_pad, c->b.fail_count.p, stream));
     return KNN_OK;
 }
 
@@ -1063,12 +1059,9 @@ static int choose_splits(knn_ctx_t *c, size_t nc)
 
 static void free_pair(knn_ctx_t *c, int pr)
 {
-    hipFree(c->pp_d[pr]);
-    hipFree(c->pp_i[pr]);
-    hipFree(c->pp_T[pr]);
-    c->pp_d[pr] = NULL;
-    c->pp_i[pr] = NULL;
-    c->pp_T[pr] = NULL;
+    buf_release(c, &c->b.pp_d[pr]);
+    buf_release(c, &c->b.pp_i[pr]);
+    buf_release(c, &c->b.pp_T[pr]);
     c->pp_cap[pr] = 0;
 }
 
@@ -1094,20 +1087,20 @@ static int ensure_part_buffers(knn_ctx_t *c, int nsplit, int set, int off)
         HIPCHK(hipStreamSynchronize(c->ms));
         free_pair(c, pr);
         const int cap = need > 2 * nsplit ? need : 2 * nsplit;
-        if (hipMalloc((void **)&c->pp_d[pr], (size_t)cap * per * sizeof(double)) != hipSuccess ||
-            hipMalloc((void **)&c->pp_i[pr], (size_t)cap * per * sizeof(int)) != hipSuccess ||
-            /* (the bounds by the context's capacity, not this search's rows: `per` can
-             * come out equal for two row counts under different list shapes -- 384
-             * rows of 4 x 16 lists, 1024 rows of 2 x 12 -- and then nothing is
-             * reallocated between them, knn_ctx_set_rows) */
-            hipMalloc((void **)&c->pp_T[pr], (size_t)cap * c->nq_cap * sizeof(double)) != hipSuccess)
-            return KNN_ERR_NOMEM;
+        /* (the bounds by the context's capacity, not this search's rows: `per` can
+         * come out equal for two row counts under different list shapes -- 384
+         * rows of 4 x 16 lists, 1024 rows of 2 x 12 -- and then nothing is
+         * reallocated between them, knn_ctx_set_rows) */
+        knn_buf_t *const g[] = {&c->b.pp_d[pr], &c->b.pp_i[pr], &c->b.pp_T[pr]};
+        const size_t bytes[] = {(size_t)cap * per * sizeof(double), (size_t)cap * per * sizeof(int),
+                                (size_t)cap * c->nq_cap * sizeof(double)};
+        RCHK(buf_alloc(c, 3, g, bytes));
         c->pp_cap[pr] = cap;
     }
     const int o = (set & 1) ? off : 0;
-    c->part_d[set] = c->pp_d[pr] + (size_t)o * per;
-    c->part_i[set] = c->pp_i[pr] + (size_t)o * per;
-    c->part_T[set] = c->pp_T[pr] + (size_t)o * c->nq_pad;
+    c->part_d[set] = (double *)c->b.pp_d[pr].p + (size_t)o * per;
+    c->part_i[set] = (int *)c->b.pp_i[pr].p + (size_t)o * per;
+    c->part_T[set] = (double *)c->b.pp_T[pr].p + (size_t)o * c->nq_pad;
     return KNN_OK;
 }
 
@@ -1136,27 +1129,20 @@ static int want_order(const knn_ctx_t *c, size_t nc)
 static int find_order(knn_ctx_t *c, int set, int nsplit)
 {
     if (c->ord_cap < c->nq_pad) {
-        hipFree(c->ord_lab);
-        hipFree(c->ord_keys);
-        hipFree(c->ord_iota);
-        hipFree(c->ord_perm);
-        hipFree(c->ord_tmp);
-        c->ord_lab = c->ord_keys = c->ord_iota = c->ord_perm = NULL;
-        c->ord_tmp = NULL;
+        knn_buf_t *const g[] = {&c->b.ord_lab, &c->b.ord_keys, &c->b.ord_iota, &c->b.ord_perm, &c->b.ord_tmp};
+        buf_release_n(c, 5, g);
         c->ord_cap = 0;
         const size_t b = c->nq_pad * sizeof(int);
         c->ord_tmp_bytes = knn_order_tmp_bytes((int)c->nq_pad);
-        if (hipMalloc((void **)&c->ord_lab, b) != hipSuccess || hipMalloc((void **)&c->ord_keys, b) != hipSuccess ||
-            hipMalloc((void **)&c->ord_iota, b) != hipSuccess || hipMalloc((void **)&c->ord_perm, b) != hipSuccess ||
-            hipMalloc(&c->ord_tmp, c->ord_tmp_bytes ? c->ord_tmp_bytes : 16) != hipSuccess)
-            return KNN_ERR_NOMEM;
+        const size_t bytes[] = {b, b, b, b, c->ord_tmp_bytes ? c->ord_tmp_bytes : 16};
+        RCHK(buf_alloc(c, 5, g, bytes));
         c->ord_cap = c->nq_pad;
     }
     /* 4 rounds: labels settle to cluster-sized pieces (pointer jumping
      * halves the distance to the piece's minimum each round) */
     RCHK(knn_launch_order(c->part_i[set], nsplit, c->lpq, c->klx, (int)c->nq, (int)c->nq_pad,
-                          (long long)c->q_base, 4, c->ord_lab, c->ord_keys, c->ord_iota, c->ord_perm, c->ord_tmp,
-                          c->ord_tmp_bytes, c->ms));
+                          (long long)c->q_base, 4, c->b.ord_lab.p, c->b.ord_keys.p, c->b.ord_iota.p, c->b.ord_perm.p,
+                          c->b.ord_tmp.p, c->ord_tmp_bytes, c->ms));
     c->ord_ready = 1;
     return KNN_OK;
 }
@@ -1192,20 +1178,21 @@ static int launch_merge_sets_fin(knn_ctx_t *c, int set, int nsets, int nsplit_to
     /* int8 lists (exact INT-mode keys, k <= 32): the rank merge */
     if (rank_merge) {
         RCHK(knn_launch_merge_rank(c->dtype, c->kp, c->klx, c->k, c->part_d[set], c->part_i[set], c->part_T[set],
-                                   nsplit_total, c->lpq, (int)c->nq, (int)c->nq_pad, !c->merged, c->st_d,
-                                   c->st_x, c->st_i, c->st_T, c->qthr, fin_out, c->fail_count, c->fail_list,
-                                   c->mode_dev, c->fbound, c->meta, (int)c->n, env_on("KNN_FORCE_RESCAN"), c->ms));
+                                   nsplit_total, c->lpq, (int)c->nq, (int)c->nq_pad, !c->merged, c->b.st_d.p,
+                                   c->b.st_x.p, c->b.st_i.p, c->b.st_T.p, c->b.qthr.p, fin_out, c->b.fail_count.p,
+                                   c->b.fail_list.p, c->mode_dev, c->b.fbound.p, c->meta, (int)c->n,
+                                   env_on("KNN_FORCE_RESCAN"), c->ms));
         if (fin_out && finalized) *finalized = 1;
     } else {
         const int *perm = NULL;
         if (want_order(c, rows)) {
             if (!c->ord_ready) RCHK(find_order(c, set, nsplit_total));
-            perm = c->ord_perm;
+            perm = c->b.ord_perm.p;
         }
         RCHK(knn_launch_merge_n(c->dtype, c->kp, c->k, c->part_d[set], c->part_i[set], c->part_T[set],
-                                nsplit_total, c->lpq, c->klx, (int)c->nq, (int)c->nq_pad, !c->merged, c->st_d,
-                                c->st_x, c->st_i, c->st_T, c->qblk, c->q_rows_pad, mb, (int)c->n, c->meta, c->qthr,
-                                c->split | kz_bit(c), perm, c->ms));
+                                nsplit_total, c->lpq, c->klx, (int)c->nq, (int)c->nq_pad, !c->merged, c->b.st_d.p,
+                                c->b.st_x.p, c->b.st_i.p, c->b.st_T.p, c->qblk, c->q_rows_pad, mb, (int)c->n, c->meta,
+                                c->b.qthr.p, c->split | kz_bit(c), perm, c->ms));
     }
     if (mk) HIPCHK(hipEventRecord(mk[1], c->ms));
     c->merged = 1;
@@ -1463,43 +1450,36 @@ static int ctx_step_impl(knn_ctx_t *c, const void *d_cblock, const void *d_sbloc
         if (!d_sblock && d_cblock == c->qblk && knn_rows_pad(c->block_cap) == c->q_rows_pad) {
             csh = c->q8;   /* the query block itself (P = 1): its byte block exists */
         } else if (!d_sblock) {
-            if (!c->cs8[set] && hipMalloc(&c->cs8[set], knn_s8_bytes(c->block_cap, c->n)) != hipSuccess)
-                return KNN_ERR_NOMEM;
-            RCHK(knn_launch_shadow8(c->cs8[set], d_cblock, c->dtype, knn_rows_pad(c->block_cap), c->n,
+            if (!c->b.cs8[set].p) RCHK(buf_alloc1(c, &c->b.cs8[set], knn_s8_bytes(c->block_cap, c->n)));
+            RCHK(knn_launch_shadow8(c->b.cs8[set].p, d_cblock, c->dtype, knn_rows_pad(c->block_cap), c->n,
                                     c->meta, ds));
-            csh = c->cs8[set];
+            csh = c->b.cs8[set].p;
         }
     } else if (c->split) {
         if (d_cblock == c->qblk && knn_rows_pad(c->block_cap) == c->q_rows_pad) {
-            csh = c->qsp;   /* the query block itself (P = 1) */
+            csh = c->b.qsp.p;   /* the query block itself (P = 1) */
         } else {
             const size_t need = knn_rows_pad(c->block_cap) * knn_split_rs(c->n);
             if (need > c->csp_bytes) {
                 /* the sets may still be read by earlier steps' kernels */
                 HIPCHK(hipDeviceSynchronize());
-                for (int b = 0; b < KNN_PSETS; b++) {
-                    hipFree(c->csp[b]);
-                    c->csp[b] = NULL;
-                }
+                for (int b = 0; b < KNN_PSETS; b++) buf_release(c, &c->b.csp[b]);
                 c->csp_bytes = need;
             }
-            if (!c->csp[set] && hipMalloc(&c->csp[set], c->csp_bytes) != hipSuccess) return KNN_ERR_NOMEM;
-            RCHK(knn_launch_shadow_split(c->csp[set], d_cblock, c->dtype, knn_rows_pad(nc), c->n, c->sscale, ds));
-            csh = c->csp[set];
+            if (!c->b.csp[set].p) RCHK(buf_alloc1(c, &c->b.csp[set], c->csp_bytes));
+            RCHK(knn_launch_shadow_split(c->b.csp[set].p, d_cblock, c->dtype, knn_rows_pad(nc), c->n, c->sscale, ds));
+            csh = c->b.csp[set].p;
         }
     } else if (d_sblock) {
         cn_ptr = (const char *)d_sblock + knn_shadow_norm_offset(c->block_cap, c->n);
     } else if (c->shadow && d_cblock == c->qblk && knn_rows_pad(nc) <= c->q_rows_pad) {
-        csh = c->qsh;   /* the query block itself (P = 1): its shadow exists */
+        csh = c->b.qsh.p;   /* the query block itself (P = 1): its shadow exists */
     } else if (c->shadow) {
         const size_t need = knn_rows_pad(c->block_cap) * knn_round_up(c->n, 64) * 2;
-        if (!c->csh[set]) {
-            /* first use of this set (hipMalloc may synchronise the device) */
-            if (hipMalloc(&c->csh[set], need) != hipSuccess) return KNN_ERR_NOMEM;
-        }
-        c->csh_bytes = need;
-        RCHK(knn_launch_shadow(c->csh[set], d_cblock, c->dtype, knn_rows_pad(nc), c->n, ds));
-        csh = c->csh[set];
+        /* first use of this set (hipMalloc may synchronise the device) */
+        if (!c->b.csh[set].p) RCHK(buf_alloc1(c, &c->b.csh[set], need));
+        RCHK(knn_launch_shadow(c->b.csh[set].p, d_cblock, c->dtype, knn_rows_pad(nc), c->n, ds));
+        csh = c->b.csh[set].p;
     }
     RCHK(step_prof(c, &st));
     if (c->i8) {
@@ -1514,13 +1494,13 @@ static int ctx_step_impl(knn_ctx_t *c, const void *d_cblock, const void *d_sbloc
         }
         RCHK(knn_launch_dist_i8(c->kp, c->klx, c->lpq, c->k, c->q8, c->q_rows_pad, c->q_base, (int)c->nq, &tab,
                                 knn_rows_pad(c->block_cap), (int)c->n, nsplit, c->part_d[set],
-                                c->part_i[set], c->part_T[set], (int)c->nq_pad, c->qthr,
-                                c->qsum, c->kz, ds));
+                                c->part_i[set], c->part_T[set], (int)c->nq_pad, c->b.qthr.p,
+                                c->b.qsum.p, c->kz, ds));
     } else
         RCHK(knn_launch_dist_topk(c->dtype, c->kp, c->k, c->qblk, c->q_rows_pad, c->q_base, (int)c->nq,
                                   d_cblock, knn_rows_pad(c->block_cap), c_base, (int)nc, (int)c->n, c->meta,
                                   nsplit, c->part_d[set], c->part_i[set], c->part_T[set], (int)c->nq_pad,
-                                  c->qthr, c->split ? c->qsp : c->qsh, csh, cn_ptr,
+                                  c->b.qthr.p, c->split ? c->b.qsp.p : c->b.qsh.p, csh, cn_ptr,
                                   (xord_for(c, nsplit) ? KNN_DIST_XORD : 0) | (c->h16 ? KNN_DIST_H16 : 0) |
                                       (c->shadow ? KNN_DIST_SHADOW : 0) | (c->split ? KNN_DIST_SPLIT : 0) |
                                       (c->kz ? KNN_DIST_KEEP0 : 0),
@@ -1598,16 +1578,9 @@ static int ctx_step_split_n(knn_ctx_t *c, int nblk, const void *const *d_cblocks
     const int set = st.set;
     hipStream_t ds = st.ds;
     const size_t per = knn_rows_pad(c->block_cap) * knn_split_rs(c->n);
-    if (c->cspm_bytes[set] < per * (size_t)nblk) {
-        /* (the set's last reader, merge s - 4, is ordered before ds above;
-         * a free waits for the device) */
-        HIPCHK(hipStreamSynchronize(ds));
-        hipFree(c->cspm[set]);
-        c->cspm[set] = NULL;
-        c->cspm_bytes[set] = 0;
-        if (hipMalloc(&c->cspm[set], per * (size_t)nblk) != hipSuccess) return KNN_ERR_NOMEM;
-        c->cspm_bytes[set] = per * (size_t)nblk;
-    }
+    /* (the set's last reader, merge s - 4, is ordered before ds above; a free
+     * waits for the device) */
+    RCHK(buf_grow(c, &c->b.cspm[set], per * (size_t)nblk, ds));
     const size_t norm_off = knn_rows_pad(c->block_cap) * knn_n_pad_dt(c->n, c->dtype) * knn_esize(c->dtype);
     knn_split_blocks_t tab;
     knn_merge_blocks_t mb;
@@ -1618,7 +1591,7 @@ static int ctx_step_split_n(knn_ctx_t *c, int nblk, const void *const *d_cblocks
     void *cdst[KNN_SPLIT_MAXBLK];
     size_t crows[KNN_SPLIT_MAXBLK];
     for (int b = 0; b < nblk; b++) {
-        cdst[b] = (char *)c->cspm[set] + per * (size_t)b;
+        cdst[b] = (char *)c->b.cspm[set].p + per * (size_t)b;
         crows[b] = knn_rows_pad(nc[b]);
     }
     RCHK(knn_launch_shadow_split_n(nblk, cdst, d_cblocks, crows, c->dtype, c->n, c->sscale, ds));
@@ -1632,9 +1605,9 @@ static int ctx_step_split_n(knn_ctx_t *c, int nblk, const void *const *d_cblocks
         mb.ptr[b] = d_cblocks[b];
     }
     RCHK(step_prof(c, &st));
-    RCHK(knn_launch_dist_split_n(c->dtype, c->kp, c->k, c->qblk, c->q_rows_pad, c->q_base, (int)c->nq, c->qsp, &tab,
+    RCHK(knn_launch_dist_split_n(c->dtype, c->kp, c->k, c->qblk, c->q_rows_pad, c->q_base, (int)c->nq, c->b.qsp.p, &tab,
                                  (int)c->n, c->meta, st.nsplit, c->part_d[set], c->part_i[set], c->part_T[set],
-                                 (int)c->nq_pad, c->qthr, xord_for(c, st.nsplit) | kz_bit(c),
+                                 (int)c->nq_pad, c->b.qthr.p, xord_for(c, st.nsplit) | kz_bit(c),
                                  (float)(-2.0 / ((double)c->sscale * c->sscale)),
                                  ds));
     /* (its merge re-ranks from its blocks' rows: never held for a later step) */
@@ -1674,19 +1647,6 @@ int knn_ctx_shadow(const knn_ctx_t *c) { return c ? c->shadow : 0; }
  * queries whose k-th and (k+1)-th distances tie, 35 of 60000.) */
 static int ctx_end_device(knn_ctx_t *c, knn_neighbour_t *d_out, hipStream_t s);
 
-static void research8_free(knn_ctx_t *c)
-{
-    if (c->sub) knn_ctx_destroy(c->sub);
-    hipFree(c->sub_q8);
-    hipFree(c->sub_out);
-    hipFree(c->sub_flag);
-    c->sub = NULL;
-    c->sub_q8 = NULL;
-    c->sub_out = NULL;
-    c->sub_flag = NULL;
-    c->sub_cap = 0;
-}
-
 /* The re-search proper: the c->nfail uncertified queries of fail_list
  * against the byte blocks of xb (NULL: the single-block search's own query
  * byte block, q8), the sub-search's q_base at q_base_sub (past every row id
@@ -1700,10 +1660,11 @@ static int research8_run(knn_ctx_t *c, int nblk, const void *const *blk, const s
         const size_t cap = knn_round_up((size_t)nf, KNN_TQ);
         RCHK(knn_ctx_create_dt(&c->sub, c->device, cap, c->n, c->block_cap, c->k, c->dtype));
         c->sub->sub_research = 1;
-        if (hipMalloc(&c->sub_q8, knn_s8_bytes(cap, c->n)) != hipSuccess ||
-            hipMalloc((void **)&c->sub_out, cap * (size_t)c->k * sizeof(knn_neighbour_t)) != hipSuccess ||
-            hipMalloc((void **)&c->sub_flag, cap) != hipSuccess ||
-            (!c->fail_list2 && hipMalloc((void **)&c->fail_list2, c->nq_cap * sizeof(int)) != hipSuccess)) {
+        /* (the last one only when the context has none yet: it is not sized with the sub-context) */
+        knn_buf_t *const g[] = {&c->b.sub_q8, &c->b.sub_out, &c->b.sub_flag, &c->b.fail_list2};
+        const size_t bytes[] = {knn_s8_bytes(cap, c->n), cap * (size_t)c->k * sizeof(knn_neighbour_t), cap,
+                                c->nq_cap * sizeof(int)};
+        if (buf_alloc(c, c->b.fail_list2.p ? 3 : 4, g, bytes)) {
             research8_free(c);   /* no half-built sub-context survives */
             return KNN_ERR_NOMEM;
         }
@@ -1720,9 +1681,9 @@ static int research8_run(knn_ctx_t *c, int nblk, const void *const *blk, const s
      * key of every uncertified query in qthr, so the re-search filters with
      * the running answer from its first tile (cold 65-entry lists admitted
      * every row of a lane's first tiles: 682 us for two MNIST queries) */
-    RCHK(ctx_begin(u, NULL, c->sub_q8, c->sub_cap, q_base_sub, c->meta, c->hmeta, s));
-    RCHK(knn_launch_gather8(c->sub_q8, c->q8, c->fail_list, nf, c->n, c->q_rows_pad, knn_rows_pad(c->sub_cap),
-                            c->qthr, u->qthr, s));
+    RCHK(ctx_begin(u, NULL, c->b.sub_q8.p, c->sub_cap, q_base_sub, c->meta, c->hmeta, s));
+    RCHK(knn_launch_gather8(c->b.sub_q8.p, c->q8, c->b.fail_list.p, nf, c->n, c->q_rows_pad, knn_rows_pad(c->sub_cap),
+                            c->b.qthr.p, u->b.qthr.p, s));
     if (nblk > 0) {
         /* a ring rank: every block it holds, KNN_I8_MAXBLK to a launch */
         for (int b0 = 0; b0 < nblk; b0 += KNN_I8_MAXBLK) {
@@ -1741,18 +1702,18 @@ static int research8_run(knn_ctx_t *c, int nblk, const void *const *blk, const s
     }
     /* the sub-search's fail list and count stay on the device: resolve8
      * reads them there, so the only host read is the final count below */
-    RCHK(ctx_end_device(u, c->sub_out, s));
-    RCHK(knn_launch_resolve8(c->sub_flag, c->fail_list, nf, u->fail_list, u->fail_count, c->sub_out, c->k, d_out,
-                             c->fail_list2, c->fail_count, s));
+    RCHK(ctx_end_device(u, c->b.sub_out.p, s));
+    RCHK(knn_launch_resolve8(c->b.sub_flag.p, c->b.fail_list.p, nf, u->b.fail_list.p, u->b.fail_count.p,
+                             c->b.sub_out.p, c->k, d_out, c->b.fail_list2.p, c->b.fail_count.p, s));
     /* (tests: a failure at this point, after resolve8 rewrote rows of d_out
      * and the device count -- knn_ctx_end's fallback must still be exact) */
     if (env_on("KNN_TEST_RESEARCH8_FAIL")) return KNN_ERR_HIP;
     int nn = 0;
-    HIPCHK(hipMemcpyAsync(&nn, c->fail_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&nn, c->b.fail_count.p, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    int *t = c->fail_list;
-    c->fail_list = c->fail_list2;
-    c->fail_list2 = t;
+    const knn_buf_t t = c->b.fail_list;
+    c->b.fail_list = c->b.fail_list2;
+    c->b.fail_list2 = t;
     c->nfail = nn;
     return KNN_OK;
 }
@@ -1782,18 +1743,14 @@ static int rescan_prep(knn_ctx_t *c, void *stream)
     if (c->nfail == 0) return KNN_OK;
     const size_t need = (size_t)c->nfail * (1 + (size_t)knn_rescan_chunks(c->nfail));
     if (need > c->rs_cap) {
-        hipFree(c->rs_d);
-        hipFree(c->rs_i);
-        c->rs_d = NULL;
-        c->rs_i = NULL;
+        knn_buf_t *const g[] = {&c->b.rs_d, &c->b.rs_i};
+        buf_release_n(c, 2, g);
         c->rs_cap = 0;
-        size_t cap = need;
-        if (hipMalloc((void **)&c->rs_d, cap * c->kp * sizeof(double)) != hipSuccess ||
-            hipMalloc((void **)&c->rs_i, cap * c->kp * sizeof(int)) != hipSuccess)
-            return KNN_ERR_NOMEM;
-        c->rs_cap = cap;
+        const size_t bytes[] = {need * c->kp * sizeof(double), need * c->kp * sizeof(int)};
+        RCHK(buf_alloc(c, 2, g, bytes));
+        c->rs_cap = need;
     }
-    return knn_launch_rescan_init(c->kp, c->rs_d, c->rs_i, c->nfail, stream);
+    return knn_launch_rescan_init(c->kp, c->b.rs_d.p, c->b.rs_i.p, c->nfail, stream);
 }
 
 /* A ring rank's int8 re-search (include/knn.h): after knn_ctx_end, its
@@ -1838,9 +1795,9 @@ static int last_merge_or_finalize(knn_ctx_t *c, knn_neighbour_t *d_out)
     int fin = 0;
     RCHK(flush_deferred(c, d_out, &fin));
     if (!fin)
-        RCHK(knn_launch_finalize(c->dtype, c->kp, c->st_d, c->st_x, c->st_i, c->st_T, c->qblk, c->q_rows_pad,
-                                 (int)c->nq, (int)c->n, c->k, c->meta, d_out, c->fail_count,
-                                 c->fail_list, c->mode_dev, c->fbound, env_on("KNN_FORCE_RESCAN"),
+        RCHK(knn_launch_finalize(c->dtype, c->kp, c->b.st_d.p, c->b.st_x.p, c->b.st_i.p, c->b.st_T.p, c->qblk,
+                                 c->q_rows_pad, (int)c->nq, (int)c->n, c->k, c->meta, d_out, c->b.fail_count.p,
+                                 c->b.fail_list.p, c->mode_dev, c->b.fbound.p, env_on("KNN_FORCE_RESCAN"),
                                  c->split | kz_bit(c), c->ms));
     return KNN_OK;
 }
@@ -1864,7 +1821,7 @@ static int ctx_end_merge(knn_ctx_t *c, knn_neighbour_t *d_out)
 {
     RCHK(last_merge_or_finalize(c, d_out));
     c->h_count[0] = c->h_count[1] = -1;
-    RCHK(knn_launch_count_out(c->fail_count, c->h_count_dev, c->meta,
+    RCHK(knn_launch_count_out(c->b.fail_count.p, c->h_count_dev, c->meta,
                               (double *)((char *)c->h_count_dev + 16), c->ms));
     /* the host waits for the results, so the caller's stream needs no wait
      * packet on them (one would sit before that stream's next kernel) */
@@ -1928,7 +1885,7 @@ int knn_ctx_end(knn_ctx_t *c, knn_neighbour_t *d_out, size_t *unresolved, void *
     if (c->nfail > 0 && research8(c, d_out, s) != KNN_OK) {
         /* the re-search is an optimisation: on any failure of it the exact
          * rescan resolves the same queries.  The rescan reads only the host
-         * count c->nfail and c->fail_list, both still the first pass's
+         * count c->nfail and c->b.fail_list.p, both still the first pass's
          * (resolve8 writes the new list into fail_list2; they are swapped
          * only after the count's read-back succeeded).  What resolve8 may
          * already have changed is harmless: the d_out rows it rewrote are
@@ -1951,8 +1908,8 @@ int knn_ctx_rescan_step(knn_ctx_t *c, const void *d_cblock, size_t nc, size_t c_
     if (c->nfail == 0) return KNN_OK;
     if (!c->qblk) return KNN_ERR_INVALID;   /* begin_s8: knn_ctx_attach_qblock first */
     HIPCHK(hipSetDevice(c->device));
-    return knn_launch_rescan_step(c->dtype, c->kp, c->fail_list, c->nfail, c->fbound, c->qblk,
-                                  d_cblock, c_base, (int)nc, (int)c->n, c->k, c->rs_d, c->rs_i,
+    return knn_launch_rescan_step(c->dtype, c->kp, c->b.fail_list.p, c->nfail, c->b.fbound.p, c->qblk,
+                                  d_cblock, c_base, (int)nc, (int)c->n, c->k, c->b.rs_d.p, c->b.rs_i.p,
                                   c->kz ? (long long)c->q_base : -1LL, stream);
 }
 
@@ -1961,7 +1918,7 @@ int knn_ctx_rescan_end(knn_ctx_t *c, knn_neighbour_t *d_out, void *stream)
     if (!c || !d_out) return KNN_ERR_INVALID;
     if (c->nfail == 0) return KNN_OK;
     HIPCHK(hipSetDevice(c->device));
-    return knn_launch_rescan_end(c->kp, c->fail_list, c->nfail, c->rs_d, c->rs_i, c->k, d_out,
+    return knn_launch_rescan_end(c->kp, c->b.fail_list.p, c->nfail, c->b.rs_d.p, c->b.rs_i.p, c->k, d_out,
                                  stream);
 }
 

@@ -10,11 +10,25 @@ blocks in one fused step) on byte blocks and on the split filter, a fused
 split-filter step of 9 blocks, and a solo context whose second step is a
 fused split-filter step -- each once more with knn_ctx_profile on.
 
+Further scenarios reach every allocation site of knn_engine.c (DESIGN.md has
+the table).  tests/engine_trace/expected/NAME.txt holds each scenario's trace
+as recorded from the knn_engine.c before its device memory was folded behind
+one owner, except that knn_ctx_destroy's lines are in the order the fold gave
+them (profiles/engine_fold_ab.md); to record a scenario again:
+engine_trace NAME > expected/NAME.txt.  The sweep (engine_trace --sweep,
+described in engine_trace.c) fails every fallible call of every call into the
+engine in turn and checks what the failed call left.
+
+Names in a trace: S1 and S2 are the caller's streams, S3 and S4 the distance
+streams, S5 the merge stream; events are numbered as knn_ctx_create makes
+them: ev_m[p] = E(2p+1), ev_ds[p] = E(2p+2).
+
 Checked here: the launches of every scenario, that every merge is ordered
 behind the distance launches whose lists it reads (through that step's ev_ds
 event, or by running on their stream), and that leaving solo mode in front of
 a fused split-filter step gives the schedule of a context that never was solo.
 """
+import glob
 import os
 import re
 import shutil
@@ -29,17 +43,50 @@ DIST = ("knn_launch_dist_i8", "knn_launch_dist_topk", "knn_launch_dist_split_n")
 MERGE = ("knn_launch_merge_rank", "knn_launch_merge_n")
 
 
-@pytest.fixture(scope="module")
-def traces(tmp_path_factory):
+HERE = os.path.join(ROOT, "tests", "engine_trace")
+EXPECTED = sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(HERE, "expected", "*.txt")))
+CALLER, CALLER2, MERGE_STREAM = "S1", "S2", "S5"
+
+
+def ev_ds(p):
+    return "E%d" % (2 * p + 2)
+
+
+def build(exe, extra=()):
     cc = shutil.which("gcc") or shutil.which("cc")
     assert cc, "no C compiler"
-    exe = str(tmp_path_factory.mktemp("engine_trace") / "engine_trace")
-    subprocess.check_call([
-        cc, "-O1", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-D__HIP_PLATFORM_AMD__",
+    return subprocess.run([
+        cc, "-O1", "-g", "-std=gnu11", "-Wall", "-Wextra", "-Werror", "-D__HIP_PLATFORM_AMD__", *extra,
         "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "mpi-knn_amd", "csrc"),
         "-I" + os.path.join(ROCM, "include"), "-o", exe,
-        os.path.join(ROOT, "tests", "engine_trace", "engine_trace.c"),
-        os.path.join(ROOT, "mpi-knn_amd", "csrc", "knn_engine.c"), "-lm"])
+        os.path.join(HERE, "engine_trace.c"),
+        os.path.join(ROOT, "mpi-knn_amd", "csrc", "knn_engine.c"), "-lm"], capture_output=True, text=True)
+
+
+def sanitizers_link(flags, tmp):
+    """Whether the toolchain links and runs a trivial program with `flags`."""
+    cc = shutil.which("gcc") or shutil.which("cc")
+    src, probe = str(tmp / "probe.c"), str(tmp / "probe")
+    with open(src, "w") as fh:
+        fh.write("int main(void) { return 0; }\n")
+    try:
+        subprocess.check_call([cc, *flags, "-o", probe, src], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        return subprocess.run([probe], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL).returncode == 0
+    except (subprocess.CalledProcessError, OSError):
+        return False
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    path = str(tmp_path_factory.mktemp("engine_trace") / "engine_trace")
+    res = build(path)
+    assert res.returncode == 0, res.stderr
+    return path
+
+
+@pytest.fixture(scope="module")
+def traces(exe):
+    # (exit status 1: knn_ctx_device_bytes was not the live bytes behind some call)
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
     res, cur = {}, None
     for line in out.splitlines():
@@ -48,6 +95,46 @@ def traces(tmp_path_factory):
         else:
             cur.append(line)
     return res
+
+
+def test_every_scenario_is_recorded(traces):
+    assert sorted(traces) == EXPECTED and len(EXPECTED) == 28
+
+
+@pytest.mark.parametrize("name", EXPECTED)
+def test_trace_is_the_recorded_one(traces, name):
+    with open(os.path.join(HERE, "expected", name + ".txt")) as fh:
+        want = fh.read().splitlines()
+    assert want[0] == "## " + name
+    assert traces[name] == want[1:]
+
+
+def check_sweep(res):
+    lines = res.stdout.splitlines()
+    assert lines, res.stderr[-4000:]
+    last = lines[-1].split()
+    # "sweep: C calls, F faults, A absorbed, W warm, V violations"
+    assert last[0] == "sweep:" and int(last[1]) >= 270 and int(last[3]) >= 5000, res.stdout[-4000:] + res.stderr[-4000:]
+    assert res.returncode == 0 and int(last[9]) == 0, res.stdout[-4000:]
+
+
+def test_fault_sweep(exe):
+    check_sweep(subprocess.run([exe, "--sweep"], capture_output=True, text=True))
+
+
+def test_traces_and_sweep_under_sanitizers(tmp_path, traces):
+    """The same program built with the address and undefined-behaviour
+    sanitizers (a program of its own: nothing is preloaded)."""
+    san = ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer")
+    if not sanitizers_link(san, tmp_path):
+        pytest.skip("-fsanitize=address,undefined does not link here")
+    path = str(tmp_path / "engine_trace_san")
+    res = build(path, san)
+    assert res.returncode == 0, res.stderr
+    out = subprocess.run([path], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-4000:]
+    assert out.stdout.splitlines() == [x for n in traces for x in ["## " + n] + traces[n]]
+    check_sweep(subprocess.run([path, "--sweep"], capture_output=True, text=True))
 
 
 def searches(lines):
@@ -69,7 +156,7 @@ def count(lines, name):
 
 def finalizing(lines):
     """Rank merges that finalize (their record pointer is set)."""
-    return sum(1 for x in lines if x.startswith("knn_launch_merge_rank") and " fin b- " not in x)
+    return sum(1 for x in lines if x.startswith("knn_launch_merge_rank") and " fin 0 " not in x)
 
 
 # per scenario and search: distance launches, merges, finalizing rank merges,
@@ -115,7 +202,7 @@ def test_solo_one_step_has_no_event_traffic(traces):
     s = searches(traces["solo1_i8"])[0]
     assert count(s, "hipEventRecord") == 0 and count(s, "hipStreamWaitEvent") == 0
     streams = {stream_of(x) for x in s if x.startswith(DIST + ("knn_launch_merge_rank", "knn_launch_count_out"))}
-    assert streams == {"s0"}, s
+    assert streams == {CALLER}, s
 
 
 def test_solo_end_on_second_stream_orders_it(traces):
@@ -124,12 +211,12 @@ def test_solo_end_on_second_stream_orders_it(traces):
     s = searches(traces["solo1_end_other_stream"])[0]
     body = s[s.index("# end"):]
     ops = [x for x in body if x.startswith(("hipEventRecord", "hipStreamWaitEvent", "knn_launch_merge_rank"))]
-    assert ops[0].split()[2] == "s0" and ops[1].split()[:3] == ["hipStreamWaitEvent", "s1", ops[0].split()[1]]
-    assert ops[2].split()[-1] == "s1"
+    assert ops[0].split()[2] == CALLER and ops[1].split()[:3] == ["hipStreamWaitEvent", CALLER2, ops[0].split()[1]]
+    assert ops[2].split()[-1] == CALLER2
 
 
 def stream_of(line):
-    """The stream a launch line ran on: the last s<id> before a block table."""
+    """The stream a launch line ran on: the last S<id> before a block table."""
     head = line.split(" blocks ")[0]
     return head.split()[-1]
 
@@ -146,9 +233,8 @@ def test_every_merge_follows_its_distance_launches(traces, name, prof):
     """A merge reads the lists of the oldest unmerged steps.  For each of
     them it runs on the step's distance stream, or its stream (or, in end(),
     the host) has waited for an event recorded on that stream behind the
-    launch -- on the merge stream (s4) that event is ev_ds of the step's
-    partial set (events are numbered as knn_ctx_create makes them:
-    ev_m[p] = e(2p), ev_ds[p] = e(2p+1))."""
+    launch -- on the merge stream that event is ev_ds of the step's
+    partial set."""
     for s in searches(traces[name + prof]):
         pending = []   # [step, stream, splits, events recorded behind the launch]
         waited = {}    # stream -> events it waited for, each with the records it then covered
@@ -175,8 +261,8 @@ def test_every_merge_follows_its_distance_launches(traces, name, prof):
                         continue
                     evs = [e for e, cov in waited.get(ms, []) + waited.get("host", []) if (st, True) in cov]
                     assert evs, (name, st, line)
-                    if ms == "s4":
-                        assert "e%d" % (2 * (st % 4) + 1) in evs, (name, st, line)
+                    if ms == MERGE_STREAM:
+                        assert ev_ds(st % 4) in evs, (name, st, line)
                 assert left == 0, (name, line)
         assert not pending, (name, pending)
 
@@ -191,7 +277,7 @@ def test_solo_then_fused_split_step_is_the_step_schedule(traces, prof):
                            searches(traces["split_own_then_2" + prof])):
         second = [i for i, x in enumerate(solo) if x == "# step"][1]
         tail = solo[second:]
-        leave = ["hipEventRecord e1 s0", "hipStreamWaitEvent s4 e1 0"]
+        leave = ["hipEventRecord %s %s" % (ev_ds(0), CALLER), "hipStreamWaitEvent %s %s 0" % (MERGE_STREAM, ev_ds(0))]
         at = tail.index(leave[0])
         assert tail[at:at + 2] == leave
         # (in front of the step's own first record, that of ev_in)
