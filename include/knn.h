@@ -378,6 +378,48 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * one); KNN_ERR_UNSUPPORTED: k (k + 1 under KNN_QUERY_KEEP_ZERO) above the
  * dtype's limit.
  *
+ * knn_index_classify: the vote (serial:104-130, blk:252-270) on the index's
+ * own state -- knn_index_query's call for the batch, unchanged (paths, tiling,
+ * KNN_QUERY_TILE, keep-zero rule, id remap after removals), then one vote
+ * launch over the records while they are still on the device; nothing comes
+ * back but the answers.  pred: mq predictions, exactly what
+ * knn_classify_query returns for that call's records with the index's labels
+ * by id (knn_index_last_id of them) as its table; vote_rule as there.
+ * qlabels (nullable): the batch's own labels, mq doubles, always on the host;
+ * *matches (nullable, always a host size_t): the q with pred[q] == qlabels[q],
+ * 0 without qlabels.  counts (nullable): mq x nclasses ints, counts[q nclasses
+ * + j] the number of query q's neighbours with label j + 1 -- the histogram
+ * the vote ran on (divided by the number of non-empty slots: what other
+ * libraries call predict_proba).  out (nullable): the mq*k records, .label
+ * filled on host-out and device-out calls alike (the vote kernel writes it, as
+ * knn_classify_device does).  flags: KNN_QUERY_KEEP_ZERO and
+ * KNN_INDEX_DEVICE_SRC as in knn_index_query; KNN_INDEX_DEVICE_OUT makes pred,
+ * counts and out device pointers on the index's device, and no copy back is
+ * made.  The labels get a device copy, by id, at the index's first classify
+ * call -- not in knn_index_create: an index that never classifies makes the
+ * device calls it always made -- counted in knn_index_info's device_bytes from
+ * then on; knn_index_add and knn_index_update with labels mark the ids they
+ * wrote, and the next classify call uploads that range in front of its span;
+ * knn_index_remove changes nothing (labels stay indexed by id, and removed ids
+ * never appear in records).  The vote's own buffers live for the call.
+ * knn_last_search_seconds() keeps reporting the search span alone: the vote is
+ * outside it, as serial:94-98 stops its timer in front of the vote.  Every
+ * output is complete on return; a failed call leaves the index answering as
+ * before.
+ *
+ * knn_index_classify_rows: the same behind knn_index_neighbours -- ids, count,
+ * ids == NULL, the keep-zero rule and its k + 1 limit as there; row i's own
+ * label is the index's label of ids[i], and *matches counts the rows predicted
+ * as their own label.  There is no source flag.  With ids == NULL, flags 0 and
+ * no removal it is the reference's whole program on the resident corpus:
+ * knn_search plus knn_classify.
+ *
+ * Both, before any device call: KNN_ERR_INVALID for a NULL index or pred, an
+ * index made without labels, nclasses <= 0, an unknown vote_rule, unknown flag
+ * bits and everything knn_index_query / knn_index_neighbours refuse (their
+ * NULL out excepted); KNN_ERR_UNSUPPORTED for nclasses > KNN_VOTE_MAX_CLASSES
+ * and for k above the limit (k + 1 under KNN_QUERY_KEEP_ZERO, for rows).
+ *
  * KNN_ERR_INVALID: NULL index, X, Q or out, zero m, mq or n, k <= 0, a bad
  * layout, unknown flag bits, m + mq > INT32_MAX; KNN_ERR_UNSUPPORTED: an
  * unknown src_dtype, dtype not KNN_F64 / KNN_F32, k above the dtype's limit
@@ -388,7 +430,7 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * ---------------------------------------------------------------------- */
 typedef struct knn_index knn_index_t;
 #define KNN_INDEX_DEVICE_SRC 2   /* X / Q is a device pointer on the index's device        */
-#define KNN_INDEX_DEVICE_OUT 4   /* out is a device pointer (knn_index_query only)         */
+#define KNN_INDEX_DEVICE_OUT 4   /* out (classify: pred, counts too) is a device pointer    */
 KNN_API int knn_index_create(knn_index_t **index, const void *X, size_t m, size_t n, int layout,
                              int src_dtype, const double *labels, int dtype, int flags);
 KNN_API int knn_index_query(knn_index_t *index, const void *Q, size_t mq, int layout, int src_dtype,
@@ -401,13 +443,21 @@ KNN_API int knn_index_update(knn_index_t *index, const int32_t *ids, size_t coun
                              int src_dtype, const double *labels /* nullable */, int flags);
 KNN_API int knn_index_neighbours(knn_index_t *index, const int32_t *ids /* nullable */, size_t count, int k,
                                  int flags, knn_neighbour_t *out);
+KNN_API int knn_index_classify(knn_index_t *index, const void *Q, size_t mq, int layout, int src_dtype,
+                               int k, int nclasses, int vote_rule, int flags,
+                               const double *qlabels /* nullable, host, mq */,
+                               int *pred, int *counts /* nullable, mq*nclasses */,
+                               size_t *matches /* nullable */, knn_neighbour_t *out /* nullable, mq*k */);
+KNN_API int knn_index_classify_rows(knn_index_t *index, const int32_t *ids /* nullable */, size_t count,
+                                    int k, int nclasses, int vote_rule, int flags,
+                                    int *pred, int *counts, size_t *matches, knn_neighbour_t *out);
 KNN_API int knn_index_last_id(const knn_index_t *index, size_t *last_id);
 KNN_API int knn_index_info(const knn_index_t *index, size_t *m, size_t *n, int *nblocks,
                            size_t *device_bytes, int *last_bits);
 KNN_API int knn_index_destroy(knn_index_t *index);
 
-/* Search wall time of the last knn_search() / knn_query() / knn_index_query() / knn_index_neighbours() on this
- * thread, seconds: the
+/* Search wall time of the last knn_search() / knn_query() / knn_index_query() / knn_index_neighbours() /
+ * knn_index_classify() / knn_index_classify_rows() on this thread, seconds: the
  * span the reference times (serial:70-98, blk:120-250) -- device compute
  * only, excluding load, H2D, D2H and vote. */
 KNN_API double knn_last_search_seconds(void);

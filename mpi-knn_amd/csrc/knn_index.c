@@ -25,7 +25,11 @@
  * scatter a touched block (knn_update_plan.h) in add's two parts (s8_stays,
  * commit_meta).  neighbours: tiles filled from the blocks by position
  * (knn_neighbours_plan.h), the same search_tiles, and under the keep-zero rule
- * k + 1 with the row itself taken out afterwards (k_drop_self).  The
+ * k + 1 with the row itself taken out afterwards (k_drop_self).  classify,
+ * classify_rows: query's and neighbours' bodies (query_search, rows_search)
+ * up to the span's end (search_tail), then the vote over the records on the
+ * device (vote_finish) with the labels' device copy, which the first such call
+ * makes and add / update keep marked (labels_sync, labels_stale).  The
  * knn_block_* operations are in knn_blocks.c; what a failed call leaves behind
  * is swept on a CPU by tests/index_trace.
  */
@@ -68,6 +72,11 @@ struct knn_index {
     double cmeta[KNN_META_DOUBLES];   /* host copy of the corpus's reduced meta */
     double *labels;
     size_t lab_cap;                   /* doubles allocated at labels (>= last_id: labels are indexed by id) */
+    /* d_labels: the labels' device copy, of dlab_cap doubles, made by the
+     * first classify call (labels_sync); entries lab_lo .. lab_hi-1 of it are
+     * stale, marked by add and update and uploaded by the next classify call */
+    double *d_labels;
+    size_t dlab_cap, lab_lo, lab_hi;
     /* ids: row p (0-based position in the blocks) has the 1-based id ids[p],
      * ascending.  NULL until the first removal: the id is then p + 1 and
      * last_id == m.  d_ids: its device copy (both of ids_cap entries). */
@@ -270,6 +279,7 @@ static void index_free(knn_index_t *ix)
     hipFree(ix->d_out);
     hipFree(ix->d_meta);
     hipFree(ix->d_ids);
+    hipFree(ix->d_labels);
     free(ix->ids);
     if (ix->red) hipHostFree(ix->red);
     if (ix->e0) hipEventDestroy(ix->e0);
@@ -569,16 +579,24 @@ static void fill_labels(knn_neighbour_t *out, size_t cnt, const double *labels)
 
 /* The end of a search call that stands at rc, its mq x k records due in d_out:
  * positions -> ids where rows were removed (the tiles wrote k + 1 wide records
- * to d_rec != d_out: the row itself, d_pos, out of them in the same pass), the
- * span's end, records and labels to the host.  A failed call keeps nothing. */
+ * to d_rec != d_out: the row itself, d_pos, out of them in the same pass) and
+ * the span's end (search_tail); then records and labels to the host.  A failed
+ * call keeps nothing. */
+static int search_tail(knn_index_t *ix, int rc, knn_neighbour_t *d_out, const knn_neighbour_t *d_rec,
+                       const int32_t *d_pos, size_t mq, int k)
+{
+    if (!rc && d_rec != d_out)
+        rc = knn_launch_drop_self(d_out, d_rec, d_pos, mq, k, ix->ids ? ix->d_ids : NULL, ix->m, NULL);
+    else if (!rc && ix->ids) rc = knn_launch_remap_idx(d_out, mq * (size_t)k, ix->d_ids, ix->m, NULL);
+    if (!rc) rc = span_end(ix);
+    return rc;
+}
+
 static int finish_search(knn_index_t *ix, int rc, knn_neighbour_t *out, int dev_out, knn_neighbour_t *d_out,
                          const knn_neighbour_t *d_rec, const int32_t *d_pos, size_t mq, int k)
 {
     const size_t cnt = mq * (size_t)k;
-    if (!rc && d_rec != d_out)
-        rc = knn_launch_drop_self(d_out, d_rec, d_pos, mq, k, ix->ids ? ix->d_ids : NULL, ix->m, NULL);
-    else if (!rc && ix->ids) rc = knn_launch_remap_idx(d_out, cnt, ix->d_ids, ix->m, NULL);
-    if (!rc) rc = span_end(ix);
+    rc = search_tail(ix, rc, d_out, d_rec, d_pos, mq, k);
     if (!rc && !dev_out && hipMemcpy(out, d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
         rc = KNN_ERR_HIP;
     if (rc) {
@@ -624,29 +642,49 @@ int knn_index_create(knn_index_t **index, const void *X, size_t m, size_t n, int
     return KNN_OK;
 }
 
-int knn_index_query(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int flags,
-                    knn_neighbour_t *out)
+/* what knn_index_query refuses before any device call (its caller: a NULL out) */
+static int query_check(const knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int flags)
 {
-    if (!ix || !Q || !out || mq == 0 || k <= 0) return KNN_ERR_INVALID;
+    if (!ix || !Q || mq == 0 || k <= 0) return KNN_ERR_INVALID;
     if (!knn_src_esize(src_dtype)) return KNN_ERR_UNSUPPORTED;
     if (k > k_max(ix->dtype)) return KNN_ERR_UNSUPPORTED;
     if (!layout_ok(layout)) return KNN_ERR_INVALID;
     if (flags & ~(KNN_QUERY_KEEP_ZERO | KNN_INDEX_DEVICE_SRC | KNN_INDEX_DEVICE_OUT)) return KNN_ERR_INVALID;
     if (mq > 0x7fffffffULL || ix->m + mq > 0x7fffffffULL) return KNN_ERR_INVALID;
-    if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
-    const int dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
+    return KNN_OK;
+}
+
+/* knn_index_query from its reservations through the last tile's search: the
+ * records go to dst (device), or to the index's own buffer (dst NULL), *d_out.
+ * The caller ends the call (finish_search, or search_tail and the vote) and
+ * frees *q, whatever is returned here. */
+static int query_search(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int flags,
+                        knn_neighbour_t *dst, dev_src_t *q, knn_neighbour_t **d_out)
+{
     const batch_t bt = tile_shape(ix, mq);
-    dev_src_t q = {0};
-    int rc = dev_out ? KNN_OK : index_out(ix, mq * (size_t)k);
-    if (!rc) rc = dev_src(&q, Q, mq * ix->n * knn_src_esize(src_dtype), flags);
+    int rc = dst ? KNN_OK : index_out(ix, mq * (size_t)k);
+    if (!rc) rc = dev_src(q, Q, mq * ix->n * knn_src_esize(src_dtype), flags);
     if (!rc) rc = index_reserve(ix, &bt, k, 1);
-    knn_neighbour_t *d_out = dev_out ? out : ix->d_out;
+    *d_out = dst ? dst : ix->d_out;
     if (!rc) {
         hipEventRecord(ix->e0, NULL);
-        rc = run_pack(ix, q.src, &bt, layout, src_dtype);
+        rc = run_pack(ix, q->src, &bt, layout, src_dtype);
         if (!rc) rc = stream_wait();
-        if (!rc) rc = run_finish(ix, q.src, &bt, layout, src_dtype, flags, d_out);
+        if (!rc) rc = run_finish(ix, q->src, &bt, layout, src_dtype, flags, *d_out);
     }
+    return rc;
+}
+
+int knn_index_query(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int flags,
+                    knn_neighbour_t *out)
+{
+    if (!out) return KNN_ERR_INVALID;
+    RCHK(query_check(ix, Q, mq, layout, src_dtype, k, flags));
+    if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
+    const int dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
+    dev_src_t q = {0};
+    knn_neighbour_t *d_out = NULL;
+    int rc = query_search(ix, Q, mq, layout, src_dtype, k, flags, dev_out ? out : NULL, &q, &d_out);
     rc = finish_search(ix, rc, out, dev_out, d_out, d_out, NULL, mq, k);
     dev_src_free(&q);
     return rc;
@@ -753,6 +791,19 @@ static void commit_meta(knn_index_t *ix, const double *cmeta, int keep_s8)
     memcpy(ix->cmeta, cmeta, META_BYTES);
 }
 
+/* labels lo .. hi-1 (0-based: id - 1) changed on the host: the device copy's
+ * stale range grows to hold them (a host flag; labels_sync uploads) */
+static void labels_stale(knn_index_t *ix, size_t lo, size_t hi)
+{
+    if (ix->lab_lo == ix->lab_hi) {
+        ix->lab_lo = lo;
+        ix->lab_hi = hi;
+        return;
+    }
+    if (lo < ix->lab_lo) ix->lab_lo = lo;
+    if (hi > ix->lab_hi) ix->lab_hi = hi;
+}
+
 int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int src_dtype, const double *labels,
                   int flags)
 {
@@ -813,7 +864,10 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
         return rc;
     }
     commit_meta(ix, cmeta, keep_s8);
-    if (labels) memcpy(ix->labels + ix->last_id, labels, rows * sizeof(double));
+    if (labels) {
+        memcpy(ix->labels + ix->last_id, labels, rows * sizeof(double));
+        labels_stale(ix, ix->last_id, id1);
+    }
     ix->nblk = nb1;
     ix->m = m1;
     ix->last_id = id1;
@@ -996,7 +1050,10 @@ int knn_index_update(knn_index_t *ix, const int32_t *ids, size_t count, const vo
     if (!rc) {
         commit_meta(ix, cmeta, keep_s8);
         if (labels)
-            for (size_t i = 0; i < count; i++) ix->labels[ids[i] - 1] = labels[i];
+            for (size_t i = 0; i < count; i++) {
+                ix->labels[ids[i] - 1] = labels[i];
+                labels_stale(ix, (size_t)ids[i] - 1, (size_t)ids[i]);
+            }
     }
     knn_up_plan_free(&pl);
     return rc;
@@ -1043,59 +1100,251 @@ static int gather_tiles(knn_index_t *ix, const void *const *d_tab, const int32_t
     return KNN_OK;
 }
 
-int knn_index_neighbours(knn_index_t *ix, const int32_t *ids, size_t count, int k, int flags, knn_neighbour_t *out)
+/* what knn_index_neighbours refuses before any device call (its caller: a
+ * NULL out) */
+static int rows_check(const knn_index_t *ix, const int32_t *ids, size_t count, int k, int flags)
 {
-    if (!ix || !out || k <= 0 || (ids ? count == 0 : count != 0)) return KNN_ERR_INVALID;
+    if (!ix || k <= 0 || (ids ? count == 0 : count != 0)) return KNN_ERR_INVALID;
     if (flags & ~(KNN_QUERY_KEEP_ZERO | KNN_INDEX_DEVICE_OUT)) return KNN_ERR_INVALID;
     /* keep-zero: the row itself comes back among its own neighbours and is
      * taken out afterwards, so the engine searches one more */
-    const int kz = (flags & KNN_QUERY_KEEP_ZERO) != 0, dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
-    if (k > k_max(ix->dtype) - kz) return KNN_ERR_UNSUPPORTED;
+    if (k > k_max(ix->dtype) - ((flags & KNN_QUERY_KEEP_ZERO) != 0)) return KNN_ERR_UNSUPPORTED;
     const size_t mq = ids ? count : ix->m;
     if (mq > 0x7fffffffULL || ix->m + mq > 0x7fffffffULL) return KNN_ERR_INVALID;
     if (!ids_ok(ix, ids, count)) return KNN_ERR_INVALID;
-    /* the positions, on the host alone (knn_neighbours_plan.h) */
-    int32_t *pos = (int32_t *)malloc(mq * sizeof(int32_t));
-    if (!pos) return KNN_ERR_NOMEM;
-    if (knn_nb_positions(ix->ids, ix->m, ids, count, pos)) {
-        free(pos);
+    return KNN_OK;
+}
+
+/* what a rows call holds until its end: the rows' positions and the blocks'
+ * pointers on the device; where the records are due (d_out) and where the
+ * tiles write them (d_rec) */
+typedef struct {
+    int32_t *d_pos;
+    void **d_tab;
+    knn_neighbour_t *d_out, *d_rec;
+} rows_t;
+
+static void rows_free(rows_t *r)
+{
+    hipFree(r->d_pos);
+    hipFree(r->d_tab);
+}
+
+/* the listed rows' positions (ids NULL: every live row's), on the host alone
+ * (knn_neighbours_plan.h); KNN_ERR_INVALID for an id that is not live */
+static int rows_plan(const knn_index_t *ix, const int32_t *ids, size_t count, int32_t **pos)
+{
+    *pos = (int32_t *)malloc((ids ? count : ix->m) * sizeof(int32_t));
+    if (!*pos) return KNN_ERR_NOMEM;
+    if (knn_nb_positions(ix->ids, ix->m, ids, count, *pos)) {
+        free(*pos);
         return KNN_ERR_INVALID;
     }
+    return KNN_OK;
+}
+
+/* knn_index_neighbours behind its plan (pos, mq positions, freed here) through
+ * the last tile's search; the records are due in dst (device), or in the
+ * index's own buffer (dst NULL).  The caller ends the call (finish_search, or
+ * search_tail and the vote) and frees *r, whatever is returned here. */
+static int rows_search(knn_index_t *ix, int32_t *pos, size_t mq, int k, int kz, knn_neighbour_t *dst, rows_t *r)
+{
     const size_t cnt = mq * (size_t)k, wide = kz ? mq * (size_t)(k + 1) : 0;
     const batch_t bt = tile_shape(ix, mq);
     int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
     /* every allocation and upload in front of the span: the positions, the
-     * blocks' pointers (element, then byte), the records of a host-out call
-     * and behind them the k + 1 wide ones of a keep-zero call */
+     * blocks' pointers (element, then byte), the records of a call without
+     * dst and behind them the k + 1 wide ones of a keep-zero call */
     const int use_s8 = s8_stays(ix, ix->cmeta);
-    int32_t *d_pos = NULL;
-    void **d_tab = NULL;
-    if (!rc) rc = index_out(ix, (dev_out ? 0 : cnt) + wide);
-    if (!rc && hipMalloc((void **)&d_pos, mq * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
-    if (!rc && hipMalloc((void **)&d_tab, 2 * ix->nblk * sizeof(void *)) != hipSuccess) rc = KNN_ERR_NOMEM;
-    if (!rc && (hipMemcpy(d_pos, pos, mq * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_tab, ix->b.blk, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_tab + ix->nblk, ix->b.s8, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess))
+    if (!rc) rc = index_out(ix, (dst ? 0 : cnt) + wide);
+    if (!rc && hipMalloc((void **)&r->d_pos, mq * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc && hipMalloc((void **)&r->d_tab, 2 * ix->nblk * sizeof(void *)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc && (hipMemcpy(r->d_pos, pos, mq * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(r->d_tab, ix->b.blk, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(r->d_tab + ix->nblk, ix->b.s8, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) !=
+                    hipSuccess))
         rc = KNN_ERR_HIP;
     free(pos);
     if (!rc) rc = index_reserve(ix, &bt, k + kz, 1);
     if (!rc && use_s8) rc = reserve_ts8(ix, bt.ntile);
-    knn_neighbour_t *d_out = dev_out ? out : ix->d_out;
-    knn_neighbour_t *d_rec = d_out;   /* what the tiles write */
-    if (!rc && kz) d_rec = ix->d_out + (dev_out ? 0 : cnt);
+    r->d_out = dst ? dst : ix->d_out;
+    r->d_rec = r->d_out;   /* what the tiles write */
+    if (!rc && kz) r->d_rec = ix->d_out + (dst ? 0 : cnt);
     if (!rc) {
         hipEventRecord(ix->e0, NULL);
         /* the batch's reduced meta is the corpus's: the queries are corpus
          * rows and cmeta only grows.  No tile meta is read back, so the host
          * does not wait between the gathers and the searches. */
         rc = put_meta(ix, NULL, 0);
-        if (!rc) rc = gather_tiles(ix, (const void *const *)d_tab, d_pos, &bt, use_s8);
+        if (!rc) rc = gather_tiles(ix, (const void *const *)r->d_tab, r->d_pos, &bt, use_s8);
         knn_ctx_set_keep_zero(ix->ctx, kz);
-        if (!rc) rc = search_tiles(ix, &bt, use_s8, d_rec);
+        if (!rc) rc = search_tiles(ix, &bt, use_s8, r->d_rec);
     }
-    rc = finish_search(ix, rc, out, dev_out, d_out, d_rec, d_pos, mq, k);
-    hipFree(d_pos);
-    hipFree(d_tab);
+    return rc;
+}
+
+int knn_index_neighbours(knn_index_t *ix, const int32_t *ids, size_t count, int k, int flags, knn_neighbour_t *out)
+{
+    if (!out) return KNN_ERR_INVALID;
+    RCHK(rows_check(ix, ids, count, k, flags));
+    const int kz = (flags & KNN_QUERY_KEEP_ZERO) != 0, dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
+    const size_t mq = ids ? count : ix->m;
+    int32_t *pos = NULL;
+    RCHK(rows_plan(ix, ids, count, &pos));
+    rows_t r = {0};
+    int rc = rows_search(ix, pos, mq, k, kz, dev_out ? out : NULL, &r);
+    rc = finish_search(ix, rc, out, dev_out, r.d_out, r.d_rec, r.d_pos, mq, k);
+    rows_free(&r);
+    return rc;
+}
+
+/* ------------------------------------------------------------- classify */
+
+static int vote_check(const knn_index_t *ix, const int *pred, int nclasses, int vote_rule)
+{
+    if (!ix || !pred || !ix->labels || nclasses <= 0) return KNN_ERR_INVALID;
+    if (vote_rule != KNN_VOTE_SERIAL && vote_rule != KNN_VOTE_MPI && vote_rule != KNN_VOTE_MAJORITY)
+        return KNN_ERR_INVALID;
+    return nclasses > KNN_VOTE_MAX_CLASSES ? KNN_ERR_UNSUPPORTED : KNN_OK;
+}
+
+/* The labels' device copy, by id: made here at the first classify call (room
+ * for lab_cap labels, as on the host), made again when the ids have outgrown
+ * it, and otherwise brought up to date by what add and update marked stale.
+ * In front of the span; a failure leaves the marks for the next call. */
+static int labels_sync(knn_index_t *ix)
+{
+    if (ix->dlab_cap < ix->last_id) {
+        double *d = NULL;
+        if (hipMalloc((void **)&d, ix->lab_cap * sizeof(double)) != hipSuccess) return KNN_ERR_NOMEM;
+        if (hipMemcpy(d, ix->labels, ix->last_id * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+            hipFree(d);
+            return KNN_ERR_HIP;
+        }
+        hipFree(ix->d_labels);
+        ix->d_labels = d;
+        ix->dlab_cap = ix->lab_cap;
+    } else if (ix->lab_lo < ix->lab_hi &&
+               hipMemcpy(ix->d_labels + ix->lab_lo, ix->labels + ix->lab_lo, (ix->lab_hi - ix->lab_lo) * sizeof(double),
+                         hipMemcpyHostToDevice) != hipSuccess) {
+        return KNN_ERR_HIP;
+    }
+    ix->lab_lo = ix->lab_hi = 0;
+    return KNN_OK;
+}
+
+/* What a classify call holds on the device besides its records, in one
+ * allocation that lives for the call: the match counter (matches: NULL when
+ * the call counts none), the batch's own labels (qlab) or the listed rows'
+ * ids (own), and pred and counts of a host-out call -- under
+ * KNN_INDEX_DEVICE_OUT those two are the caller's. */
+typedef struct {
+    void *buf;
+    unsigned long long *matches;
+    double *qlab;
+    int32_t *own;
+    int *pred, *counts;
+} vote_t;
+
+static int vote_reserve(vote_t *v, size_t mq, int nclasses, int dev_out, int want_matches, const double *qlabels,
+                        const int32_t *ids, int *pred, int *counts)
+{
+    /* 8-byte entries first, then the 4-byte ones */
+    const size_t nq = qlabels ? mq : 0, nown = ids ? mq : 0, npred = dev_out ? 0 : mq;
+    const size_t ncnt = !dev_out && counts ? mq * (size_t)nclasses : 0;
+    if (hipMalloc(&v->buf, sizeof(unsigned long long) + nq * sizeof(double) + (nown + npred + ncnt) * sizeof(int32_t)) !=
+        hipSuccess)
+        return KNN_ERR_NOMEM;
+    unsigned long long *m8 = (unsigned long long *)v->buf;
+    double *ql = (double *)(m8 + 1);
+    int32_t *i4 = (int32_t *)(ql + nq);
+    v->matches = want_matches ? m8 : NULL;
+    v->qlab = qlabels ? ql : NULL;
+    v->own = ids ? i4 : NULL;
+    v->pred = dev_out ? pred : (int *)(i4 + nown);
+    v->counts = dev_out ? counts : counts ? (int *)(i4 + nown + npred) : NULL;
+    if (qlabels && hipMemcpy(ql, qlabels, mq * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return KNN_ERR_HIP;
+    if (ids && hipMemcpy(i4, ids, mq * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) return KNN_ERR_HIP;
+    return KNN_OK;
+}
+
+/* The end of a classify call that stands at rc behind search_tail, its mq x k
+ * records in d_out: the vote (outside the span, as serial:94-98 stops its timer
+ * in front of it; d_own: the rows' ids on the device, see
+ * knn_launch_vote_index), then what a host-out call copies back, the match
+ * count, and a wait -- every output is complete on return.  A failed call keeps
+ * nothing, as in finish_search. */
+static int vote_finish(knn_index_t *ix, int rc, vote_t *v, knn_neighbour_t *d_out, const int32_t *d_own, size_t mq,
+                       int k, int nclasses, int vote_rule, int dev_out, int *pred, int *counts, size_t *matches,
+                       knn_neighbour_t *out)
+{
+    unsigned long long hit = 0;
+    if (!rc)
+        rc = knn_launch_vote_index(d_out, mq, k, nclasses, vote_rule, ix->d_labels, ix->last_id, v->qlab, d_own,
+                                   v->pred, v->counts, v->matches, NULL);
+    if (!rc && !dev_out &&
+        (hipMemcpy(pred, v->pred, mq * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+         (counts && hipMemcpy(counts, v->counts, mq * (size_t)nclasses * sizeof(int), hipMemcpyDeviceToHost) !=
+                        hipSuccess) ||
+         (out && hipMemcpy(out, d_out, mq * (size_t)k * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)))
+        rc = KNN_ERR_HIP;
+    if (!rc && v->matches && hipMemcpy(&hit, v->matches, sizeof(hit), hipMemcpyDeviceToHost) != hipSuccess)
+        rc = KNN_ERR_HIP;
+    if (!rc) rc = stream_wait();
+    if (rc) {
+        hipStreamSynchronize(NULL);
+        free_query_state(ix);
+    } else if (matches) {
+        *matches = (size_t)hit;
+    }
+    hipFree(v->buf);
+    return rc;
+}
+
+int knn_index_classify(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int nclasses,
+                       int vote_rule, int flags, const double *qlabels, int *pred, int *counts, size_t *matches,
+                       knn_neighbour_t *out)
+{
+    RCHK(vote_check(ix, pred, nclasses, vote_rule));
+    RCHK(query_check(ix, Q, mq, layout, src_dtype, k, flags));
+    if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
+    const int dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
+    vote_t v = {0};
+    dev_src_t q = {0};
+    knn_neighbour_t *d_out = NULL;
+    /* the labels and the vote's buffers in front of the span, then
+     * knn_index_query's call up to its copy back */
+    int rc = labels_sync(ix);
+    if (!rc) rc = vote_reserve(&v, mq, nclasses, dev_out, qlabels && matches, qlabels, NULL, pred, counts);
+    if (!rc) rc = query_search(ix, Q, mq, layout, src_dtype, k, flags, dev_out ? out : NULL, &q, &d_out);
+    rc = search_tail(ix, rc, d_out, d_out, NULL, mq, k);
+    rc = vote_finish(ix, rc, &v, d_out, NULL, mq, k, nclasses, vote_rule, dev_out, pred, counts, matches, out);
+    dev_src_free(&q);
+    return rc;
+}
+
+int knn_index_classify_rows(knn_index_t *ix, const int32_t *ids, size_t count, int k, int nclasses, int vote_rule,
+                            int flags, int *pred, int *counts, size_t *matches, knn_neighbour_t *out)
+{
+    RCHK(vote_check(ix, pred, nclasses, vote_rule));
+    RCHK(rows_check(ix, ids, count, k, flags));
+    const int kz = (flags & KNN_QUERY_KEEP_ZERO) != 0, dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
+    const size_t mq = ids ? count : ix->m;
+    int32_t *pos = NULL;
+    RCHK(rows_plan(ix, ids, count, &pos));
+    vote_t v = {0};
+    rows_t r = {0};
+    int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+    if (!rc) rc = labels_sync(ix);
+    if (!rc) rc = vote_reserve(&v, mq, nclasses, dev_out, matches != NULL, NULL, ids, pred, counts);
+    if (!rc) rc = rows_search(ix, pos, mq, k, kz, dev_out ? out : NULL, &r);
+    else free(pos);
+    rc = search_tail(ix, rc, r.d_out, r.d_rec, r.d_pos, mq, k);
+    /* a row's own label is the index's label of its id: the listed ids, or
+     * every live row's (the id map; none while nothing was removed: q + 1) */
+    const int32_t *d_own = ids ? v.own : ix->ids ? ix->d_ids : NULL;
+    rc = vote_finish(ix, rc, &v, r.d_out, d_own, mq, k, nclasses, vote_rule, dev_out, pred, counts, matches, out);
+    rows_free(&r);
     return rc;
 }
 
@@ -1122,6 +1371,7 @@ int knn_index_info(const knn_index_t *ix, size_t *m, size_t *n, int *nblocks, si
         }
         b += ix->out_recs * sizeof(knn_neighbour_t);
         if (ix->d_ids) b += ix->ids_cap * sizeof(int32_t);
+        b += ix->dlab_cap * sizeof(double);
         *device_bytes = b + knn_ctx_device_bytes(ix->ctx);
     }
     return KNN_OK;

@@ -298,6 +298,15 @@ int knn_launch_rescan_end(int kp, const int *fail_list, int nfail, const double 
 int knn_launch_vote(knn_neighbour_t *nb, size_t m, int k, int nclasses, int rule,
                     const double *labels, size_t nlabels, size_t q_base, int *pred,
                     unsigned long long *matches, void *stream);
+/* knn_kernels.hip: the vote of knn_index_classify / knn_index_classify_rows
+ * (k_vote_index) over mq x k records whose idx are ids into labels (nlabels of
+ * them, by id).  A query's own label: qlab[q] (device, nullable), else
+ * labels[own_ids[q] - 1] (own_ids NULL: labels[q]); read only when matches
+ * (nullable, one device counter, zeroed here) is given.  pred: mq ints; counts
+ * (nullable): mq x nclasses ints, each query's histogram; .label is filled */
+int knn_launch_vote_index(knn_neighbour_t *nb, size_t mq, int k, int nclasses, int rule, const double *labels,
+                          size_t nlabels, const double *qlab, const int32_t *own_ids, int *pred, int *counts,
+                          unsigned long long *matches, void *stream);
 /* knn_pack.hip: block elements <-> int16 wire elements (cnt % 8 == 0) */
 int knn_launch_wire(int unpack, void *dst, const void *src, int dtype, size_t cnt, void *stream);
 /* knn_engine.c: the value knn_last_search_seconds() returns (this thread) */

@@ -2298,6 +2298,53 @@ extern "C" int knn_launch_rescan_end(int kp, const int *fail_list, int nfail, co
 // label (serial:126-127).  The neighbour records get their .label filled
 // (blk:176).  Empty slots and idx > nlabels are skipped.
 // ---------------------------------------------------------------------------
+// What k_vote and k_vote_index share.  vote_fill: the wave's lanes stride over
+// query L's k records, write each one's .label and count it into the wave's
+// histogram c, which every lane may read on return.  vote_pick: one lane's walk
+// over that histogram, knn_vote.c's to the letter.
+__device__ __forceinline__ void vote_fill(knn_neighbour_t *L, int k, int lane, int *c, int nclasses,
+                                          const double *__restrict__ labels, long long nlabels)
+{
+    for (int i = lane; i < k; i += 64) {
+        const int id = L[i].idx;
+        int lab = 0;
+        if (id > 0 && id <= nlabels) {
+            lab = (int)labels[id - 1];
+            L[i].label = lab;
+            if (lab >= 1 && lab <= nclasses) atomicAdd(&c[lab - 1], 1);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+__device__ __forceinline__ int vote_pick(const knn_neighbour_t *L, int k, const int *c, int nclasses, int rule,
+                                         const double *__restrict__ labels, long long nlabels)
+{
+    int most = 0;
+    if (rule == KNN_VOTE_MAJORITY) {
+        int best = 0;
+        for (int j = 0; j < nclasses; j++) best = c[j] > best ? c[j] : best;
+        for (int i = 0; i < k && best > 0; i++) {
+            const int id = L[i].idx;
+            if (id <= 0 || id > nlabels) continue;
+            const int lab = (int)labels[id - 1];
+            if (lab >= 1 && lab <= nclasses && c[lab - 1] == best) {
+                most = lab;
+                break;
+            }
+        }
+    } else {
+        const int id0 = L[0].idx;
+        const int nn0 = (id0 > 0 && id0 <= nlabels) ? (int)labels[id0 - 1] : 0;
+        const int tie = rule == KNN_VOTE_MPI ? nn0 - 1 : nn0;
+        for (int j = 0; j < nclasses; j++)
+            if (c[j] > most || (c[j] == most && (j + 1) == tie)) most = j + 1;
+    }
+    return most;
+}
+
 __global__ __launch_bounds__(256) void k_vote(knn_neighbour_t *__restrict__ nb, int m, int k,
                                               int nclasses, int rule,
                                               const double *__restrict__ labels,
@@ -2316,39 +2363,9 @@ __global__ __launch_bounds__(256) void k_vote(knn_neighbour_t *__restrict__ nb, 
     unsigned hit = 0;
     if (q < m) {
         knn_neighbour_t *L = nb + (size_t)q * k;
-        for (int i = lane; i < k; i += 64) {
-            const int id = L[i].idx;
-            int lab = 0;
-            if (id > 0 && id <= nlabels) {
-                lab = (int)labels[id - 1];
-                L[i].label = lab;
-                if (lab >= 1 && lab <= nclasses) atomicAdd(&c[lab - 1], 1);
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        vote_fill(L, k, lane, c, nclasses, labels, nlabels);
         if (lane == 0) {
-            int most = 0;
-            if (rule == KNN_VOTE_MAJORITY) {
-                int best = 0;
-                for (int j = 0; j < nclasses; j++) best = c[j] > best ? c[j] : best;
-                for (int i = 0; i < k && best > 0; i++) {
-                    const int id = L[i].idx;
-                    if (id <= 0 || id > nlabels) continue;
-                    const int lab = (int)labels[id - 1];
-                    if (lab >= 1 && lab <= nclasses && c[lab - 1] == best) {
-                        most = lab;
-                        break;
-                    }
-                }
-            } else {
-                const int id0 = L[0].idx;
-                const int nn0 = (id0 > 0 && id0 <= nlabels) ? (int)labels[id0 - 1] : 0;
-                const int tie = rule == KNN_VOTE_MPI ? nn0 - 1 : nn0;
-                for (int j = 0; j < nclasses; j++)
-                    if (c[j] > most || (c[j] == most && (j + 1) == tie)) most = j + 1;
-            }
+            const int most = vote_pick(L, k, c, nclasses, rule, labels, nlabels);
             if (pred) pred[q] = most;
             const long long g = q_base + q;
             hit = (g < nlabels && (double)most == labels[g]) ? 1u : 0u;
@@ -2373,6 +2390,73 @@ extern "C" int knn_launch_vote(knn_neighbour_t *nb, size_t m, int k, int nclasse
         return KNN_ERR_HIP;
     hipLaunchKernelGGL(k_vote, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s, nb, (int)m, k,
                        nclasses, rule, labels, (long long)nlabels, (long long)q_base, pred, matches);
+    return hip_status();
+}
+
+// ---------------------------------------------------------------------------
+// k_vote_index: the vote of knn_index_classify / knn_index_classify_rows, on
+// the records behind the id remap.  k_vote's layout (one wave a query, four
+// queries a workgroup, the wave's LDS histogram, lanes striding over k) and its
+// fill and walk; what differs is where a query's own label comes from -- qlab[q]
+// (the batch's labels, uploaded), or labels[id - 1] of the resident row it is,
+// id = own_ids[q] (NULL: q + 1, every row of an index that removed nothing), or
+// nowhere (matches == NULL) -- and counts (nullable): the histogram itself,
+// nclasses ints a query, stored behind the wave's barrier.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_vote_index(knn_neighbour_t *__restrict__ nb, int m, int k, int nclasses,
+                                                    int rule, const double *__restrict__ labels, long long nlabels,
+                                                    const double *__restrict__ qlab,
+                                                    const int *__restrict__ own_ids, int *__restrict__ pred,
+                                                    int *__restrict__ counts,
+                                                    unsigned long long *__restrict__ matches)
+{
+    __shared__ int cls[4][KNN_VOTE_MAX_CLASSES];
+    __shared__ unsigned hits[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int q = blockIdx.x * 4 + wave;
+    int *c = cls[wave];
+    for (int j = lane; j < nclasses; j += 64) c[j] = 0;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    unsigned hit = 0;
+    if (q < m) {
+        knn_neighbour_t *L = nb + (size_t)q * k;
+        vote_fill(L, k, lane, c, nclasses, labels, nlabels);
+        if (counts)
+            for (int j = lane; j < nclasses; j += 64) counts[(size_t)q * nclasses + j] = c[j];
+        if (lane == 0) {
+            const int most = vote_pick(L, k, c, nclasses, rule, labels, nlabels);
+            pred[q] = most;
+            if (matches) {
+                if (qlab) {
+                    hit = (double)most == qlab[q] ? 1u : 0u;
+                } else {
+                    const long long id = own_ids ? own_ids[q] : q + 1;
+                    hit = (id >= 1 && id <= nlabels && (double)most == labels[id - 1]) ? 1u : 0u;
+                }
+            }
+        }
+    }
+    if (lane == 0) hits[wave] = hit;
+    __syncthreads();
+    if (threadIdx.x == 0 && matches) {
+        const unsigned h = hits[0] + hits[1] + hits[2] + hits[3];
+        if (h) atomicAdd(matches, (unsigned long long)h);
+    }
+}
+
+extern "C" int knn_launch_vote_index(knn_neighbour_t *nb, size_t mq, int k, int nclasses, int rule,
+                                     const double *labels, size_t nlabels, const double *qlab,
+                                     const int32_t *own_ids, int *pred, int *counts, unsigned long long *matches,
+                                     void *stream)
+{
+    if (mq == 0) return KNN_OK;
+    if (k <= 0 || nclasses <= 0 || !pred) return KNN_ERR_INVALID;
+    if (nclasses > KNN_VOTE_MAX_CLASSES || mq > 0x7fffffffULL) return KNN_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    if (matches && hipMemsetAsync(matches, 0, sizeof(unsigned long long), s) != hipSuccess) return KNN_ERR_HIP;
+    hipLaunchKernelGGL(k_vote_index, dim3((unsigned)((mq + 3) / 4)), dim3(256), 0, s, nb, (int)mq, k, nclasses, rule,
+                       labels, (long long)nlabels, qlab, own_ids, pred, counts, matches);
     return hip_status();
 }
 

@@ -56,6 +56,7 @@ API_SYMBOLS = (
     "knn_index_remove", "knn_index_last_id", "knn_block_gather_dt", "knn_block_gather_s8",
     "knn_index_update", "knn_block_scatter_dt", "knn_block_scatter_s8",
     "knn_index_neighbours", "knn_block_gather_pos_dt", "knn_block_gather_pos_s8",
+    "knn_index_classify", "knn_index_classify_rows",
 )
 DTYPES = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 # a pack / index SOURCE may also be unsigned bytes (KNN_U8: never a block or search dtype)
@@ -163,6 +164,8 @@ def _load():
         "knn_block_scatter_dt": ([p, i, sz, p, p, sz, sz, p, sz, i, sz, i, p], i),
         "knn_block_scatter_s8": ([p, i, sz, p, p, sz, sz, p, sz, i, sz, i, p], i),
         "knn_index_neighbours": ([p, p, sz, i, i, p], i),
+        "knn_index_classify": ([p, p, sz, i, i, i, i, i, i, p, p, p, psz, p], i),
+        "knn_index_classify_rows": ([p, p, sz, i, i, i, i, p, p, psz, p], i),
         "knn_block_gather_pos_dt": ([p, sz, sz, p, sz, sz, p, sz, sz, i, p], i),
         "knn_block_gather_pos_s8": ([p, sz, sz, p, sz, sz, p, sz, sz, p], i),
     }
@@ -470,6 +473,7 @@ def _close_all():
 INDEX_DEVICE_SRC = 2  # KNN_INDEX_DEVICE_SRC
 INDEX_DEVICE_OUT = 4  # KNN_INDEX_DEVICE_OUT
 IndexInfo = collections.namedtuple("IndexInfo", "m n nblocks device_bytes last_bits")
+ClassifyResult = collections.namedtuple("ClassifyResult", "pred matches counts neighbours seconds")
 _NP_SRC = {np.dtype(np.uint8): U8, np.dtype(np.float32): F32, np.dtype(np.float64): F64}
 
 
@@ -674,6 +678,85 @@ class Index:
         _check(lib.knn_index_neighbours(self._h, _ptr(a), rows if a is not None else 0, k, flags, optr),
                "knn_index_neighbours")
         return res, lib.knn_last_search_seconds()
+
+    def _vote_outputs(self, rows, k, nclasses, counts, neighbours, out, flags):
+        """pred, counts and records of a classify call, on the device when out
+        (as in query) is given, with their pointers and the call's flags"""
+        if out is not None:
+            import torch
+            if not _is_device_tensor(out) or not out.is_contiguous() or \
+                    out.numel() * out.element_size() < rows * k * NB_DTYPE.itemsize:
+                raise ValueError("out must be a contiguous torch GPU buffer of >= %d bytes" %
+                                 (rows * k * NB_DTYPE.itemsize))
+            _on_index_device(out, "out")
+            pred = torch.empty(rows, dtype=torch.int32, device=out.device)
+            cnt = torch.empty((rows, max(nclasses, 0)), dtype=torch.int32, device=out.device) if counts else None
+            ptrs = [ctypes.c_void_p(t.data_ptr()) if t is not None else None for t in (pred, cnt, out)]
+            return pred, cnt, out, ptrs, flags | INDEX_DEVICE_OUT
+        pred = np.zeros(rows, dtype=np.int32)
+        cnt = np.zeros((rows, max(nclasses, 0)), dtype=np.int32) if counts else None
+        nb = np.zeros((rows, max(k, 0)), dtype=NB_DTYPE) if neighbours else None
+        return pred, cnt, nb, [_ptr(pred), _ptr(cnt), _ptr(nb)], flags
+
+    def classify(self, Q, k=30, keep_zero=True, qlabels=None, nclasses=10, rule=VOTE_SERIAL, counts=False,
+                 out=None, neighbours=False):
+        """knn_index_classify: query's search for the rows of Q (handled as
+        there), then the vote among each one's k neighbours with the index's
+        own labels, on the device.  qlabels: the rows' true labels (host), for
+        matches.  Returns ClassifyResult(pred, matches, counts, neighbours,
+        seconds): pred a numpy int32 array of mq predictions (what
+        classify_query gives for query's records); matches the number of
+        pred[q] == qlabels[q] (0 without qlabels); counts (counts=True) the
+        (mq, nclasses) int32 histogram each vote ran on, else None; neighbours
+        (neighbours=True) the (mq, k) records with their labels, else None;
+        seconds the search's device span (the vote is outside it).  out: a
+        torch GPU uint8 buffer of mq*k*16 bytes as in query -- it receives the
+        records (labels filled) and is returned as neighbours, and pred and
+        counts are then torch int32 tensors on the same device: the whole
+        result stays there."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        ptr, keep, mq, n, lay, src, flags = _index_source(Q, self.layout, "Q")
+        if n != self.n:
+            raise ValueError("Q must be (mq, %d), got (%d, %d)" % (self.n, mq, n))
+        if keep_zero:
+            flags |= QUERY_KEEP_ZERO
+        ql = None if qlabels is None else np.ascontiguousarray(qlabels, dtype=np.float64)
+        if ql is not None and ql.shape != (mq,):
+            raise ValueError("qlabels must have %d entries, got %r" % (mq, ql.shape))
+        pred, cnt, nb, (pp, cp, op), flags = self._vote_outputs(mq, k, nclasses, counts, neighbours, out, flags)
+        hit = ctypes.c_size_t()
+        _check(lib.knn_index_classify(self._h, ptr, mq, lay, src, k, nclasses, rule, flags, _ptr(ql), pp, cp,
+                                      ctypes.byref(hit), op), "knn_index_classify")
+        del keep
+        return ClassifyResult(pred, hit.value, cnt, nb, lib.knn_last_search_seconds())
+
+    def classify_rows(self, ids=None, k=30, keep_zero=True, nclasses=10, rule=VOTE_SERIAL, counts=False, out=None,
+                      neighbours=False):
+        """knn_index_classify_rows: neighbours' search for the listed ids
+        (ids=None: every live row in ascending id), then the vote; a row's own
+        label is the index's.  With ids=None and keep_zero=False on an index
+        that removed nothing: search plus classify, the reference's whole
+        program.  Arguments and the ClassifyResult as in classify; matches
+        counts the rows predicted as their own label."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        if ids is None:
+            a, rows = None, self.m
+        else:
+            a = np.asarray(ids).reshape(-1)
+            if a.size and a.dtype.kind not in "iu":
+                raise ValueError("ids must be integers, got %s" % a.dtype)
+            if a.size == 0 or a.min() < -2 ** 31 or a.max() >= 2 ** 31:   # (an empty list is not ids=None)
+                raise KnnError(ERR_INVALID, "knn_index_classify_rows")
+            a = np.ascontiguousarray(a, dtype=np.int32)
+            rows = a.size
+        pred, cnt, nb, (pp, cp, op), flags = self._vote_outputs(rows, k, nclasses, counts, neighbours, out,
+                                                                QUERY_KEEP_ZERO if keep_zero else 0)
+        hit = ctypes.c_size_t()
+        _check(lib.knn_index_classify_rows(self._h, _ptr(a), rows if a is not None else 0, k, nclasses, rule, flags,
+                                           pp, cp, ctypes.byref(hit), op), "knn_index_classify_rows")
+        return ClassifyResult(pred, hit.value, cnt, nb, lib.knn_last_search_seconds())
 
     @property
     def last_id(self):
