@@ -405,7 +405,9 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * knn_last_search_seconds() keeps reporting the search span alone: the vote is
  * outside it, as serial:94-98 stops its timer in front of the vote.  Every
  * output is complete on return; a failed call leaves the index answering as
- * before.
+ * before, and has written none of its host outputs (pred, counts, out,
+ * *matches); under KNN_INDEX_DEVICE_OUT the caller's device arrays may hold
+ * what the vote wrote before the failure.
  *
  * knn_index_classify_rows: the same behind knn_index_neighbours -- ids, count,
  * ids == NULL, the keep-zero rule and its k + 1 limit as there; row i's own

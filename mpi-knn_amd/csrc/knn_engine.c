@@ -9,6 +9,7 @@
  * (knn_query() and the resident index: knn_index.c).
  */
 #include "knn_internal.h"
+#include "knn_buf.h"
 
 #include <hip/hip_runtime_api.h>
 #include <math.h>
@@ -30,13 +31,9 @@
 #define KNN_PSETS 4       /* partial-list sets: step s uses set s % 4   */
 #define KNN_PROF_STEPS 64 /* steps timed between two knn_ctx_end calls */
 
-/* A device buffer the context owns: its pointer and its bytes.  Allocated,
+/* A device buffer the context owns is a knn_buf_t (knn_buf.h): allocated,
  * grown and released only by the buf_* functions below, which keep the
  * context's byte count (dev_bytes) in step. */
-typedef struct {
-    void *p;
-    size_t bytes;
-} knn_buf_t;
 
 struct knn_ctx {
     int device;
@@ -320,26 +317,17 @@ int knn_block_pack(void *d_block, size_t cap, size_t rows, size_t n, const doubl
 
 /* ---- the context's device memory ----------------------------------------- */
 
-static void buf_release(knn_ctx_t *c, knn_buf_t *b)
-{
-    hipFree(b->p);
-    c->dev_bytes -= b->bytes;
-    b->p = NULL;
-    b->bytes = 0;
-}
+static void buf_release(knn_ctx_t *c, knn_buf_t *b) { knn_buf_release(&c->dev_bytes, b); }
 
 /* The n empty buffers of g[] with bytes[] bytes each: all of them or, with
  * KNN_ERR_NOMEM, none. */
 static int buf_alloc(knn_ctx_t *c, int n, knn_buf_t *const *g, const size_t *bytes)
 {
     for (int i = 0; i < n; i++) {
-        if (hipMalloc(&g[i]->p, bytes[i]) != hipSuccess) {
-            g[i]->p = NULL;
+        if (knn_buf_alloc(&c->dev_bytes, g[i], bytes[i])) {
             while (i-- > 0) buf_release(c, g[i]);
             return KNN_ERR_NOMEM;
         }
-        g[i]->bytes = bytes[i];
-        c->dev_bytes += bytes[i];
     }
     return KNN_OK;
 }

@@ -5,9 +5,15 @@
  * The corpus is resident as blocks of one capacity (KNN_QUERY_BLOCK=rows
  * overrides the choice): element blocks, their meta MAX-reduced on the host,
  * and byte blocks while that meta passes knn_s8_spec_ok.  The per-block host
- * arrays are one blocks_t; set_counts, blocks_release, fresh_blocks,
- * write_meta_words, read_meta and drop_s8 are what every entry point does
- * with them.  A batch of queries is a batch_t: tiles of at most
+ * arrays are one blocks_t; set_counts, fresh_blocks, write_meta_words,
+ * read_meta and drop_s8 are what every entry point does with them.  The device
+ * memory the index holds between calls has one owner: the byte count
+ * dev_bytes, kept by knn_buf_alloc / knn_buf_release (knn_buf.h, shared with
+ * the context) under own_grow, own_grow_keep (d_meta, d_out, d_ids, d_labels:
+ * each a knn_buf_t that knows its size) and image_alloc, images_release (the
+ * blocks and tiles, by their set's capacity); knn_index_info reports that
+ * count and the context's.  What a call allocates for itself (scratch) is
+ * freed on every exit and not counted.  A batch of queries is a batch_t: tiles of at most
  * KNN_QUERY_TILE_MAX rows (KNN_QUERY_TILE=rows overrides that, for tests) with
  * ids m.. (past every corpus id, so no row is ever "the query itself").
  * Every entry point reads: checks, plan, reserve, enqueue, wait, commit.
@@ -15,9 +21,11 @@
  * source (dev_src_t) in two parts around one wait.  query: run_pack /
  * run_finish pack the tiles, MAX-reduce their meta with the corpus's
  * (put_meta) and run search_tiles -- per tile the ring rank's sequence against
- * foreign blocks (blk:217-242; query_tile) -- and finish_search ends the call:
- * ids for positions, the span, the records, which stay on the device until
- * the last tile is done (a timed span holds no copy to the host).  add: the
+ * foreign blocks (blk:217-242; query_tile) -- and finish_search ends every
+ * search call: ids for positions, the span, a classify call's vote, the
+ * records, which stay on the device until the last tile is done (a timed span
+ * holds no copy to the host), and on failure a wait and the query state
+ * dropped.  add: the
  * two parts again for rows that arrive later, the packs at a row offset, behind
  * index_reblock where the blocks would become too many.  remove: compacts the
  * blocks from the first removed row on with the block gathers
@@ -26,14 +34,17 @@
  * commit_meta).  neighbours: tiles filled from the blocks by position
  * (knn_neighbours_plan.h), the same search_tiles, and under the keep-zero rule
  * k + 1 with the row itself taken out afterwards (k_drop_self).  classify,
- * classify_rows: query's and neighbours' bodies (query_search, rows_search)
- * up to the span's end (search_tail), then the vote over the records on the
- * device (vote_finish) with the labels' device copy, which the first such call
- * makes and add / update keep marked (labels_sync, labels_stale).  The
+ * classify_rows: query's and neighbours' calls (query_call, rows_call) with a
+ * vote_t: vote_begin in front of the span -- the labels' device copy, which
+ * the first such call makes and add / update keep marked (labels_sync,
+ * labels_stale), and the vote's scratch -- and the vote over the records on
+ * the device behind it, its host outputs through a staging array so that a
+ * failed call has written none of them.  The
  * knn_block_* operations are in knn_blocks.c; what a failed call leaves behind
  * is swept on a CPU by tests/index_trace.
  */
 #include "knn_internal.h"
+#include "knn_buf.h"
 #include "knn_remove_plan.h"
 #include "knn_update_plan.h"
 #include "knn_neighbours_plan.h"
@@ -70,19 +81,23 @@ struct knn_index {
     blocks_t b;
     int have_s8;
     double cmeta[KNN_META_DOUBLES];   /* host copy of the corpus's reduced meta */
+    /* every byte of device memory the index holds between calls, the
+     * context's aside (kept by knn_buf_alloc / knn_buf_release alone) */
+    size_t dev_bytes;
     double *labels;
     size_t lab_cap;                   /* doubles allocated at labels (>= last_id: labels are indexed by id) */
-    /* d_labels: the labels' device copy, of dlab_cap doubles, made by the
-     * first classify call (labels_sync); entries lab_lo .. lab_hi-1 of it are
-     * stale, marked by add and update and uploaded by the next classify call */
-    double *d_labels;
-    size_t dlab_cap, lab_lo, lab_hi;
+    /* d_labels: the labels' device copy, made by the first classify call
+     * (labels_sync); entries lab_lo .. lab_hi-1 of it are stale, marked by add
+     * and update and uploaded by the next classify call */
+    knn_buf_t d_labels;
+    size_t lab_lo, lab_hi;
     /* ids: row p (0-based position in the blocks) has the 1-based id ids[p],
      * ascending.  NULL until the first removal: the id is then p + 1 and
-     * last_id == m.  d_ids: its device copy (both of ids_cap entries). */
+     * last_id == m.  d_ids: its device copy, of ids_cap() entries (the host
+     * array has at least as many). */
     size_t last_id;
-    int32_t *ids, *d_ids;
-    size_t ids_cap;
+    int32_t *ids;
+    knn_buf_t d_ids;
     /* kept between queries: the context (for k, tile_cap query rows), ntile
      * tile buffers of capacity tile_cap (byte forms allocated on first use),
      * the records of a host-out call, the reduced meta, the span's events */
@@ -91,9 +106,9 @@ struct knn_index {
     size_t tile_cap, ntile;
     void **tblk, **ts8;
     double *thm;                      /* the tiles' meta as read back */
-    knn_neighbour_t *d_out;
-    size_t out_recs;
-    double *d_meta, *red;             /* the reduced meta of the batch: device, and its pinned host copy */
+    knn_buf_t d_out;
+    knn_buf_t d_meta;                 /* the reduced meta of the batch on the device ... */
+    double *red;                      /* ... and its pinned host copy */
     hipEvent_t e0, e1;
     int last_bits;
 };
@@ -155,15 +170,73 @@ static int blocks_alloc(blocks_t *b, size_t na)
     return KNN_OK;
 }
 
-/* the device memory of blocks b0 .. b1-1, both images */
-static void blocks_release(void **blk, void **s8, size_t b0, size_t b1)
+/* ---- the index's device memory (dev_bytes) ------------------------------- */
+
+/* at least `need` bytes in b; what it held is gone when it grows */
+static int own_grow(knn_index_t *ix, knn_buf_t *b, size_t need)
 {
-    for (size_t b = b0; b < b1; b++) {
-        hipFree(blk[b]);
-        hipFree(s8[b]);
-        blk[b] = s8[b] = NULL;
-    }
+    if (need <= b->bytes) return KNN_OK;
+    knn_buf_release(&ix->dev_bytes, b);
+    return knn_buf_alloc(&ix->dev_bytes, b, need);
 }
+
+/* b anew with `bytes` bytes, the first `keep` of them uploaded from the host
+ * copy; the old memory goes once the new one is filled.  All or nothing. */
+static int own_grow_keep(knn_index_t *ix, knn_buf_t *b, size_t bytes, const void *host, size_t keep)
+{
+    knn_buf_t nb = {0};
+    RCHK(knn_buf_alloc(&ix->dev_bytes, &nb, bytes));
+    if (hipMemcpy(nb.p, host, keep, hipMemcpyHostToDevice) != hipSuccess) {
+        knn_buf_release(&ix->dev_bytes, &nb);
+        return KNN_ERR_HIP;
+    }
+    knn_buf_release(&ix->dev_bytes, b);
+    *b = nb;
+    return KNN_OK;
+}
+
+/* one image of a block or tile of capacity cap: elements and norms, or bytes */
+static size_t image_bytes(const knn_index_t *ix, size_t cap, int s8)
+{
+    return s8 ? knn_s8_bytes(cap, ix->n) : knn_block_bytes_dt(cap, ix->n, ix->dtype);
+}
+
+/* *p: that image's memory, where it has none yet */
+static int image_alloc(knn_index_t *ix, void **p, size_t cap, int s8)
+{
+    knn_buf_t b = {0};
+    if (*p) return KNN_OK;
+    RCHK(knn_buf_alloc(&ix->dev_bytes, &b, image_bytes(ix, cap, s8)));
+    *p = b.p;
+    return KNN_OK;
+}
+
+/* the device memory of buffers b0 .. b1-1 of capacity cap: both images, or
+ * the one whose array is given */
+static void images_release(knn_index_t *ix, void **blk, void **s8, size_t cap, size_t b0, size_t b1)
+{
+    for (size_t b = b0; b < b1; b++)
+        for (int i = 0; i < 2; i++) {
+            void **a = i ? s8 : blk;
+            if (!a || !a[b]) continue;
+            knn_buf_t t = {a[b], image_bytes(ix, cap, i)};
+            knn_buf_release(&ix->dev_bytes, &t);
+            a[b] = NULL;
+        }
+}
+
+/* Per-call scratch -- an uploaded source, id and position lists, the vote's
+ * buffer: not counted, and freed (scratch_free; NULL is fine) on every exit of
+ * the call that made it. */
+static int scratch(void **p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess ? KNN_OK : KNN_ERR_NOMEM; }
+static void scratch_free(void *p) { hipFree(p); }
+
+static int upload(void *dst, const void *src, size_t bytes)
+{
+    return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+}
+
+static size_t ids_cap(const knn_index_t *ix) { return ix->d_ids.bytes / sizeof(int32_t); }
 
 /* cnc / cbase of the nblk blocks that hold m rows */
 static void set_counts(knn_index_t *ix)
@@ -177,25 +250,21 @@ static void set_counts(knn_index_t *ix)
 /* a value outside the byte image arrived: the element path from now on */
 static void drop_s8(knn_index_t *ix)
 {
-    for (size_t b = 0; b < ix->nblk; b++) {
-        hipFree(ix->b.s8[b]);
-        ix->b.s8[b] = NULL;
-    }
+    images_release(ix, NULL, ix->b.s8, ix->cap, 0, ix->nblk);
     ix->have_s8 = 0;
 }
 
 /* Fresh buffers for rebuilt blocks b0 .. b1-1 of capacity cap, into blk[] and
  * (where the index has byte blocks) s8[]: the element image zeroed, the byte
  * image when zero_s8.  On failure the caller releases what was made. */
-static int fresh_blocks(const knn_index_t *ix, size_t cap, size_t b0, size_t b1, void **blk, void **s8, int zero_s8)
+static int fresh_blocks(knn_index_t *ix, size_t cap, size_t b0, size_t b1, void **blk, void **s8, int zero_s8)
 {
-    const size_t ebytes = knn_block_bytes_dt(cap, ix->n, ix->dtype), sbytes = knn_s8_bytes(cap, ix->n);
     for (size_t b = b0; b < b1; b++) {
-        if (hipMalloc(&blk[b], ebytes) != hipSuccess) return KNN_ERR_NOMEM;
-        if (hipMemsetAsync(blk[b], 0, ebytes, NULL) != hipSuccess) return KNN_ERR_HIP;
+        RCHK(image_alloc(ix, &blk[b], cap, 0));
+        if (hipMemsetAsync(blk[b], 0, image_bytes(ix, cap, 0), NULL) != hipSuccess) return KNN_ERR_HIP;
         if (!ix->have_s8) continue;
-        if (hipMalloc(&s8[b], sbytes) != hipSuccess) return KNN_ERR_NOMEM;
-        if (zero_s8 && hipMemsetAsync(s8[b], 0, sbytes, NULL) != hipSuccess) return KNN_ERR_HIP;
+        RCHK(image_alloc(ix, &s8[b], cap, 1));
+        if (zero_s8 && hipMemsetAsync(s8[b], 0, image_bytes(ix, cap, 1), NULL) != hipSuccess) return KNN_ERR_HIP;
     }
     return KNN_OK;
 }
@@ -233,7 +302,7 @@ static int put_meta(knn_index_t *ix, const double *hm, size_t nb)
 {
     memcpy(ix->red, ix->cmeta, META_BYTES);
     meta_max(ix->red, hm, nb);
-    return hipMemcpyAsync(ix->d_meta, ix->red, META_BYTES, hipMemcpyHostToDevice, NULL) == hipSuccess ? KNN_OK
+    return hipMemcpyAsync(ix->d_meta.p, ix->red, META_BYTES, hipMemcpyHostToDevice, NULL) == hipSuccess ? KNN_OK
                                                                                                         : KNN_ERR_HIP;
 }
 
@@ -248,19 +317,16 @@ static int dev_src(dev_src_t *d, const void *X, size_t bytes, int flags)
 {
     d->src = X;
     if (flags & KNN_INDEX_DEVICE_SRC) return KNN_OK;
-    if (hipMalloc(&d->own, bytes) != hipSuccess) return KNN_ERR_NOMEM;
+    RCHK(scratch(&d->own, bytes));
     d->src = d->own;
-    return hipMemcpy(d->own, X, bytes, hipMemcpyHostToDevice) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+    return upload(d->own, X, bytes);
 }
 
-static void dev_src_free(dev_src_t *d) { hipFree(d->own); }
+static void dev_src_free(dev_src_t *d) { scratch_free(d->own); }
 
 static void free_query_state(knn_index_t *ix)
 {
-    for (size_t t = 0; t < ix->ntile; t++) {
-        hipFree(ix->tblk[t]);
-        hipFree(ix->ts8[t]);
-    }
+    images_release(ix, ix->tblk, ix->ts8, ix->tile_cap, 0, ix->ntile);
     free(ix->tblk);
     free(ix->ts8);
     free(ix->thm);
@@ -275,11 +341,11 @@ static void index_free(knn_index_t *ix)
 {
     if (!ix) return;
     free_query_state(ix);
-    if (ix->b.blk) blocks_release(ix->b.blk, ix->b.s8, 0, ix->nblk);
-    hipFree(ix->d_out);
-    hipFree(ix->d_meta);
-    hipFree(ix->d_ids);
-    hipFree(ix->d_labels);
+    if (ix->b.blk) images_release(ix, ix->b.blk, ix->b.s8, ix->cap, 0, ix->nblk);
+    knn_buf_release(&ix->dev_bytes, &ix->d_out);
+    knn_buf_release(&ix->dev_bytes, &ix->d_meta);
+    knn_buf_release(&ix->dev_bytes, &ix->d_ids);
+    knn_buf_release(&ix->dev_bytes, &ix->d_labels);
     free(ix->ids);
     if (ix->red) hipHostFree(ix->red);
     if (ix->e0) hipEventDestroy(ix->e0);
@@ -305,7 +371,7 @@ static int index_alloc(knn_index_t **out, size_t m, size_t n, int dtype)
     ix->nblk = (m + ix->cap - 1) / ix->cap;   /* (<= INT32_MAX) */
     ix->nalloc = ix->nblk;
     int rc = blocks_alloc(&ix->b, ix->nblk);
-    if (!rc && (hipMalloc((void **)&ix->d_meta, META_BYTES) != hipSuccess ||
+    if (!rc && (own_grow(ix, &ix->d_meta, META_BYTES) ||
                 hipHostMalloc((void **)&ix->red, META_BYTES, hipHostMallocDefault) != hipSuccess))
         rc = KNN_ERR_NOMEM;
     if (!rc && (hipEventCreate(&ix->e0) != hipSuccess || hipEventCreate(&ix->e1) != hipSuccess)) rc = KNN_ERR_HIP;
@@ -338,37 +404,16 @@ static int index_grow_arrays(knn_index_t *ix, size_t nb)
 /* the id map (host and device) for at least `need` entries, its m entries kept */
 static int index_ids_reserve(knn_index_t *ix, size_t need)
 {
-    if (need <= ix->ids_cap) return KNN_OK;
-    const size_t nc = 2 * ix->ids_cap > need ? 2 * ix->ids_cap : need;
-    int32_t *d = NULL;
-    if (hipMalloc((void **)&d, nc * sizeof(int32_t)) != hipSuccess) return KNN_ERR_NOMEM;
+    if (need <= ids_cap(ix)) return KNN_OK;
+    const size_t nc = 2 * ids_cap(ix) > need ? 2 * ids_cap(ix) : need;
     int32_t *h = (int32_t *)realloc(ix->ids, nc * sizeof(int32_t));
-    if (!h) {
-        hipFree(d);
-        return KNN_ERR_NOMEM;
-    }
+    if (!h) return KNN_ERR_NOMEM;
     ix->ids = h;   /* (the same entries, whatever follows) */
-    if (hipMemcpy(d, h, ix->m * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(d);
-        return KNN_ERR_HIP;
-    }
-    hipFree(ix->d_ids);
-    ix->d_ids = d;
-    ix->ids_cap = nc;
-    return KNN_OK;
+    return own_grow_keep(ix, &ix->d_ids, nc * sizeof(int32_t), h, ix->m * sizeof(int32_t));
 }
 
 /* the index's own record buffer, for cnt records */
-static int index_out(knn_index_t *ix, size_t cnt)
-{
-    if (cnt <= ix->out_recs) return KNN_OK;
-    hipFree(ix->d_out);
-    ix->d_out = NULL;
-    ix->out_recs = 0;
-    if (hipMalloc((void **)&ix->d_out, cnt * sizeof(knn_neighbour_t)) != hipSuccess) return KNN_ERR_NOMEM;
-    ix->out_recs = cnt;
-    return KNN_OK;
-}
+static int index_out(knn_index_t *ix, size_t cnt) { return own_grow(ix, &ix->d_out, cnt * sizeof(knn_neighbour_t)); }
 
 /* Pack rows r0.. of a `tot`-row device source into nb buffers of capacity bc
  * (buffer b: rows r0 = b * step ..), element blocks (s8 = 0; their meta
@@ -396,9 +441,7 @@ static int pack_rows(const knn_index_t *ix, void *const *buf, size_t nb, size_t 
 static int index_alloc_blocks(knn_index_t *ix)
 {
     set_counts(ix);
-    for (size_t b = 0; b < ix->nblk; b++)
-        if (!ix->b.blk[b] && hipMalloc(&ix->b.blk[b], knn_block_bytes_dt(ix->cap, ix->n, ix->dtype)) != hipSuccess)
-            return KNN_ERR_NOMEM;
+    for (size_t b = 0; b < ix->nblk; b++) RCHK(image_alloc(ix, &ix->b.blk[b], ix->cap, 0));
     return KNN_OK;
 }
 
@@ -426,8 +469,7 @@ static int build_finish(knn_index_t *ix, const void *d_X, int layout, int src_dt
     if (batch_hm) meta_max(joint, batch_hm, batch_n);
     ix->have_s8 = knn_s8_spec_ok(joint, ix->n, ix->dtype);
     if (!ix->have_s8) return KNN_OK;
-    for (size_t b = 0; b < ix->nblk; b++)
-        if (hipMalloc(&ix->b.s8[b], knn_s8_bytes(ix->cap, ix->n)) != hipSuccess) return KNN_ERR_NOMEM;
+    for (size_t b = 0; b < ix->nblk; b++) RCHK(image_alloc(ix, &ix->b.s8[b], ix->cap, 1));
     return pack_rows(ix, ix->b.s8, ix->nblk, ix->cap, ix->cap, d_X, ix->m, layout, src_dtype, 1, NULL);
 }
 
@@ -477,18 +519,14 @@ static int index_reserve(knn_index_t *ix, const batch_t *bt, int k, int grow)
         ix->ts8 = b;
         ix->ntile = ntile;
     }
-    for (size_t t = 0; t < ntile; t++)
-        if (!ix->tblk[t] && hipMalloc(&ix->tblk[t], knn_block_bytes_dt(ix->tile_cap, ix->n, ix->dtype)) != hipSuccess)
-            return KNN_ERR_NOMEM;
+    for (size_t t = 0; t < ntile; t++) RCHK(image_alloc(ix, &ix->tblk[t], ix->tile_cap, 0));
     return KNN_OK;
 }
 
 /* the byte forms of the batch's tiles, allocated on first use */
 static int reserve_ts8(knn_index_t *ix, size_t ntile)
 {
-    for (size_t t = 0; t < ntile; t++)
-        if (!ix->ts8[t] && hipMalloc(&ix->ts8[t], knn_s8_bytes(ix->tile_cap, ix->n)) != hipSuccess)
-            return KNN_ERR_NOMEM;
+    for (size_t t = 0; t < ntile; t++) RCHK(image_alloc(ix, &ix->ts8[t], ix->tile_cap, 1));
     return KNN_OK;
 }
 
@@ -529,7 +567,7 @@ static int search_tiles(knn_index_t *ix, const batch_t *bt, int use_s8, knn_neig
     for (size_t t = 0; t < bt->ntile; t++) {
         const size_t r0 = t * bt->tcap, rows = bt->mq - r0 < bt->tcap ? bt->mq - r0 : bt->tcap;
         RCHK(query_tile(ix->ctx, ix->nblk, ix->b.blk, use_s8 ? ix->b.s8 : NULL, ix->b.cnc, ix->b.cbase, ix->tblk[t],
-                        use_s8 ? ix->ts8[t] : NULL, ix->tile_cap, rows, ix->m + r0, ix->d_meta, ix->red,
+                        use_s8 ? ix->ts8[t] : NULL, ix->tile_cap, rows, ix->m + r0, (const double *)ix->d_meta.p, ix->red,
                         d_rec + r0 * (size_t)ix->k));
     }
     ix->last_bits = knn_ctx_contraction_bits(ix->ctx);
@@ -577,34 +615,114 @@ static void fill_labels(knn_neighbour_t *out, size_t cnt, const double *labels)
     for (size_t i = 0; i < cnt; i++) out[i].label = out[i].idx > 0 ? (int32_t)labels[out[i].idx - 1] : 0;
 }
 
+/* ---- the vote of a classify call ----------------------------------------- */
+
+/* The labels' device copy, by id: made here at the first classify call (room
+ * for lab_cap labels, as on the host), made again when the ids have outgrown
+ * it, and otherwise brought up to date by what add and update marked stale.
+ * In front of the span; a failure leaves the marks for the next call. */
+static int labels_sync(knn_index_t *ix)
+{
+    if (ix->d_labels.bytes / sizeof(double) < ix->last_id)
+        RCHK(own_grow_keep(ix, &ix->d_labels, ix->lab_cap * sizeof(double), ix->labels, ix->last_id * sizeof(double)));
+    else if (ix->lab_lo < ix->lab_hi)
+        RCHK(upload((double *)ix->d_labels.p + ix->lab_lo, ix->labels + ix->lab_lo,
+                    (ix->lab_hi - ix->lab_lo) * sizeof(double)));
+    ix->lab_lo = ix->lab_hi = 0;
+    return KNN_OK;
+}
+
+/* A classify call's vote: its arguments (by_row: a row's own label is the
+ * index's label of its id -- ids, or every live row's), and what it holds on
+ * the device besides its records, in one scratch allocation: the match counter
+ * (d_matches: NULL when the call counts none), the batch's own labels (d_qlab)
+ * or the listed rows' ids, and pred and counts of a host-out call -- under
+ * KNN_INDEX_DEVICE_OUT those two are the caller's.  launch: knn_launch_vote_index,
+ * named by the classify entry points alone, so that a program which links
+ * only the others needs no vote kernel. */
+typedef struct {
+    int (*launch)(knn_neighbour_t *, size_t, int, int, int, const double *, size_t, const double *, const int32_t *,
+                  int *, int *, unsigned long long *, void *);
+    int nclasses, rule, by_row;
+    const double *qlabels;
+    const int32_t *ids;
+    int *pred, *counts;
+    size_t *matches;
+    void *buf;
+    unsigned long long *d_matches;
+    double *d_qlab;
+    const int32_t *d_own;   /* the rows' ids (by_row; NULL: q + 1, nothing was removed) */
+    int *d_pred, *d_counts;
+} vote_t;
+
+/* the labels and the vote's buffer, in front of the span */
+static int vote_begin(knn_index_t *ix, vote_t *v, size_t mq, int dev_out)
+{
+    RCHK(labels_sync(ix));
+    /* 8-byte entries first, then the 4-byte ones */
+    const size_t nq = v->qlabels ? mq : 0, nown = v->ids ? mq : 0, npred = dev_out ? 0 : mq;
+    const size_t ncnt = !dev_out && v->counts ? mq * (size_t)v->nclasses : 0;
+    RCHK(scratch(&v->buf, sizeof(unsigned long long) + nq * sizeof(double) + (nown + npred + ncnt) * sizeof(int32_t)));
+    unsigned long long *m8 = (unsigned long long *)v->buf;
+    double *ql = (double *)(m8 + 1);
+    int32_t *i4 = (int32_t *)(ql + nq);
+    v->d_matches = v->matches && (v->qlabels || v->by_row) ? m8 : NULL;
+    v->d_qlab = v->qlabels ? ql : NULL;
+    v->d_own = v->ids ? i4 : v->by_row && ix->ids ? (const int32_t *)ix->d_ids.p : NULL;
+    v->d_pred = dev_out ? v->pred : (int *)(i4 + nown);
+    v->d_counts = dev_out ? v->counts : v->counts ? (int *)(i4 + nown + npred) : NULL;
+    if (v->qlabels) RCHK(upload(ql, v->qlabels, mq * sizeof(double)));
+    if (v->ids) RCHK(upload(i4, v->ids, mq * sizeof(int32_t)));
+    return KNN_OK;
+}
+
+static int download(void *dst, const void *src, size_t bytes)
+{
+    return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+}
+
 /* The end of a search call that stands at rc, its mq x k records due in d_out:
  * positions -> ids where rows were removed (the tiles wrote k + 1 wide records
  * to d_rec != d_out: the row itself, d_pos, out of them in the same pass) and
- * the span's end (search_tail); then records and labels to the host.  A failed
- * call keeps nothing. */
-static int search_tail(knn_index_t *ix, int rc, knn_neighbour_t *d_out, const knn_neighbour_t *d_rec,
-                       const int32_t *d_pos, size_t mq, int k)
+ * the span's end; then records and labels to the host.  With a vote (v, whose
+ * buffer is freed here): the vote behind the span (serial:94-98 stops its timer
+ * in front of it), pred and counts to the host in front of the records, the
+ * match count behind them, and a wait.  A failed call keeps no query state and
+ * writes no output of a classify call: those arrive in a staging array. */
+static int finish_search(knn_index_t *ix, int rc, vote_t *v, knn_neighbour_t *out, int dev_out,
+                         knn_neighbour_t *d_out, const knn_neighbour_t *d_rec, const int32_t *d_pos, size_t mq, int k)
 {
-    if (!rc && d_rec != d_out)
-        rc = knn_launch_drop_self(d_out, d_rec, d_pos, mq, k, ix->ids ? ix->d_ids : NULL, ix->m, NULL);
-    else if (!rc && ix->ids) rc = knn_launch_remap_idx(d_out, mq * (size_t)k, ix->d_ids, ix->m, NULL);
+    const int32_t *d_ids = ix->ids ? (const int32_t *)ix->d_ids.p : NULL;
+    const size_t cnt = mq * (size_t)k, out_b = !dev_out && out ? cnt * sizeof(knn_neighbour_t) : 0;
+    const size_t pred_b = v && !dev_out ? mq * sizeof(int) : 0;
+    const size_t counts_b = pred_b && v->counts ? mq * (size_t)v->nclasses * sizeof(int) : 0;
+    unsigned long long hit = 0;
+    char *stage = NULL;
+    if (!rc && d_rec != d_out) rc = knn_launch_drop_self(d_out, d_rec, d_pos, mq, k, d_ids, ix->m, NULL);
+    else if (!rc && d_ids) rc = knn_launch_remap_idx(d_out, cnt, d_ids, ix->m, NULL);
     if (!rc) rc = span_end(ix);
-    return rc;
-}
-
-static int finish_search(knn_index_t *ix, int rc, knn_neighbour_t *out, int dev_out, knn_neighbour_t *d_out,
-                         const knn_neighbour_t *d_rec, const int32_t *d_pos, size_t mq, int k)
-{
-    const size_t cnt = mq * (size_t)k;
-    rc = search_tail(ix, rc, d_out, d_rec, d_pos, mq, k);
-    if (!rc && !dev_out && hipMemcpy(out, d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = KNN_ERR_HIP;
+    if (!rc && v)
+        rc = v->launch(d_out, mq, k, v->nclasses, v->rule, (const double *)ix->d_labels.p, ix->last_id, v->d_qlab,
+                       v->d_own, v->d_pred, v->d_counts, v->d_matches, NULL);
+    if (!rc && pred_b && !(stage = (char *)malloc(pred_b + counts_b + out_b))) rc = KNN_ERR_NOMEM;
+    if (!rc && pred_b) rc = download(stage, v->d_pred, pred_b);
+    if (!rc && counts_b) rc = download(stage + pred_b, v->d_counts, counts_b);
+    if (!rc && out_b) rc = download(stage ? stage + pred_b + counts_b : (char *)out, d_out, out_b);
+    if (!rc && v && v->d_matches) rc = download(&hit, v->d_matches, sizeof(hit));
+    if (!rc && v) rc = stream_wait();
     if (rc) {
         hipStreamSynchronize(NULL);
         free_query_state(ix);
-    } else if (!dev_out && ix->labels) {
+    } else if (v) {
+        if (stage) memcpy(v->pred, stage, pred_b);
+        if (counts_b) memcpy(v->counts, stage + pred_b, counts_b);
+        if (stage && out_b) memcpy(out, stage + pred_b + counts_b, out_b);
+        if (v->matches) *v->matches = (size_t)hit;
+    } else if (out_b && ix->labels) {
         fill_labels(out, cnt, ix->labels);
     }
+    free(stage);
+    if (v) scratch_free(v->buf);
     return rc;
 }
 
@@ -656,8 +774,8 @@ static int query_check(const knn_index_t *ix, const void *Q, size_t mq, int layo
 
 /* knn_index_query from its reservations through the last tile's search: the
  * records go to dst (device), or to the index's own buffer (dst NULL), *d_out.
- * The caller ends the call (finish_search, or search_tail and the vote) and
- * frees *q, whatever is returned here. */
+ * The caller ends the call (finish_search) and frees *q, whatever is returned
+ * here. */
 static int query_search(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int flags,
                         knn_neighbour_t *dst, dev_src_t *q, knn_neighbour_t **d_out)
 {
@@ -665,7 +783,7 @@ static int query_search(knn_index_t *ix, const void *Q, size_t mq, int layout, i
     int rc = dst ? KNN_OK : index_out(ix, mq * (size_t)k);
     if (!rc) rc = dev_src(q, Q, mq * ix->n * knn_src_esize(src_dtype), flags);
     if (!rc) rc = index_reserve(ix, &bt, k, 1);
-    *d_out = dst ? dst : ix->d_out;
+    *d_out = dst ? dst : (knn_neighbour_t *)ix->d_out.p;
     if (!rc) {
         hipEventRecord(ix->e0, NULL);
         rc = run_pack(ix, q->src, &bt, layout, src_dtype);
@@ -675,19 +793,47 @@ static int query_search(knn_index_t *ix, const void *Q, size_t mq, int layout, i
     return rc;
 }
 
+/* knn_index_query, and with a vote (v) knn_index_classify: the labels and the
+ * vote's buffers in front of the span, the same call, the vote behind it */
+static int query_call(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int flags, vote_t *v,
+                      knn_neighbour_t *out)
+{
+    if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
+    const int dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
+    dev_src_t q = {0};
+    knn_neighbour_t *d_out = NULL;
+    int rc = v ? vote_begin(ix, v, mq, dev_out) : KNN_OK;
+    if (!rc) rc = query_search(ix, Q, mq, layout, src_dtype, k, flags, dev_out ? out : NULL, &q, &d_out);
+    rc = finish_search(ix, rc, v, out, dev_out, d_out, d_out, NULL, mq, k);
+    dev_src_free(&q);
+    return rc;
+}
+
 int knn_index_query(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int flags,
                     knn_neighbour_t *out)
 {
     if (!out) return KNN_ERR_INVALID;
     RCHK(query_check(ix, Q, mq, layout, src_dtype, k, flags));
-    if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
-    const int dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
-    dev_src_t q = {0};
-    knn_neighbour_t *d_out = NULL;
-    int rc = query_search(ix, Q, mq, layout, src_dtype, k, flags, dev_out ? out : NULL, &q, &d_out);
-    rc = finish_search(ix, rc, out, dev_out, d_out, d_out, NULL, mq, k);
-    dev_src_free(&q);
-    return rc;
+    return query_call(ix, Q, mq, layout, src_dtype, k, flags, NULL, out);
+}
+
+static int vote_check(const knn_index_t *ix, const int *pred, int nclasses, int vote_rule)
+{
+    if (!ix || !pred || !ix->labels || nclasses <= 0) return KNN_ERR_INVALID;
+    if (vote_rule != KNN_VOTE_SERIAL && vote_rule != KNN_VOTE_MPI && vote_rule != KNN_VOTE_MAJORITY)
+        return KNN_ERR_INVALID;
+    return nclasses > KNN_VOTE_MAX_CLASSES ? KNN_ERR_UNSUPPORTED : KNN_OK;
+}
+
+int knn_index_classify(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int nclasses,
+                       int vote_rule, int flags, const double *qlabels, int *pred, int *counts, size_t *matches,
+                       knn_neighbour_t *out)
+{
+    RCHK(vote_check(ix, pred, nclasses, vote_rule));
+    RCHK(query_check(ix, Q, mq, layout, src_dtype, k, flags));
+    vote_t v = {.launch = knn_launch_vote_index, .nclasses = nclasses, .rule = vote_rule, .qlabels = qlabels,
+                .pred = pred, .counts = counts, .matches = matches};
+    return query_call(ix, Q, mq, layout, src_dtype, k, flags, &v, out);
 }
 
 /* ------------------------------------------------------------------ add */
@@ -728,20 +874,20 @@ static int index_reblock(knn_index_t *ix, size_t ncap)
         double *st = stage + 2 * b * KNN_META_DOUBLES;
         rc = write_meta_words((char *)g.blk[b] + knn_block_meta_offset_dt(ncap, n, ix->dtype), hm, 0, st);
         if (rc || !ix->have_s8) continue;
-        rc = knn_launch_shadow8(g.s8[b], g.blk[b], ix->dtype, nrp, n, ix->d_meta, NULL);
+        rc = knn_launch_shadow8(g.s8[b], g.blk[b], ix->dtype, nrp, n, (const double *)ix->d_meta.p, NULL);
         if (!rc) rc = write_meta_words((char *)g.s8[b] + knn_s8_meta_offset(ncap, n), hm, 1, st + KNN_META_DOUBLES);
     }
     if (!rc) rc = stream_wait();
     else hipStreamSynchronize(NULL);
     free(stage);
     if (rc) {
-        if (g.blk) blocks_release(g.blk, g.s8, 0, nb);
+        if (g.blk) images_release(ix, g.blk, g.s8, ncap, 0, nb);
         blocks_free_arrays(&g);
         return rc;
     }
     /* commit; the context was made for the old capacity */
     free_query_state(ix);
-    blocks_release(ix->b.blk, ix->b.s8, 0, ix->nblk);
+    images_release(ix, ix->b.blk, ix->b.s8, ix->cap, 0, ix->nblk);
     blocks_free_arrays(&ix->b);
     ix->b = g;
     ix->cap = ncap;
@@ -766,8 +912,7 @@ static int add_rows(knn_index_t *ix, void **buf, const void *d_X, size_t rows, i
             RCHK(s8 ? knn_block_append_s8(buf[b], ix->dtype, cap, off, len, n, src, src_dtype, ld, layout, NULL)
                     : knn_block_append_dt(buf[b], ix->dtype, cap, off, len, n, src, src_dtype, ld, layout, NULL));
         } else {
-            const size_t bytes = s8 ? knn_s8_bytes(cap, n) : knn_block_bytes_dt(cap, n, ix->dtype);
-            if (!buf[b] && hipMalloc(&buf[b], bytes) != hipSuccess) return KNN_ERR_NOMEM;
+            RCHK(image_alloc(ix, &buf[b], cap, s8));
             RCHK(s8 ? knn_block_pack_s8(buf[b], ix->dtype, cap, len, n, src, src_dtype, ld, layout, NULL)
                     : knn_block_pack_dt(buf[b], ix->dtype, cap, len, n, src, src_dtype, ld, layout, NULL));
         }
@@ -850,8 +995,8 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
      * are read by nothing until m is committed below) */
     if (!rc && ix->ids) {
         for (size_t r = 0; r < rows; r++) ix->ids[ix->m + r] = (int32_t)(ix->last_id + 1 + r);
-        if (hipMemcpyAsync(ix->d_ids + ix->m, ix->ids + ix->m, rows * sizeof(int32_t), hipMemcpyHostToDevice, NULL) !=
-            hipSuccess)
+        if (hipMemcpyAsync((int32_t *)ix->d_ids.p + ix->m, ix->ids + ix->m, rows * sizeof(int32_t),
+                           hipMemcpyHostToDevice, NULL) != hipSuccess)
             rc = KNN_ERR_HIP;
     }
     /* the packs have read the source before the call returns */
@@ -860,7 +1005,7 @@ int knn_index_add(knn_index_t *ix, const void *X, size_t rows, int layout, int s
     dev_src_free(&x);
     if (rc) {
         /* rows written past a block's nc are never read, and its meta only grew */
-        blocks_release(ix->b.blk, ix->b.s8, nb0, nb1);
+        images_release(ix, ix->b.blk, ix->b.s8, ix->cap, nb0, nb1);
         return rc;
     }
     commit_meta(ix, cmeta, keep_s8);
@@ -890,7 +1035,7 @@ static int remove_move(knn_index_t *ix, const knn_rm_plan_t *pl, blocks_t *g)
     double *stage = (double *)calloc(2 * (nb1 - b0) * KNN_META_DOUBLES, sizeof(double));   /* until the wait */
     int rc = stage ? fresh_blocks(ix, cap, b0, nb1, g->blk, g->s8, 1) : KNN_ERR_NOMEM;
     /* the runs' lists, one array */
-    if (!rc && hipMalloc((void **)&d_list, pl->nlist * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc) rc = scratch((void **)&d_list, pl->nlist * sizeof(int32_t));
     if (!rc && hipMemcpyAsync(d_list, pl->list, pl->nlist * sizeof(int32_t), hipMemcpyHostToDevice, NULL) != hipSuccess)
         rc = KNN_ERR_HIP;
     for (size_t r = 0; r < pl->nruns && !rc; r++) {
@@ -911,9 +1056,9 @@ static int remove_move(knn_index_t *ix, const knn_rm_plan_t *pl, blocks_t *g)
     }
     if (!rc) rc = stream_wait();
     else hipStreamSynchronize(NULL);
-    hipFree(d_list);
+    scratch_free(d_list);
     free(stage);
-    if (rc) blocks_release(g->blk, g->s8, b0, nb1);
+    if (rc) images_release(ix, g->blk, g->s8, cap, b0, nb1);
     return rc;
 }
 
@@ -938,26 +1083,27 @@ int knn_index_remove(knn_index_t *ix, const int32_t *ids, size_t count, int flag
     if (prc) return KNN_ERR_NOMEM;
     int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
     /* the new id map beside the old one, and the moved blocks beside theirs */
-    const size_t icap = ix->ids_cap > pl.m1 ? ix->ids_cap : pl.m1;
-    int32_t *d_ids = NULL, *h_ids = NULL;
+    const size_t icap = ids_cap(ix) > pl.m1 ? ids_cap(ix) : pl.m1;
+    knn_buf_t d_ids = {0};
+    int32_t *h_ids = NULL;
     blocks_t g = {0};
     if (!rc) rc = blocks_alloc(&g, ix->nblk);
     if (!rc && !(h_ids = (int32_t *)malloc(icap * sizeof(int32_t)))) rc = KNN_ERR_NOMEM;
-    if (!rc && hipMalloc((void **)&d_ids, icap * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
+    if (!rc) rc = knn_buf_alloc(&ix->dev_bytes, &d_ids, icap * sizeof(int32_t));
     if (!rc) {
         memcpy(h_ids, pl.ids, pl.m1 * sizeof(int32_t));
-        if (hipMemcpy(d_ids, h_ids, pl.m1 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = KNN_ERR_HIP;
+        rc = upload(d_ids.p, h_ids, pl.m1 * sizeof(int32_t));
     }
     if (!rc && pl.moves) rc = remove_move(ix, &pl, &g);
     if (rc) {   /* the index answers as before the call */
-        hipFree(d_ids);
+        knn_buf_release(&ix->dev_bytes, &d_ids);
         free(h_ids);
     } else {
         /* commit: the moved blocks in place of the old ones, the blocks past
          * the new count released, then m, cnc, cbase, nblk and the id map.
          * cmeta stays: a MAX that has only become too large is conservative. */
         if (pl.moves) {
-            blocks_release(ix->b.blk, ix->b.s8, pl.b0, pl.nb1);
+            images_release(ix, ix->b.blk, ix->b.s8, ix->cap, pl.b0, pl.nb1);
             for (size_t b = pl.b0; b < pl.nb1; b++) {
                 ix->b.blk[b] = g.blk[b];
                 ix->b.s8[b] = g.s8[b];
@@ -965,15 +1111,14 @@ int knn_index_remove(knn_index_t *ix, const int32_t *ids, size_t count, int flag
             memcpy(ix->b.chm + pl.b0 * KNN_META_DOUBLES, g.chm + pl.b0 * KNN_META_DOUBLES,
                    (pl.nb1 - pl.b0) * META_BYTES);
         }
-        blocks_release(ix->b.blk, ix->b.s8, pl.nb1, ix->nblk);
+        images_release(ix, ix->b.blk, ix->b.s8, ix->cap, pl.nb1, ix->nblk);
         ix->m = pl.m1;
         ix->nblk = pl.nb1;
         set_counts(ix);
-        hipFree(ix->d_ids);
+        knn_buf_release(&ix->dev_bytes, &ix->d_ids);
         free(ix->ids);
         ix->ids = h_ids;
         ix->d_ids = d_ids;
-        ix->ids_cap = icap;
         if (removed) *removed = pl.removed;
     }
     blocks_free_arrays(&g);
@@ -1023,10 +1168,9 @@ int knn_index_update(knn_index_t *ix, const int32_t *ids, size_t count, const vo
     dev_src_t x = {0};
     int32_t *d_list = NULL;
     if (!rc) rc = dev_src(&x, X, count * ix->n * knn_src_esize(src_dtype), flags);
-    if (!rc && hipMalloc((void **)&d_list, 2 * count * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
-    if (!rc && (hipMemcpy(d_list, pl.pos, count * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(d_list + count, pl.srow, count * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess))
-        rc = KNN_ERR_HIP;
+    if (!rc) rc = scratch((void **)&d_list, 2 * count * sizeof(int32_t));
+    if (!rc) rc = upload(d_list, pl.pos, count * sizeof(int32_t));
+    if (!rc) rc = upload(d_list + count, pl.srow, count * sizeof(int32_t));
     /* From here on a failure leaves rows half written: KNN_ERR_HIP, and the
      * index is fit only for knn_index_destroy. */
     double cmeta[KNN_META_DOUBLES];
@@ -1046,7 +1190,7 @@ int knn_index_update(knn_index_t *ix, const int32_t *ids, size_t count, const vo
         if (rc) rc = KNN_ERR_HIP;
     }
     dev_src_free(&x);
-    hipFree(d_list);
+    scratch_free(d_list);
     if (!rc) {
         commit_meta(ix, cmeta, keep_s8);
         if (labels)
@@ -1126,8 +1270,8 @@ typedef struct {
 
 static void rows_free(rows_t *r)
 {
-    hipFree(r->d_pos);
-    hipFree(r->d_tab);
+    scratch_free(r->d_pos);
+    scratch_free(r->d_tab);
 }
 
 /* the listed rows' positions (ids NULL: every live row's), on the host alone
@@ -1145,8 +1289,8 @@ static int rows_plan(const knn_index_t *ix, const int32_t *ids, size_t count, in
 
 /* knn_index_neighbours behind its plan (pos, mq positions, freed here) through
  * the last tile's search; the records are due in dst (device), or in the
- * index's own buffer (dst NULL).  The caller ends the call (finish_search, or
- * search_tail and the vote) and frees *r, whatever is returned here. */
+ * index's own buffer (dst NULL).  The caller ends the call (finish_search) and
+ * frees *r, whatever is returned here. */
 static int rows_search(knn_index_t *ix, int32_t *pos, size_t mq, int k, int kz, knn_neighbour_t *dst, rows_t *r)
 {
     const size_t cnt = mq * (size_t)k, wide = kz ? mq * (size_t)(k + 1) : 0;
@@ -1157,19 +1301,17 @@ static int rows_search(knn_index_t *ix, int32_t *pos, size_t mq, int k, int kz, 
      * dst and behind them the k + 1 wide ones of a keep-zero call */
     const int use_s8 = s8_stays(ix, ix->cmeta);
     if (!rc) rc = index_out(ix, (dst ? 0 : cnt) + wide);
-    if (!rc && hipMalloc((void **)&r->d_pos, mq * sizeof(int32_t)) != hipSuccess) rc = KNN_ERR_NOMEM;
-    if (!rc && hipMalloc((void **)&r->d_tab, 2 * ix->nblk * sizeof(void *)) != hipSuccess) rc = KNN_ERR_NOMEM;
-    if (!rc && (hipMemcpy(r->d_pos, pos, mq * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(r->d_tab, ix->b.blk, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(r->d_tab + ix->nblk, ix->b.s8, ix->nblk * sizeof(void *), hipMemcpyHostToDevice) !=
-                    hipSuccess))
-        rc = KNN_ERR_HIP;
+    if (!rc) rc = scratch((void **)&r->d_pos, mq * sizeof(int32_t));
+    if (!rc) rc = scratch((void **)&r->d_tab, 2 * ix->nblk * sizeof(void *));
+    if (!rc) rc = upload(r->d_pos, pos, mq * sizeof(int32_t));
+    if (!rc) rc = upload(r->d_tab, ix->b.blk, ix->nblk * sizeof(void *));
+    if (!rc) rc = upload(r->d_tab + ix->nblk, ix->b.s8, ix->nblk * sizeof(void *));
     free(pos);
     if (!rc) rc = index_reserve(ix, &bt, k + kz, 1);
     if (!rc && use_s8) rc = reserve_ts8(ix, bt.ntile);
-    r->d_out = dst ? dst : ix->d_out;
+    r->d_out = dst ? dst : (knn_neighbour_t *)ix->d_out.p;
     r->d_rec = r->d_out;   /* what the tiles write */
-    if (!rc && kz) r->d_rec = ix->d_out + (dst ? 0 : cnt);
+    if (!rc && kz) r->d_rec = (knn_neighbour_t *)ix->d_out.p + (dst ? 0 : cnt);
     if (!rc) {
         hipEventRecord(ix->e0, NULL);
         /* the batch's reduced meta is the corpus's: the queries are corpus
@@ -1183,144 +1325,29 @@ static int rows_search(knn_index_t *ix, int32_t *pos, size_t mq, int k, int kz, 
     return rc;
 }
 
-int knn_index_neighbours(knn_index_t *ix, const int32_t *ids, size_t count, int k, int flags, knn_neighbour_t *out)
+/* knn_index_neighbours, and with a vote (v) knn_index_classify_rows */
+static int rows_call(knn_index_t *ix, const int32_t *ids, size_t count, int k, int flags, vote_t *v,
+                     knn_neighbour_t *out)
 {
-    if (!out) return KNN_ERR_INVALID;
-    RCHK(rows_check(ix, ids, count, k, flags));
     const int kz = (flags & KNN_QUERY_KEEP_ZERO) != 0, dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
     const size_t mq = ids ? count : ix->m;
     int32_t *pos = NULL;
     RCHK(rows_plan(ix, ids, count, &pos));
     rows_t r = {0};
-    int rc = rows_search(ix, pos, mq, k, kz, dev_out ? out : NULL, &r);
-    rc = finish_search(ix, rc, out, dev_out, r.d_out, r.d_rec, r.d_pos, mq, k);
+    int rc = KNN_OK;
+    if (v) rc = hipSetDevice(0) == hipSuccess ? vote_begin(ix, v, mq, dev_out) : KNN_ERR_HIP;
+    if (!rc) rc = rows_search(ix, pos, mq, k, kz, dev_out ? out : NULL, &r);
+    else free(pos);
+    rc = finish_search(ix, rc, v, out, dev_out, r.d_out, r.d_rec, r.d_pos, mq, k);
     rows_free(&r);
     return rc;
 }
 
-/* ------------------------------------------------------------- classify */
-
-static int vote_check(const knn_index_t *ix, const int *pred, int nclasses, int vote_rule)
+int knn_index_neighbours(knn_index_t *ix, const int32_t *ids, size_t count, int k, int flags, knn_neighbour_t *out)
 {
-    if (!ix || !pred || !ix->labels || nclasses <= 0) return KNN_ERR_INVALID;
-    if (vote_rule != KNN_VOTE_SERIAL && vote_rule != KNN_VOTE_MPI && vote_rule != KNN_VOTE_MAJORITY)
-        return KNN_ERR_INVALID;
-    return nclasses > KNN_VOTE_MAX_CLASSES ? KNN_ERR_UNSUPPORTED : KNN_OK;
-}
-
-/* The labels' device copy, by id: made here at the first classify call (room
- * for lab_cap labels, as on the host), made again when the ids have outgrown
- * it, and otherwise brought up to date by what add and update marked stale.
- * In front of the span; a failure leaves the marks for the next call. */
-static int labels_sync(knn_index_t *ix)
-{
-    if (ix->dlab_cap < ix->last_id) {
-        double *d = NULL;
-        if (hipMalloc((void **)&d, ix->lab_cap * sizeof(double)) != hipSuccess) return KNN_ERR_NOMEM;
-        if (hipMemcpy(d, ix->labels, ix->last_id * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-            hipFree(d);
-            return KNN_ERR_HIP;
-        }
-        hipFree(ix->d_labels);
-        ix->d_labels = d;
-        ix->dlab_cap = ix->lab_cap;
-    } else if (ix->lab_lo < ix->lab_hi &&
-               hipMemcpy(ix->d_labels + ix->lab_lo, ix->labels + ix->lab_lo, (ix->lab_hi - ix->lab_lo) * sizeof(double),
-                         hipMemcpyHostToDevice) != hipSuccess) {
-        return KNN_ERR_HIP;
-    }
-    ix->lab_lo = ix->lab_hi = 0;
-    return KNN_OK;
-}
-
-/* What a classify call holds on the device besides its records, in one
- * allocation that lives for the call: the match counter (matches: NULL when
- * the call counts none), the batch's own labels (qlab) or the listed rows'
- * ids (own), and pred and counts of a host-out call -- under
- * KNN_INDEX_DEVICE_OUT those two are the caller's. */
-typedef struct {
-    void *buf;
-    unsigned long long *matches;
-    double *qlab;
-    int32_t *own;
-    int *pred, *counts;
-} vote_t;
-
-static int vote_reserve(vote_t *v, size_t mq, int nclasses, int dev_out, int want_matches, const double *qlabels,
-                        const int32_t *ids, int *pred, int *counts)
-{
-    /* 8-byte entries first, then the 4-byte ones */
-    const size_t nq = qlabels ? mq : 0, nown = ids ? mq : 0, npred = dev_out ? 0 : mq;
-    const size_t ncnt = !dev_out && counts ? mq * (size_t)nclasses : 0;
-    if (hipMalloc(&v->buf, sizeof(unsigned long long) + nq * sizeof(double) + (nown + npred + ncnt) * sizeof(int32_t)) !=
-        hipSuccess)
-        return KNN_ERR_NOMEM;
-    unsigned long long *m8 = (unsigned long long *)v->buf;
-    double *ql = (double *)(m8 + 1);
-    int32_t *i4 = (int32_t *)(ql + nq);
-    v->matches = want_matches ? m8 : NULL;
-    v->qlab = qlabels ? ql : NULL;
-    v->own = ids ? i4 : NULL;
-    v->pred = dev_out ? pred : (int *)(i4 + nown);
-    v->counts = dev_out ? counts : counts ? (int *)(i4 + nown + npred) : NULL;
-    if (qlabels && hipMemcpy(ql, qlabels, mq * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return KNN_ERR_HIP;
-    if (ids && hipMemcpy(i4, ids, mq * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) return KNN_ERR_HIP;
-    return KNN_OK;
-}
-
-/* The end of a classify call that stands at rc behind search_tail, its mq x k
- * records in d_out: the vote (outside the span, as serial:94-98 stops its timer
- * in front of it; d_own: the rows' ids on the device, see
- * knn_launch_vote_index), then what a host-out call copies back, the match
- * count, and a wait -- every output is complete on return.  A failed call keeps
- * nothing, as in finish_search. */
-static int vote_finish(knn_index_t *ix, int rc, vote_t *v, knn_neighbour_t *d_out, const int32_t *d_own, size_t mq,
-                       int k, int nclasses, int vote_rule, int dev_out, int *pred, int *counts, size_t *matches,
-                       knn_neighbour_t *out)
-{
-    unsigned long long hit = 0;
-    if (!rc)
-        rc = knn_launch_vote_index(d_out, mq, k, nclasses, vote_rule, ix->d_labels, ix->last_id, v->qlab, d_own,
-                                   v->pred, v->counts, v->matches, NULL);
-    if (!rc && !dev_out &&
-        (hipMemcpy(pred, v->pred, mq * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-         (counts && hipMemcpy(counts, v->counts, mq * (size_t)nclasses * sizeof(int), hipMemcpyDeviceToHost) !=
-                        hipSuccess) ||
-         (out && hipMemcpy(out, d_out, mq * (size_t)k * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)))
-        rc = KNN_ERR_HIP;
-    if (!rc && v->matches && hipMemcpy(&hit, v->matches, sizeof(hit), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = KNN_ERR_HIP;
-    if (!rc) rc = stream_wait();
-    if (rc) {
-        hipStreamSynchronize(NULL);
-        free_query_state(ix);
-    } else if (matches) {
-        *matches = (size_t)hit;
-    }
-    hipFree(v->buf);
-    return rc;
-}
-
-int knn_index_classify(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int nclasses,
-                       int vote_rule, int flags, const double *qlabels, int *pred, int *counts, size_t *matches,
-                       knn_neighbour_t *out)
-{
-    RCHK(vote_check(ix, pred, nclasses, vote_rule));
-    RCHK(query_check(ix, Q, mq, layout, src_dtype, k, flags));
-    if (hipSetDevice(0) != hipSuccess) return KNN_ERR_HIP;
-    const int dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
-    vote_t v = {0};
-    dev_src_t q = {0};
-    knn_neighbour_t *d_out = NULL;
-    /* the labels and the vote's buffers in front of the span, then
-     * knn_index_query's call up to its copy back */
-    int rc = labels_sync(ix);
-    if (!rc) rc = vote_reserve(&v, mq, nclasses, dev_out, qlabels && matches, qlabels, NULL, pred, counts);
-    if (!rc) rc = query_search(ix, Q, mq, layout, src_dtype, k, flags, dev_out ? out : NULL, &q, &d_out);
-    rc = search_tail(ix, rc, d_out, d_out, NULL, mq, k);
-    rc = vote_finish(ix, rc, &v, d_out, NULL, mq, k, nclasses, vote_rule, dev_out, pred, counts, matches, out);
-    dev_src_free(&q);
-    return rc;
+    if (!out) return KNN_ERR_INVALID;
+    RCHK(rows_check(ix, ids, count, k, flags));
+    return rows_call(ix, ids, count, k, flags, NULL, out);
 }
 
 int knn_index_classify_rows(knn_index_t *ix, const int32_t *ids, size_t count, int k, int nclasses, int vote_rule,
@@ -1328,24 +1355,9 @@ int knn_index_classify_rows(knn_index_t *ix, const int32_t *ids, size_t count, i
 {
     RCHK(vote_check(ix, pred, nclasses, vote_rule));
     RCHK(rows_check(ix, ids, count, k, flags));
-    const int kz = (flags & KNN_QUERY_KEEP_ZERO) != 0, dev_out = (flags & KNN_INDEX_DEVICE_OUT) != 0;
-    const size_t mq = ids ? count : ix->m;
-    int32_t *pos = NULL;
-    RCHK(rows_plan(ix, ids, count, &pos));
-    vote_t v = {0};
-    rows_t r = {0};
-    int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
-    if (!rc) rc = labels_sync(ix);
-    if (!rc) rc = vote_reserve(&v, mq, nclasses, dev_out, matches != NULL, NULL, ids, pred, counts);
-    if (!rc) rc = rows_search(ix, pos, mq, k, kz, dev_out ? out : NULL, &r);
-    else free(pos);
-    rc = search_tail(ix, rc, r.d_out, r.d_rec, r.d_pos, mq, k);
-    /* a row's own label is the index's label of its id: the listed ids, or
-     * every live row's (the id map; none while nothing was removed: q + 1) */
-    const int32_t *d_own = ids ? v.own : ix->ids ? ix->d_ids : NULL;
-    rc = vote_finish(ix, rc, &v, r.d_out, d_own, mq, k, nclasses, vote_rule, dev_out, pred, counts, matches, out);
-    rows_free(&r);
-    return rc;
+    vote_t v = {.launch = knn_launch_vote_index, .nclasses = nclasses, .rule = vote_rule, .by_row = 1, .ids = ids,
+                .pred = pred, .counts = counts, .matches = matches};
+    return rows_call(ix, ids, count, k, flags, &v, out);
 }
 
 int knn_index_last_id(const knn_index_t *ix, size_t *last_id)
@@ -1362,18 +1374,7 @@ int knn_index_info(const knn_index_t *ix, size_t *m, size_t *n, int *nblocks, si
     if (n) *n = ix->n;
     if (nblocks) *nblocks = (int)ix->nblk;
     if (last_bits) *last_bits = ix->last_bits;
-    if (device_bytes) {
-        size_t b = ix->nblk * knn_block_bytes_dt(ix->cap, ix->n, ix->dtype) + META_BYTES;
-        if (ix->have_s8) b += ix->nblk * knn_s8_bytes(ix->cap, ix->n);
-        for (size_t t = 0; t < ix->ntile; t++) {
-            if (ix->tblk[t]) b += knn_block_bytes_dt(ix->tile_cap, ix->n, ix->dtype);
-            if (ix->ts8[t]) b += knn_s8_bytes(ix->tile_cap, ix->n);
-        }
-        b += ix->out_recs * sizeof(knn_neighbour_t);
-        if (ix->d_ids) b += ix->ids_cap * sizeof(int32_t);
-        b += ix->dlab_cap * sizeof(double);
-        *device_bytes = b + knn_ctx_device_bytes(ix->ctx);
-    }
+    if (device_bytes) *device_bytes = ix->dev_bytes + knn_ctx_device_bytes(ix->ctx);
     return KNN_OK;
 }
 
@@ -1418,11 +1419,10 @@ int knn_query(const double *X, size_t m, const double *Q, size_t mq, size_t n, i
         if (!rc) rc = run_pack(ix, q.src, &bt, layout, KNN_F64);
         if (!rc) rc = stream_wait();
         if (!rc) rc = build_finish(ix, x.src, layout, KNN_F64, ix->thm, ix->ntile);
-        if (!rc) rc = run_finish(ix, q.src, &bt, layout, KNN_F64, flags, ix->d_out);
+        if (!rc) rc = run_finish(ix, q.src, &bt, layout, KNN_F64, flags, (knn_neighbour_t *)ix->d_out.p);
         if (!rc) rc = span_end(ix);
     }
-    if (!rc && hipMemcpy(out, ix->d_out, cnt * sizeof(knn_neighbour_t), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = KNN_ERR_HIP;
+    if (!rc) rc = download(out, ix->d_out.p, cnt * sizeof(knn_neighbour_t));
     if (rc) hipStreamSynchronize(NULL);
     dev_src_free(&x);
     dev_src_free(&q);

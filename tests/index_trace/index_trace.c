@@ -43,7 +43,12 @@
  * end where the failed call's reblock stayed; and leave nothing live behind
  * knn_index_destroy.  A knn_index_update that failed behind its first
  * enqueued scatter is fit only for destroy: return value, frees and the
- * empty live set alone are checked.
+ * empty live set alone are checked.  A failed classify call must also leave
+ * its host outputs (pred, counts, the records, *matches; filled with a
+ * sentinel in front of the call) as they were, and every vote, the clean
+ * retry's included, must be handed the labels a model of the index's labels
+ * by id holds (run_step keeps it; every call brings other label values, so a
+ * stale range that was not uploaded shows).
  */
 #define TRACE_PROG "index_trace"
 /* (a knn_index_update that fails behind its first enqueued scatter) */
@@ -228,6 +233,34 @@ int knn_launch_drop_self(knn_neighbour_t *out, const knn_neighbour_t *in, const 
     return KNN_OK;
 }
 
+/* the labels by id as the calls so far have left them (run_step keeps it), and
+ * how often the vote saw another device copy than that */
+#define MAX_LABELS 4096
+static double g_model[MAX_LABELS];
+static int g_bad_labels;
+#define VOTE_MATCHES 7   /* what the vote leaves in the match counter */
+
+int knn_launch_vote_index(knn_neighbour_t *nb, size_t mq, int k, int nclasses, int rule, const double *labels,
+                          size_t nlabels, const double *qlab, const int32_t *own_ids, int *pred, int *counts,
+                          unsigned long long *matches, void *stream)
+{
+    FALLIBLE("knn_launch_vote_index", KNN_ERR_HIP);
+    L("knn_launch_vote_index %s %zu %d %d %d %s %zu %s %s %s %s %s %s", N(nb), mq, k, nclasses, rule, N(labels), nlabels,
+      N(qlab), N(own_ids), N(pred), N(counts), N(matches), N(stream));
+    need(nb, mq * (size_t)k * sizeof(*nb), "knn_launch_vote_index");
+    need(labels, nlabels * sizeof(double), "knn_launch_vote_index");
+    if (qlab) need(qlab, mq * sizeof(double), "knn_launch_vote_index");
+    if (own_ids) need(own_ids, mq * sizeof(int32_t), "knn_launch_vote_index");
+    need(pred, mq * sizeof(int), "knn_launch_vote_index");
+    if (counts) need(counts, mq * (size_t)nclasses * sizeof(int), "knn_launch_vote_index");
+    if (nlabels > MAX_LABELS || memcmp(labels, g_model, nlabels * sizeof(double))) g_bad_labels++;
+    if (matches) {
+        need(matches, sizeof(*matches), "knn_launch_vote_index");
+        *matches = VOTE_MATCHES;
+    }
+    return KNN_OK;
+}
+
 /* the context: one device buffer, and the form of its last begin */
 struct knn_ctx {
     void *buf;
@@ -365,8 +398,10 @@ int knn_ctx_rescan_end(knn_ctx_t *c, knn_neighbour_t *d_out, void *stream)
 #define OUT (KNN_INDEX_DEVICE_OUT)
 #define KZ (KNN_QUERY_KEEP_ZERO)
 
-enum { CREATE, QUERY, ADD, REMOVE, UPDATE, NEIGHBOURS, ONECALL, DESTROY };
-static const char *const op_name[] = {"create", "query", "add", "remove", "update", "neighbours", "knn_query", "destroy"};
+enum { CREATE, QUERY, ADD, REMOVE, UPDATE, NEIGHBOURS, CLASSIFY_ROWS, CLASSIFY, ONECALL, DESTROY };
+static const char *const op_name[] = {"create", "query", "add", "remove", "update", "neighbours", "classify_rows",
+                                      "classify", "knn_query", "destroy"};
+#define NCLS 10
 
 typedef struct {
     int op;
@@ -376,13 +411,17 @@ typedef struct {
     const char *tile;        /* KNN_QUERY_TILE */
     int id0, idstep;         /* the ids id0, id0 + idstep, ... */
     int may_reblock;         /* an add whose reblock may outlive its failure */
+    int nolab;               /* an update that leaves the labels as they are */
+    /* classify: the rule, and which of qlabels, matches, counts and out are given
+     * (nclasses: NCLS) */
+    int rule, qlab, matches, counts, out;
 } step_t;
 
 typedef struct {
     const char *name;
     const char *block;       /* KNN_QUERY_BLOCK */
     int f32, labels;
-    step_t s[8];             /* up to the destroy */
+    step_t s[12];            /* up to the destroy */
 } scn_t;
 
 static const scn_t g_scn[] = {
@@ -497,12 +536,91 @@ static const scn_t g_scn[] = {
       {.op = ONECALL, .rows = 100, .k = 5, .kind = INT8, .tile = "64", .unres = 2, .unres2 = 1},
       {.op = ONECALL, .rows = 100, .k = 5, .kind = REAL},
       {.op = DESTROY}}},
+    {"classify_host", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = CLASSIFY, .rows = 100, .k = 5, .kind = INT8, .qlab = 1, .matches = 1},   /* makes the labels' copy */
+      {.op = CLASSIFY, .rows = 100, .k = 5, .kind = INT8, .rule = KNN_VOTE_MPI, .qlab = 1, .matches = 1, .counts = 1,
+       .out = 1},                                                                    /* uploads nothing */
+      {.op = CLASSIFY, .rows = 100, .k = 5, .kind = REAL, .rule = KNN_VOTE_MAJORITY, .matches = 1},   /* counts none */
+      {.op = DESTROY}}},
+    {"classify_device", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = CLASSIFY, .rows = 100, .k = 5, .kind = INT8, .flags = SRC | OUT, .qlab = 1, .matches = 1, .counts = 1,
+       .out = 1},
+      {.op = CLASSIFY, .rows = 100, .k = 5, .kind = INT8, .flags = KZ, .qlab = 1, .matches = 1},
+      {.op = CLASSIFY, .rows = 100, .k = 5, .kind = INT8, .flags = OUT},   /* the records in the index's buffer */
+      {.op = DESTROY}}},
+    {"classify_two_tiles", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = CLASSIFY, .rows = 100, .k = 5, .kind = INT8, .tile = "64", .unres = 3, .unres2 = 1, .qlab = 1,
+       .matches = 1, .out = 1},   /* re-search and rescan ahead of the vote */
+      {.op = DESTROY}}},
+    {"classify_stale", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = ADD, .rows = 100, .kind = INT8},   /* room for 1200 labels */
+      {.op = CLASSIFY, .rows = 20, .k = 5, .kind = INT8, .qlab = 1, .matches = 1},
+      {.op = ADD, .rows = 50, .kind = INT8},    /* inside the device copy: a stale range */
+      {.op = CLASSIFY, .rows = 20, .k = 5, .kind = INT8, .qlab = 1, .matches = 1},
+      {.op = ADD, .rows = 20, .kind = INT8},
+      {.op = UPDATE, .rows = 1, .id0 = 3, .kind = INT8},   /* the range grows downwards ... */
+      {.op = ADD, .rows = 10, .kind = INT8},               /* ... and upwards */
+      {.op = CLASSIFY, .rows = 20, .k = 5, .kind = INT8, .qlab = 1, .matches = 1},
+      {.op = ADD, .rows = 500, .kind = INT8},   /* ids past the device copy: made again */
+      {.op = CLASSIFY, .rows = 20, .k = 5, .kind = INT8, .qlab = 1, .matches = 1},
+      {.op = DESTROY}}},
+    {"classify_update", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = CLASSIFY, .rows = 20, .k = 5, .kind = INT8, .counts = 1},
+      {.op = UPDATE, .rows = 3, .id0 = 10, .idstep = 290, .kind = INT8},
+      {.op = CLASSIFY, .rows = 20, .k = 5, .kind = INT8, .counts = 1},
+      {.op = UPDATE, .rows = 2, .id0 = 10, .idstep = 290, .kind = INT8, .nolab = 1},
+      {.op = CLASSIFY, .rows = 20, .k = 5, .kind = INT8, .counts = 1},   /* uploads nothing */
+      {.op = DESTROY}}},
+    {"classify_rows", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = CLASSIFY_ROWS, .rows = 3, .id0 = 1, .idstep = 299, .k = 5, .matches = 1},
+      {.op = CLASSIFY_ROWS, .rows = 0, .k = 5, .rule = KNN_VOTE_MPI, .matches = 1, .counts = 1, .out = 1},
+      {.op = CLASSIFY_ROWS, .rows = 3, .id0 = 1, .idstep = 299, .k = 5, .flags = KZ, .matches = 1, .out = 1},
+      {.op = CLASSIFY_ROWS, .rows = 0, .k = 5, .flags = KZ | OUT, .tile = "512", .unres = 2, .matches = 1, .counts = 1,
+       .out = 1},
+      {.op = CLASSIFY_ROWS, .rows = 3, .id0 = 1, .idstep = 299, .k = 5, .flags = OUT},
+      {.op = DESTROY}}},
+    {"classify_rows_real", "256", 1, 1,
+     {{.op = CREATE, .rows = 300, .kind = REAL},
+      {.op = CLASSIFY_ROWS, .rows = 0, .k = 5, .matches = 1, .out = 1},
+      {.op = CLASSIFY_ROWS, .rows = 2, .id0 = 2, .idstep = 270, .k = 5, .flags = KZ, .unres = 1, .matches = 1},
+      {.op = CLASSIFY, .rows = 20, .k = 5, .kind = REAL, .qlab = 1, .matches = 1},
+      {.op = DESTROY}}},
+    {"classify_after_remove", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = REMOVE, .rows = 1, .id0 = 7},
+      {.op = CLASSIFY_ROWS, .rows = 0, .k = 5, .matches = 1},   /* own labels through the id map */
+      {.op = CLASSIFY_ROWS, .rows = 3, .id0 = 1, .idstep = 299, .k = 5, .flags = KZ, .matches = 1},   /* the uploaded ids */
+      {.op = CLASSIFY, .rows = 20, .k = 5, .kind = INT8, .qlab = 1, .matches = 1},
+      {.op = DESTROY}}},
+    {"classify_drop_s8", "256", 0, 1,
+     {{.op = CREATE, .rows = 600, .kind = INT8},
+      {.op = ADD, .rows = 300, .kind = REAL},   /* drops the byte blocks */
+      {.op = CLASSIFY, .rows = 20, .k = 5, .kind = INT8, .qlab = 1, .matches = 1},
+      {.op = CLASSIFY_ROWS, .rows = 0, .k = 5, .matches = 1},
+      {.op = DESTROY}}},
 };
 #define NSCN ((int)(sizeof(g_scn) / sizeof(g_scn[0])))
 #define ONECALL_M 600   /* knn_query's corpus rows */
 
 static double g_X[MAX_ROWS * DIMS], g_lab[MAX_ROWS];
 static knn_neighbour_t g_out[MAX_RECS];
+static int g_pred[MAX_ROWS], g_counts[MAX_ROWS * NCLS];
+static int g_step_no;    /* calls into the index so far: every call brings other labels */
+static int g_touched;    /* a failed classify wrote one of its host outputs */
+#define SENTINEL 0x5a
+
+static int all_sentinel(const void *p, size_t bytes)
+{
+    for (size_t i = 0; i < bytes; i++)
+        if (((const unsigned char *)p)[i] != SENTINEL) return 0;
+    return 1;
+}
 
 static void *user_alloc(size_t bytes) { return live_new(bytes, 'U'); }
 
@@ -526,17 +644,38 @@ static int run_step(const scn_t *sc, knn_index_t **ix, const step_t *s)
     g_unres_research = s->unres2;
     if (s->tile) setenv("KNN_QUERY_TILE", s->tile, 1);
     else unsetenv("KNN_QUERY_TILE");
-    if (s->rows > MAX_ROWS || (s->op >= REMOVE && s->op <= NEIGHBOURS && s->rows > MAX_IDS)) DIE("step too large");
+    if (s->rows > MAX_ROWS || (s->op >= REMOVE && s->op <= CLASSIFY_ROWS && s->rows > MAX_IDS)) DIE("step too large");
     for (size_t i = 0; i < s->rows && i < MAX_IDS; i++) ids[i] = s->id0 + (int32_t)i * s->idstep;
+    const int cls = s->op == CLASSIFY || s->op == CLASSIFY_ROWS;
     L("# %s %zu k %d flags %d", op_name[s->op], s->rows, s->k, s->flags);
+    if (cls) L("# rule %d qlabels %d matches %d counts %d out %d", s->rule, s->qlab, s->matches, s->counts, s->out);
     size_t mq = s->rows;
-    if (s->op == NEIGHBOURS && !mq) knn_index_info(*ix, &mq, NULL, NULL, NULL, NULL);
-    if (mq * (size_t)(s->k ? s->k : 1) > MAX_RECS) DIE("step too large");
+    if ((s->op == NEIGHBOURS || s->op == CLASSIFY_ROWS) && !mq) knn_index_info(*ix, &mq, NULL, NULL, NULL, NULL);
+    if (mq * (size_t)(s->k ? s->k : 1) > MAX_RECS || (cls && mq > MAX_ROWS)) DIE("step too large");
+    /* other labels with every call, so that a stale device copy shows */
+    g_step_no++;
+    for (size_t i = 0; i < MAX_ROWS; i++) g_lab[i] = (double)((i + 3 * (size_t)g_step_no) % NCLS);
     const void *src = (dev & SRC) ? user_alloc(s->rows * DIMS * sizeof(double)) : (void *)g_X;
     knn_neighbour_t *out = (dev & OUT) ? (knn_neighbour_t *)user_alloc(mq * (size_t)s->k * sizeof(*out)) : g_out;
-    const double *lab = sc->labels ? g_lab : NULL;
-    size_t removed = 0;
+    const double *lab = sc->labels && !s->nolab ? g_lab : NULL;
+    size_t removed = 0, last = 0;
     int rc = KNN_OK;
+    if (*ix) knn_index_last_id(*ix, &last);
+    /* classify's outputs: the caller's device buffers under OUT, else host
+     * arrays that a failed call must leave as they are */
+    const size_t pred_b = mq * sizeof(int), counts_b = mq * NCLS * sizeof(int), out_b = mq * (size_t)s->k * sizeof(*out);
+    int *pred = g_pred, *counts = s->counts ? g_counts : NULL;
+    size_t hit = 0;
+    if (cls && (dev & OUT)) {
+        pred = (int *)user_alloc(pred_b);
+        if (s->counts) counts = (int *)user_alloc(counts_b);
+    } else if (cls) {
+        memset(g_pred, SENTINEL, pred_b);
+        memset(g_counts, SENTINEL, counts_b);
+        memset(g_out, SENTINEL, out_b);
+    }
+    memset(&hit, SENTINEL, sizeof(hit));
+    if (cls && !s->out) out = NULL;
     switch (s->op) {
     case CREATE: rc = knn_index_create(ix, src, s->rows, DIMS, lay, dt, lab, dt, flags); break;
     case QUERY: rc = knn_index_query(*ix, src, s->rows, lay, dt, s->k, flags, out); break;
@@ -547,15 +686,34 @@ static int run_step(const scn_t *sc, knn_index_t **ix, const step_t *s)
         break;
     case UPDATE: rc = knn_index_update(*ix, ids, s->rows, src, lay, dt, lab, flags); break;
     case NEIGHBOURS: rc = knn_index_neighbours(*ix, s->rows ? ids : NULL, s->rows, s->k, flags, out); break;
+    case CLASSIFY_ROWS:
+        rc = knn_index_classify_rows(*ix, s->rows ? ids : NULL, s->rows, s->k, NCLS, s->rule, flags, pred, counts,
+                                     s->matches ? &hit : NULL, out);
+        break;
+    case CLASSIFY:
+        rc = knn_index_classify(*ix, src, s->rows, lay, dt, s->k, NCLS, s->rule, flags, s->qlab ? g_lab : NULL, pred,
+                                counts, s->matches ? &hit : NULL, out);
+        break;
     case ONECALL: rc = knn_query(g_X, ONECALL_M, g_X, s->rows, DIMS, lay, lab, s->k, dt, flags, g_out); break;
     default:
         if (*ix) rc = knn_index_destroy(*ix);
         *ix = NULL;
     }
     user_free_all();
+    if (cls && rc) {
+        g_touched = !all_sentinel(&hit, sizeof(hit));
+        if (!(dev & OUT)) g_touched |= !all_sentinel(g_pred, pred_b) || !all_sentinel(g_counts, counts_b) || !all_sentinel(g_out, out_b);
+    }
+    if (cls && !rc && s->matches) L("# matches %zu", all_sentinel(&hit, sizeof(hit)) ? (size_t)-1 : hit);
+    /* the labels by id as the call left them */
+    if (!rc && lab && s->op == CREATE) memcpy(g_model, g_lab, s->rows * sizeof(double));
+    if (!rc && lab && s->op == ADD) memcpy(g_model + last, g_lab, s->rows * sizeof(double));
+    if (!rc && lab && s->op == UPDATE)
+        for (size_t i = 0; i < s->rows; i++) g_model[ids[i] - 1] = g_lab[i];
+    if (g_bad_labels && g_echo) DIE("%s: the vote saw labels that are not the index's", sc->name);
     if (rc) L("# -> %d", rc);
     else if (*ix) {
-        size_t m = 0, last = 0, bytes = 0;
+        size_t m = 0, bytes = 0;
         int nblk = 0, bits = 0;
         knn_index_info(*ix, &m, NULL, &nblk, &bytes, &bits);
         knn_index_last_id(*ix, &last);
@@ -622,6 +780,7 @@ static void sweep_step(const scn_t *sc, int step, long *faults)
         }
         lines_clear();
         g_calls = g_scattered = g_fault_behind_scatter = 0;
+        g_touched = g_bad_labels = 0;
         g_fail_at = n;
         int rc = run_step(sc, &ix, s);
         g_fail_at = 0;
@@ -635,6 +794,7 @@ static void sweep_step(const scn_t *sc, int step, long *faults)
         } else {
             ++*faults;
             if (!rc) violation(sc, step, n, "the call succeeded");
+            if (g_touched) violation(sc, step, n, "a failed classify wrote pred, matches, counts or out");
             const int ruined = s->op == UPDATE && g_fault_behind_scatter;
             if ((s->op == CREATE || s->op == ONECALL) && ix) violation(sc, step, n, "an index came out of a failed create");
             if (ix && !ruined) {
@@ -660,6 +820,7 @@ static void sweep_step(const scn_t *sc, int step, long *faults)
                 }
             }
         }
+        if (g_bad_labels) violation(sc, step, n, "the vote saw labels that are not the index's");
         if (ix) knn_index_destroy(ix);
         ix = NULL;
         lines_clear();
