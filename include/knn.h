@@ -109,6 +109,9 @@ enum knn_layout { KNN_COLMAJOR = 0, KNN_ROWMAJOR = 1 };
  * block, context or search has it as its dtype. */
 enum knn_dtype  { KNN_F64 = 0, KNN_F32 = 1, KNN_U8 = 2 };
 enum knn_vote   { KNN_VOTE_SERIAL = 0, KNN_VOTE_MPI = 1, KNN_VOTE_MAJORITY = 2 };
+/* what a neighbour counts in knn_classify_weighted / knn_regress and the
+ * knn_index_* calls on top of them: one ballot, or 1 / distance */
+enum knn_weights { KNN_WEIGHT_UNIFORM = 0, KNN_WEIGHT_DISTANCE = 1 };
 
 /* Largest k served: KNN_F64 32 (the reference fixes NN = 30, serial:8 /
  * blk:9); KNN_F32 128 (BASELINE configs[4]: k = 100). */
@@ -422,6 +425,25 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * NULL out excepted); KNN_ERR_UNSUPPORTED for nclasses > KNN_VOTE_MAX_CLASSES
  * and for k above the limit (k + 1 under KNN_QUERY_KEEP_ZERO, for rows).
  *
+ * knn_index_classify_weighted, knn_index_classify_weighted_rows,
+ * knn_index_regress, knn_index_regress_rows: the index as a predictor.  They
+ * are knn_index_classify / knn_index_classify_rows with another vote behind
+ * the same search -- paths, tiling, KNN_QUERY_TILE, the keep-zero rule and its
+ * k + 1 limit for rows, the id remap, the labels' device copy, the staging of
+ * host outputs, both device flags, knn_last_search_seconds() all as there --
+ * and that vote is knn_classify_weighted / knn_regress (below, where the
+ * semantics are written down) of the call's records with the index's labels by
+ * id, bit for bit.  weights: enum knn_weights.  Weighted classification: pred
+ * (mq ints), sums (nullable, mq x nclasses doubles: sums[q nclasses + j] the
+ * weight of class j + 1, the weighted counterpart of counts), *matches and
+ * qlabels as in knn_index_classify; the records' .label is filled.
+ * Regression reads the index's labels as real-valued targets: pred is mq
+ * doubles, and the records' .label stays as the search left it (0), on host-out
+ * calls too.  Under KNN_INDEX_DEVICE_OUT pred, sums and out are device
+ * pointers.  All four, before any device call: what the classify pair refuses
+ * (regression has no class checks), and KNN_ERR_INVALID for an unknown weights;
+ * an index made without labels is KNN_ERR_INVALID here too.
+ *
  * KNN_ERR_INVALID: NULL index, X, Q or out, zero m, mq or n, k <= 0, a bad
  * layout, unknown flag bits, m + mq > INT32_MAX; KNN_ERR_UNSUPPORTED: an
  * unknown src_dtype, dtype not KNN_F64 / KNN_F32, k above the dtype's limit
@@ -432,7 +454,7 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * ---------------------------------------------------------------------- */
 typedef struct knn_index knn_index_t;
 #define KNN_INDEX_DEVICE_SRC 2   /* X / Q is a device pointer on the index's device        */
-#define KNN_INDEX_DEVICE_OUT 4   /* out (classify: pred, counts too) is a device pointer    */
+#define KNN_INDEX_DEVICE_OUT 4   /* out (classify, regress: pred, counts / sums too) is a device pointer */
 KNN_API int knn_index_create(knn_index_t **index, const void *X, size_t m, size_t n, int layout,
                              int src_dtype, const double *labels, int dtype, int flags);
 KNN_API int knn_index_query(knn_index_t *index, const void *Q, size_t mq, int layout, int src_dtype,
@@ -453,6 +475,18 @@ KNN_API int knn_index_classify(knn_index_t *index, const void *Q, size_t mq, int
 KNN_API int knn_index_classify_rows(knn_index_t *index, const int32_t *ids /* nullable */, size_t count,
                                     int k, int nclasses, int vote_rule, int flags,
                                     int *pred, int *counts, size_t *matches, knn_neighbour_t *out);
+KNN_API int knn_index_classify_weighted(knn_index_t *index, const void *Q, size_t mq, int layout, int src_dtype,
+                                        int k, int nclasses, int weights, int flags,
+                                        const double *qlabels /* nullable, host, mq */,
+                                        int *pred, double *sums /* nullable, mq*nclasses */,
+                                        size_t *matches /* nullable */, knn_neighbour_t *out /* nullable, mq*k */);
+KNN_API int knn_index_classify_weighted_rows(knn_index_t *index, const int32_t *ids /* nullable */, size_t count,
+                                             int k, int nclasses, int weights, int flags,
+                                             int *pred, double *sums, size_t *matches, knn_neighbour_t *out);
+KNN_API int knn_index_regress(knn_index_t *index, const void *Q, size_t mq, int layout, int src_dtype,
+                              int k, int weights, int flags, double *pred, knn_neighbour_t *out /* nullable */);
+KNN_API int knn_index_regress_rows(knn_index_t *index, const int32_t *ids /* nullable */, size_t count,
+                                   int k, int weights, int flags, double *pred, knn_neighbour_t *out);
 KNN_API int knn_index_last_id(const knn_index_t *index, size_t *last_id);
 KNN_API int knn_index_info(const knn_index_t *index, size_t *m, size_t *n, int *nblocks,
                            size_t *device_bytes, int *last_bits);
@@ -482,6 +516,43 @@ KNN_API int knn_classify(const knn_neighbour_t *nb, size_t m, int k, int nclasse
 KNN_API int knn_classify_query(const knn_neighbour_t *nb, size_t mq, int k, int nclasses, int vote_rule,
                                const double *labels, size_t m, const double *qlabels,
                                int *pred, size_t *matches);
+
+/* ---------------------------------------------------------------------- *
+ * The records as a predictor (not in the reference): the distance-weighted
+ * vote and kNN regression, on the host.  nb: mq*k records as a search wrote
+ * them (ascending distance, then id) whose idx index labels / targets by id,
+ * as in knn_classify_query.  One definition, which the device vote of
+ * knn_index_classify_weighted / knn_index_regress repeats bit for bit:
+ *
+ *   valid    record i counts when 1 <= idx <= nlabels; empty slots
+ *            {INFINITY, 0, 0} and stray ids are skipped.
+ *   weights  KNN_WEIGHT_UNIFORM: w_i = 1.0.  KNN_WEIGHT_DISTANCE: w_i =
+ *            1.0 / distance_i, one correctly rounded fp64 division -- unless a
+ *            valid record of the query has distance exactly 0.0: then every
+ *            valid record at distance 0 gets w = 1.0 and every other one
+ *            w = 0.0 (an exact match decides; scikit-learn's rule).
+ *   classify lab_i = (int)labels[idx_i - 1] is counted when 1 <= lab_i <=
+ *            nclasses.  sums[q nclasses + j]: the fp64 sum of w_i over the
+ *            counted records of class j + 1, added in record order.  pred[q]:
+ *            the class with the largest sum if that is > 0, ties to the tied
+ *            class met first in record order (KNN_VOTE_MAJORITY's rule), 0
+ *            when nothing was counted.  *matches: the q with pred[q] ==
+ *            qlabels[q] (0 without qlabels).
+ *   regress  y_i = targets[idx_i - 1] of every valid record, any double.
+ *            pred[q] = (sum of w_i * y_i) / (sum of w_i): each product
+ *            rounded on its own (no fused multiply-add), both sums fp64 in
+ *            record order; NaN (the positive quiet one) without a valid record.
+ *
+ * pred, sums (mq x nclasses doubles) and matches of knn_classify_weighted
+ * are nullable.  KNN_ERR_INVALID: NULL nb, labels or targets, k <= 0,
+ * nclasses <= 0, an unknown weights, nlabels / ntargets == 0, a NULL pred of
+ * knn_regress.  No device call.
+ * ---------------------------------------------------------------------- */
+KNN_API int knn_classify_weighted(const knn_neighbour_t *nb, size_t mq, int k, int nclasses, int weights,
+                                  const double *labels, size_t nlabels, const double *qlabels /* nullable */,
+                                  int *pred, double *sums, size_t *matches);
+KNN_API int knn_regress(const knn_neighbour_t *nb, size_t mq, int k, int weights, const double *targets,
+                        size_t ntargets, double *pred);
 
 /* The same vote on the device, on the records knn_ctx_end / rescan_end
  * wrote (no host round trip).  d_nb: m*k records of queries with global ids

@@ -39,7 +39,10 @@
  * the first such call makes and add / update keep marked (labels_sync,
  * labels_stale), and the vote's scratch -- and the vote over the records on
  * the device behind it, its host outputs through a staging array so that a
- * failed call has written none of them.  The
+ * failed call has written none of them.  classify_weighted, regress and their
+ * _rows forms: the same two calls with the same vote_t, its launch the
+ * weighted vote or the regression (knn_predict.hip) and its outputs of 8-byte
+ * entries where those are doubles.  The
  * knn_block_* operations are in knn_blocks.c; what a failed call leaves behind
  * is swept on a CPU by tests/index_trace.
  */
@@ -636,41 +639,63 @@ static int labels_sync(knn_index_t *ix)
  * index's label of its id -- ids, or every live row's), and what it holds on
  * the device besides its records, in one scratch allocation: the match counter
  * (d_matches: NULL when the call counts none), the batch's own labels (d_qlab)
- * or the listed rows' ids, and pred and counts of a host-out call -- under
- * KNN_INDEX_DEVICE_OUT those two are the caller's.  launch: knn_launch_vote_index,
- * named by the classify entry points alone, so that a program which links
- * only the others needs no vote kernel. */
+ * or the listed rows' ids, and pred and tally of a host-out call -- under
+ * KNN_INDEX_DEVICE_OUT those two are the caller's.  An output (vote_out_t) is
+ * `per` entries of `es` bytes a query: pred one int, or one double for a
+ * regression; tally (to NULL: none) the nclasses ints of counts, or the
+ * nclasses doubles of sums.  launch: knn_launch_vote_index, named by the
+ * classify entry points alone, so that a program which links only the others
+ * needs no vote kernel; predict (launch NULL): knn_launch_predict, named by
+ * the classify_weighted and regress entry points alone, rule then an enum
+ * knn_weights and nclasses 0 for a regression. */
+typedef struct {
+    void *to;        /* the caller's array: host, or device under KNN_INDEX_DEVICE_OUT */
+    size_t es, per;
+    void *d;         /* where the vote writes */
+} vote_out_t;
+
 typedef struct {
     int (*launch)(knn_neighbour_t *, size_t, int, int, int, const double *, size_t, const double *, const int32_t *,
                   int *, int *, unsigned long long *, void *);
+    int (*predict)(knn_neighbour_t *, size_t, int, int, int, const double *, size_t, const double *, const int32_t *,
+                   void *, double *, unsigned long long *, void *);
     int nclasses, rule, by_row;
     const double *qlabels;
     const int32_t *ids;
-    int *pred, *counts;
+    vote_out_t pred, tally;
     size_t *matches;
     void *buf;
     unsigned long long *d_matches;
     double *d_qlab;
     const int32_t *d_own;   /* the rows' ids (by_row; NULL: q + 1, nothing was removed) */
-    int *d_pred, *d_counts;
 } vote_t;
+
+/* the bytes of an output of mq queries that the call holds or copies: none of
+ * one that is absent */
+static size_t vote_out_bytes(const vote_out_t *o, size_t mq) { return o->to ? mq * o->per * o->es : 0; }
 
 /* the labels and the vote's buffer, in front of the span */
 static int vote_begin(knn_index_t *ix, vote_t *v, size_t mq, int dev_out)
 {
     RCHK(labels_sync(ix));
-    /* 8-byte entries first, then the 4-byte ones */
-    const size_t nq = v->qlabels ? mq : 0, nown = v->ids ? mq : 0, npred = dev_out ? 0 : mq;
-    const size_t ncnt = !dev_out && v->counts ? mq * (size_t)v->nclasses : 0;
-    RCHK(scratch(&v->buf, sizeof(unsigned long long) + nq * sizeof(double) + (nown + npred + ncnt) * sizeof(int32_t)));
+    /* 8-byte entries first, then the 4-byte ones: an output is among the
+     * ones or the others by its entry size */
+    const size_t nq = v->qlabels ? mq : 0, nown = v->ids ? mq : 0;
+    const size_t pred_b = dev_out ? 0 : vote_out_bytes(&v->pred, mq);
+    const size_t tally_b = dev_out ? 0 : vote_out_bytes(&v->tally, mq);
+    const size_t p8 = v->pred.es == 8 ? pred_b : 0, t8 = v->tally.es == 8 ? tally_b : 0;
+    RCHK(scratch(&v->buf,
+                 sizeof(unsigned long long) + nq * sizeof(double) + nown * sizeof(int32_t) + pred_b + tally_b));
     unsigned long long *m8 = (unsigned long long *)v->buf;
     double *ql = (double *)(m8 + 1);
-    int32_t *i4 = (int32_t *)(ql + nq);
+    char *o8 = (char *)(ql + nq);
+    int32_t *i4 = (int32_t *)(o8 + p8 + t8);
+    char *o4 = (char *)(i4 + nown);
     v->d_matches = v->matches && (v->qlabels || v->by_row) ? m8 : NULL;
     v->d_qlab = v->qlabels ? ql : NULL;
     v->d_own = v->ids ? i4 : v->by_row && ix->ids ? (const int32_t *)ix->d_ids.p : NULL;
-    v->d_pred = dev_out ? v->pred : (int *)(i4 + nown);
-    v->d_counts = dev_out ? v->counts : v->counts ? (int *)(i4 + nown + npred) : NULL;
+    v->pred.d = dev_out ? v->pred.to : p8 ? (void *)o8 : (void *)o4;
+    v->tally.d = dev_out || !v->tally.to ? v->tally.to : t8 ? (void *)(o8 + p8) : (void *)(o4 + (pred_b - p8));
     if (v->qlabels) RCHK(upload(ql, v->qlabels, mq * sizeof(double)));
     if (v->ids) RCHK(upload(i4, v->ids, mq * sizeof(int32_t)));
     return KNN_OK;
@@ -694,19 +719,23 @@ static int finish_search(knn_index_t *ix, int rc, vote_t *v, knn_neighbour_t *ou
 {
     const int32_t *d_ids = ix->ids ? (const int32_t *)ix->d_ids.p : NULL;
     const size_t cnt = mq * (size_t)k, out_b = !dev_out && out ? cnt * sizeof(knn_neighbour_t) : 0;
-    const size_t pred_b = v && !dev_out ? mq * sizeof(int) : 0;
-    const size_t counts_b = pred_b && v->counts ? mq * (size_t)v->nclasses * sizeof(int) : 0;
+    const size_t pred_b = v && !dev_out ? vote_out_bytes(&v->pred, mq) : 0;
+    const size_t counts_b = pred_b ? vote_out_bytes(&v->tally, mq) : 0;
+    const double *d_labels = (const double *)ix->d_labels.p;
     unsigned long long hit = 0;
     char *stage = NULL;
     if (!rc && d_rec != d_out) rc = knn_launch_drop_self(d_out, d_rec, d_pos, mq, k, d_ids, ix->m, NULL);
     else if (!rc && d_ids) rc = knn_launch_remap_idx(d_out, cnt, d_ids, ix->m, NULL);
     if (!rc) rc = span_end(ix);
-    if (!rc && v)
-        rc = v->launch(d_out, mq, k, v->nclasses, v->rule, (const double *)ix->d_labels.p, ix->last_id, v->d_qlab,
-                       v->d_own, v->d_pred, v->d_counts, v->d_matches, NULL);
+    if (!rc && v && v->launch)
+        rc = v->launch(d_out, mq, k, v->nclasses, v->rule, d_labels, ix->last_id, v->d_qlab, v->d_own,
+                       (int *)v->pred.d, (int *)v->tally.d, v->d_matches, NULL);
+    else if (!rc && v)
+        rc = v->predict(d_out, mq, k, v->nclasses, v->rule, d_labels, ix->last_id, v->d_qlab, v->d_own, v->pred.d,
+                        (double *)v->tally.d, v->d_matches, NULL);
     if (!rc && pred_b && !(stage = (char *)malloc(pred_b + counts_b + out_b))) rc = KNN_ERR_NOMEM;
-    if (!rc && pred_b) rc = download(stage, v->d_pred, pred_b);
-    if (!rc && counts_b) rc = download(stage + pred_b, v->d_counts, counts_b);
+    if (!rc && pred_b) rc = download(stage, v->pred.d, pred_b);
+    if (!rc && counts_b) rc = download(stage + pred_b, v->tally.d, counts_b);
     if (!rc && out_b) rc = download(stage ? stage + pred_b + counts_b : (char *)out, d_out, out_b);
     if (!rc && v && v->d_matches) rc = download(&hit, v->d_matches, sizeof(hit));
     if (!rc && v) rc = stream_wait();
@@ -714,8 +743,8 @@ static int finish_search(knn_index_t *ix, int rc, vote_t *v, knn_neighbour_t *ou
         hipStreamSynchronize(NULL);
         free_query_state(ix);
     } else if (v) {
-        if (stage) memcpy(v->pred, stage, pred_b);
-        if (counts_b) memcpy(v->counts, stage + pred_b, counts_b);
+        if (stage) memcpy(v->pred.to, stage, pred_b);
+        if (counts_b) memcpy(v->tally.to, stage + pred_b, counts_b);
         if (stage && out_b) memcpy(out, stage + pred_b + counts_b, out_b);
         if (v->matches) *v->matches = (size_t)hit;
     } else if (out_b && ix->labels) {
@@ -832,7 +861,40 @@ int knn_index_classify(knn_index_t *ix, const void *Q, size_t mq, int layout, in
     RCHK(vote_check(ix, pred, nclasses, vote_rule));
     RCHK(query_check(ix, Q, mq, layout, src_dtype, k, flags));
     vote_t v = {.launch = knn_launch_vote_index, .nclasses = nclasses, .rule = vote_rule, .qlabels = qlabels,
-                .pred = pred, .counts = counts, .matches = matches};
+                .pred = {pred, sizeof(int), 1, NULL}, .tally = {counts, sizeof(int), (size_t)nclasses, NULL},
+                .matches = matches};
+    return query_call(ix, Q, mq, layout, src_dtype, k, flags, &v, out);
+}
+
+/* what the weighted vote and the regression refuse on top of their search's
+ * checks (nclasses 0: a regression, which has no class checks) */
+static int predict_check(const knn_index_t *ix, const void *pred, int nclasses, int weights, int regress)
+{
+    if (!ix || !pred || !ix->labels) return KNN_ERR_INVALID;
+    if (weights != KNN_WEIGHT_UNIFORM && weights != KNN_WEIGHT_DISTANCE) return KNN_ERR_INVALID;
+    if (regress) return KNN_OK;
+    if (nclasses <= 0) return KNN_ERR_INVALID;
+    return nclasses > KNN_VOTE_MAX_CLASSES ? KNN_ERR_UNSUPPORTED : KNN_OK;
+}
+
+int knn_index_classify_weighted(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k,
+                                int nclasses, int weights, int flags, const double *qlabels, int *pred, double *sums,
+                                size_t *matches, knn_neighbour_t *out)
+{
+    RCHK(predict_check(ix, pred, nclasses, weights, 0));
+    RCHK(query_check(ix, Q, mq, layout, src_dtype, k, flags));
+    vote_t v = {.predict = knn_launch_predict, .nclasses = nclasses, .rule = weights, .qlabels = qlabels,
+                .pred = {pred, sizeof(int), 1, NULL}, .tally = {sums, sizeof(double), (size_t)nclasses, NULL},
+                .matches = matches};
+    return query_call(ix, Q, mq, layout, src_dtype, k, flags, &v, out);
+}
+
+int knn_index_regress(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, int k, int weights,
+                      int flags, double *pred, knn_neighbour_t *out)
+{
+    RCHK(predict_check(ix, pred, 0, weights, 1));
+    RCHK(query_check(ix, Q, mq, layout, src_dtype, k, flags));
+    vote_t v = {.predict = knn_launch_predict, .rule = weights, .pred = {pred, sizeof(double), 1, NULL}};
     return query_call(ix, Q, mq, layout, src_dtype, k, flags, &v, out);
 }
 
@@ -1356,7 +1418,30 @@ int knn_index_classify_rows(knn_index_t *ix, const int32_t *ids, size_t count, i
     RCHK(vote_check(ix, pred, nclasses, vote_rule));
     RCHK(rows_check(ix, ids, count, k, flags));
     vote_t v = {.launch = knn_launch_vote_index, .nclasses = nclasses, .rule = vote_rule, .by_row = 1, .ids = ids,
-                .pred = pred, .counts = counts, .matches = matches};
+                .pred = {pred, sizeof(int), 1, NULL}, .tally = {counts, sizeof(int), (size_t)nclasses, NULL},
+                .matches = matches};
+    return rows_call(ix, ids, count, k, flags, &v, out);
+}
+
+int knn_index_classify_weighted_rows(knn_index_t *ix, const int32_t *ids, size_t count, int k, int nclasses,
+                                     int weights, int flags, int *pred, double *sums, size_t *matches,
+                                     knn_neighbour_t *out)
+{
+    RCHK(predict_check(ix, pred, nclasses, weights, 0));
+    RCHK(rows_check(ix, ids, count, k, flags));
+    vote_t v = {.predict = knn_launch_predict, .nclasses = nclasses, .rule = weights, .by_row = 1, .ids = ids,
+                .pred = {pred, sizeof(int), 1, NULL}, .tally = {sums, sizeof(double), (size_t)nclasses, NULL},
+                .matches = matches};
+    return rows_call(ix, ids, count, k, flags, &v, out);
+}
+
+/* (a regression compares nothing with a row's own target: no by_row, no ids) */
+int knn_index_regress_rows(knn_index_t *ix, const int32_t *ids, size_t count, int k, int weights, int flags,
+                           double *pred, knn_neighbour_t *out)
+{
+    RCHK(predict_check(ix, pred, 0, weights, 1));
+    RCHK(rows_check(ix, ids, count, k, flags));
+    vote_t v = {.predict = knn_launch_predict, .rule = weights, .pred = {pred, sizeof(double), 1, NULL}};
     return rows_call(ix, ids, count, k, flags, &v, out);
 }
 

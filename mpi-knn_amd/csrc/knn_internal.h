@@ -307,6 +307,17 @@ int knn_launch_vote(knn_neighbour_t *nb, size_t m, int k, int nclasses, int rule
 int knn_launch_vote_index(knn_neighbour_t *nb, size_t mq, int k, int nclasses, int rule, const double *labels,
                           size_t nlabels, const double *qlab, const int32_t *own_ids, int *pred, int *counts,
                           unsigned long long *matches, void *stream);
+/* knn_predict.hip: the weighted vote and the regression of the
+ * knn_index_classify_weighted / knn_index_regress calls (k_predict_classify,
+ * k_predict_regress; host twins knn_classify_weighted / knn_regress, bit for
+ * bit) over the same records, with k_vote_index's arguments.  weights: enum
+ * knn_weights.  nclasses > 0: pred is mq ints, sums (nullable) mq x nclasses
+ * doubles, .label is filled.  nclasses == 0: regression -- pred is mq doubles,
+ * labels are the targets, sums, qlab, own_ids and matches are not read and
+ * .label stays */
+int knn_launch_predict(knn_neighbour_t *nb, size_t mq, int k, int nclasses, int weights, const double *labels,
+                       size_t nlabels, const double *qlab, const int32_t *own_ids, void *pred, double *sums,
+                       unsigned long long *matches, void *stream);
 /* knn_pack.hip: block elements <-> int16 wire elements (cnt % 8 == 0) */
 int knn_launch_wire(int unpack, void *dst, const void *src, int dtype, size_t cnt, void *stream);
 /* knn_engine.c: the value knn_last_search_seconds() returns (this thread) */

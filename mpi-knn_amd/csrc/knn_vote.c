@@ -13,6 +13,7 @@
 #include "knn_internal.h"
 
 #include <hip/hip_runtime_api.h>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -92,4 +93,98 @@ int knn_classify_device(knn_neighbour_t *d_nb, size_t m, int k, int nclasses, in
     if (nclasses > KNN_VOTE_MAX_CLASSES) return KNN_ERR_UNSUPPORTED;
     return knn_launch_vote(d_nb, m, k, nclasses, vote_rule, d_labels, nlabels, q_base, d_pred,
                            d_matches, stream);
+}
+
+/* ---- the records as a predictor: knn_classify_weighted, knn_regress --------
+ * include/knn.h has the definition; k_predict_classify / k_predict_regress
+ * (knn_predict.hip) give these results bit for bit.  Every product and sum
+ * below is a statement of its own, and the compiler may not fuse them. */
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#elif defined(__GNUC__)
+#pragma GCC optimize("fp-contract=off")
+#endif
+
+static int weights_ok(int weights) { return weights == KNN_WEIGHT_UNIFORM || weights == KNN_WEIGHT_DISTANCE; }
+
+static int rec_valid(const knn_neighbour_t *r, size_t n) { return r->idx >= 1 && (size_t)r->idx <= n; }
+
+/* a query's zero rule: a valid record at distance exactly 0 */
+static int any_zero(const knn_neighbour_t *L, int k, size_t n)
+{
+    for (int i = 0; i < k; i++)
+        if (rec_valid(L + i, n) && L[i].distance == 0.0) return 1;
+    return 0;
+}
+
+static double rec_weight(double d, int weights, int zero)
+{
+    if (weights != KNN_WEIGHT_DISTANCE) return 1.0;
+    if (zero) return d == 0.0 ? 1.0 : 0.0;
+    const double w = 1.0 / d;
+    return w;
+}
+
+int knn_classify_weighted(const knn_neighbour_t *nb, size_t mq, int k, int nclasses, int weights,
+                          const double *labels, size_t nlabels, const double *qlabels, int *pred, double *sums,
+                          size_t *matches)
+{
+    if (!nb || !labels || k <= 0 || nclasses <= 0 || nlabels == 0 || !weights_ok(weights)) return KNN_ERR_INVALID;
+    double *own = sums ? NULL : (double *)malloc((size_t)nclasses * sizeof(double));
+    if (!sums && !own) return KNN_ERR_NOMEM;
+    size_t hit = 0;
+    for (size_t q = 0; q < mq; q++) {
+        const knn_neighbour_t *L = nb + q * (size_t)k;
+        double *s = sums ? sums + q * (size_t)nclasses : own;
+        const int zero = weights == KNN_WEIGHT_DISTANCE && any_zero(L, k, nlabels);
+        for (int j = 0; j < nclasses; j++) s[j] = 0.0;
+        for (int i = 0; i < k; i++) {
+            if (!rec_valid(L + i, nlabels)) continue;
+            const int lab = (int)labels[L[i].idx - 1];
+            if (lab < 1 || lab > nclasses) continue;
+            const double w = rec_weight(L[i].distance, weights, zero);
+            const double t = s[lab - 1] + w;
+            s[lab - 1] = t;
+        }
+        double best = 0.0;
+        for (int j = 0; j < nclasses; j++)
+            if (s[j] > best) best = s[j];
+        int most = 0;
+        for (int i = 0; i < k && best > 0.0; i++) {
+            if (!rec_valid(L + i, nlabels)) continue;
+            const int lab = (int)labels[L[i].idx - 1];
+            if (lab >= 1 && lab <= nclasses && s[lab - 1] == best) {
+                most = lab;
+                break;
+            }
+        }
+        if (pred) pred[q] = most;
+        if (qlabels && most == qlabels[q]) hit++;
+    }
+    free(own);
+    if (matches) *matches = hit;
+    return KNN_OK;
+}
+
+int knn_regress(const knn_neighbour_t *nb, size_t mq, int k, int weights, const double *targets, size_t ntargets,
+                double *pred)
+{
+    if (!nb || !targets || !pred || k <= 0 || ntargets == 0 || !weights_ok(weights)) return KNN_ERR_INVALID;
+    for (size_t q = 0; q < mq; q++) {
+        const knn_neighbour_t *L = nb + q * (size_t)k;
+        const int zero = weights == KNN_WEIGHT_DISTANCE && any_zero(L, k, ntargets);
+        double num = 0.0, den = 0.0;
+        int seen = 0;
+        for (int i = 0; i < k; i++) {
+            if (!rec_valid(L + i, ntargets)) continue;
+            const double w = rec_weight(L[i].distance, weights, zero);
+            const double p = w * targets[L[i].idx - 1];
+            num = num + p;
+            den = den + w;
+            seen = 1;
+        }
+        const double r = num / den;
+        pred[q] = seen ? r : (double)NAN;
+    }
+    return KNN_OK;
 }

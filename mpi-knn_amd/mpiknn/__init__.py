@@ -30,6 +30,7 @@ OK, ERR_INVALID, ERR_NOMEM, ERR_HIP, ERR_IO, ERR_FORMAT, ERR_UNSUPPORTED, ERR_NO
 COLMAJOR, ROWMAJOR = 0, 1
 F64, F32, U8 = 0, 1, 2
 VOTE_SERIAL, VOTE_MPI, VOTE_MAJORITY = 0, 1, 2
+WEIGHT_UNIFORM, WEIGHT_DISTANCE = 0, 1   # enum knn_weights
 MAX_K = 32          # KNN_MAX_K (fp64)
 MAX_K_F32 = 128     # KNN_MAX_K_F32
 META_DOUBLES = 8
@@ -57,6 +58,8 @@ API_SYMBOLS = (
     "knn_index_update", "knn_block_scatter_dt", "knn_block_scatter_s8",
     "knn_index_neighbours", "knn_block_gather_pos_dt", "knn_block_gather_pos_s8",
     "knn_index_classify", "knn_index_classify_rows",
+    "knn_classify_weighted", "knn_regress", "knn_index_classify_weighted", "knn_index_classify_weighted_rows",
+    "knn_index_regress", "knn_index_regress_rows",
 )
 DTYPES = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 # a pack / index SOURCE may also be unsigned bytes (KNN_U8: never a block or search dtype)
@@ -166,6 +169,12 @@ def _load():
         "knn_index_neighbours": ([p, p, sz, i, i, p], i),
         "knn_index_classify": ([p, p, sz, i, i, i, i, i, i, p, p, p, psz, p], i),
         "knn_index_classify_rows": ([p, p, sz, i, i, i, i, p, p, psz, p], i),
+        "knn_classify_weighted": ([p, sz, i, i, i, p, sz, p, p, p, psz], i),
+        "knn_regress": ([p, sz, i, i, p, sz, p], i),
+        "knn_index_classify_weighted": ([p, p, sz, i, i, i, i, i, i, p, p, p, psz, p], i),
+        "knn_index_classify_weighted_rows": ([p, p, sz, i, i, i, i, p, p, psz, p], i),
+        "knn_index_regress": ([p, p, sz, i, i, i, i, i, p, p], i),
+        "knn_index_regress_rows": ([p, p, sz, i, i, i, p, p], i),
         "knn_block_gather_pos_dt": ([p, sz, sz, p, sz, sz, p, sz, sz, i, p], i),
         "knn_block_gather_pos_s8": ([p, sz, sz, p, sz, sz, p, sz, sz, p], i),
     }
@@ -312,6 +321,37 @@ def classify(nb, labels, nclasses=10, rule=VOTE_SERIAL):
     rc = lib.knn_classify(_ptr(nb), m, k, nclasses, rule, _ptr(lab), _ptr(pred), ctypes.byref(matches))
     _check(rc, "knn_classify")
     return pred, matches.value
+
+
+def classify_weighted(nb, labels, qlabels=None, nclasses=10, weights=WEIGHT_DISTANCE):
+    """knn_classify_weighted: the weighted vote of query()'s records over the
+    labels by id -- WEIGHT_DISTANCE: a neighbour at distance d counts 1/d, and
+    an exact match decides; WEIGHT_UNIFORM: one ballot each (include/knn.h).
+    Returns (pred int32 (mq,), sums float64 (mq, nclasses), matches)."""
+    nb = np.ascontiguousarray(nb)
+    mq, k = nb.shape
+    lab = np.ascontiguousarray(labels, dtype=np.float64)
+    ql = None if qlabels is None else np.ascontiguousarray(qlabels, dtype=np.float64)
+    pred = np.zeros(mq, dtype=np.int32)
+    sums = np.zeros((mq, max(nclasses, 0)), dtype=np.float64)
+    matches = ctypes.c_size_t()
+    rc = lib.knn_classify_weighted(_ptr(nb), mq, k, nclasses, weights, _ptr(lab), lab.shape[0], _ptr(ql),
+                                   _ptr(pred), _ptr(sums), ctypes.byref(matches))
+    _check(rc, "knn_classify_weighted")
+    return pred, sums, matches.value
+
+
+def regress(nb, targets, weights=WEIGHT_UNIFORM):
+    """knn_regress: the uniform or distance-weighted mean of the neighbours'
+    targets (by id; include/knn.h), NaN for a query without a neighbour.
+    Returns pred float64 (mq,)."""
+    nb = np.ascontiguousarray(nb)
+    mq, k = nb.shape
+    tg = np.ascontiguousarray(targets, dtype=np.float64)
+    pred = np.zeros(mq, dtype=np.float64)
+    rc = lib.knn_regress(_ptr(nb), mq, k, weights, _ptr(tg), tg.shape[0], _ptr(pred))
+    _check(rc, "knn_regress")
+    return pred
 
 
 # ------------------------------------------------------ device-resident API
@@ -474,6 +514,8 @@ INDEX_DEVICE_SRC = 2  # KNN_INDEX_DEVICE_SRC
 INDEX_DEVICE_OUT = 4  # KNN_INDEX_DEVICE_OUT
 IndexInfo = collections.namedtuple("IndexInfo", "m n nblocks device_bytes last_bits")
 ClassifyResult = collections.namedtuple("ClassifyResult", "pred matches counts neighbours seconds")
+WeightedResult = collections.namedtuple("WeightedResult", "pred matches sums neighbours seconds")
+RegressResult = collections.namedtuple("RegressResult", "pred neighbours seconds")
 _NP_SRC = {np.dtype(np.uint8): U8, np.dtype(np.float32): F32, np.dtype(np.float64): F64}
 
 
@@ -757,6 +799,115 @@ class Index:
         _check(lib.knn_index_classify_rows(self._h, _ptr(a), rows if a is not None else 0, k, nclasses, rule, flags,
                                            pp, cp, ctypes.byref(hit), op), "knn_index_classify_rows")
         return ClassifyResult(pred, hit.value, cnt, nb, lib.knn_last_search_seconds())
+
+    # -- the index as a predictor: distance-weighted vote, regression
+
+    def _predict_outputs(self, rows, k, pred_dtype, nsums, neighbours, out, flags):
+        """_vote_outputs for the weighted vote and the regression: pred of
+        pred_dtype, float64 sums ((rows, nsums); nsums None: no sums)"""
+        if out is not None:
+            import torch
+            if not _is_device_tensor(out) or not out.is_contiguous() or \
+                    out.numel() * out.element_size() < rows * k * NB_DTYPE.itemsize:
+                raise ValueError("out must be a contiguous torch GPU buffer of >= %d bytes" %
+                                 (rows * k * NB_DTYPE.itemsize))
+            _on_index_device(out, "out")
+            pred = torch.empty(rows, dtype={np.int32: torch.int32, np.float64: torch.float64}[pred_dtype],
+                               device=out.device)
+            sums = None if nsums is None else torch.empty((rows, nsums), dtype=torch.float64, device=out.device)
+            ptrs = [ctypes.c_void_p(t.data_ptr()) if t is not None else None for t in (pred, sums, out)]
+            return pred, sums, out, ptrs, flags | INDEX_DEVICE_OUT
+        pred = np.zeros(rows, dtype=pred_dtype)
+        sums = None if nsums is None else np.zeros((rows, nsums), dtype=np.float64)
+        nb = np.zeros((rows, max(k, 0)), dtype=NB_DTYPE) if neighbours else None
+        return pred, sums, nb, [_ptr(pred), _ptr(sums), _ptr(nb)], flags
+
+    def _query_source(self, Q, keep_zero):
+        if not self._h:
+            raise ValueError("the index is closed")
+        ptr, keep, mq, n, lay, src, flags = _index_source(Q, self.layout, "Q")
+        if n != self.n:
+            raise ValueError("Q must be (mq, %d), got (%d, %d)" % (self.n, mq, n))
+        return ptr, keep, mq, lay, src, flags | (QUERY_KEEP_ZERO if keep_zero else 0)
+
+    def _id_list(self, ids, what):
+        """(int32 array or None, rows) of a rows call's ids argument"""
+        if not self._h:
+            raise ValueError("the index is closed")
+        if ids is None:
+            return None, self.m
+        a = np.asarray(ids).reshape(-1)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError("ids must be integers, got %s" % a.dtype)
+        if a.size == 0 or a.min() < -2 ** 31 or a.max() >= 2 ** 31:   # (an empty list is not ids=None)
+            raise KnnError(ERR_INVALID, what)
+        return np.ascontiguousarray(a, dtype=np.int32), a.size
+
+    def classify_weighted(self, Q, k=30, keep_zero=True, qlabels=None, nclasses=10, weights=WEIGHT_DISTANCE,
+                          sums=False, out=None, neighbours=False):
+        """knn_index_classify_weighted: classify's call with the weighted vote
+        behind the search -- WEIGHT_DISTANCE: a neighbour at distance d counts
+        1/d and an exact match (distance 0 under keep_zero) decides;
+        WEIGHT_UNIFORM: one ballot each, ties to the class met first.  Returns
+        WeightedResult(pred, matches, sums, neighbours, seconds), classify's
+        result with sums (sums=True: the (mq, nclasses) float64 class weights,
+        bit for bit what the module's classify_weighted gives for query's
+        records) in place of counts.  out as in classify: pred and sums are
+        then torch tensors on that device."""
+        ptr, keep, mq, lay, src, flags = self._query_source(Q, keep_zero)
+        ql = None if qlabels is None else np.ascontiguousarray(qlabels, dtype=np.float64)
+        if ql is not None and ql.shape != (mq,):
+            raise ValueError("qlabels must have %d entries, got %r" % (mq, ql.shape))
+        pred, sm, nb, (pp, sp, op), flags = self._predict_outputs(mq, k, np.int32, max(nclasses, 0) if sums else None,
+                                                                  neighbours, out, flags)
+        hit = ctypes.c_size_t()
+        _check(lib.knn_index_classify_weighted(self._h, ptr, mq, lay, src, k, nclasses, weights, flags, _ptr(ql),
+                                               pp, sp, ctypes.byref(hit), op), "knn_index_classify_weighted")
+        del keep
+        return WeightedResult(pred, hit.value, sm, nb, lib.knn_last_search_seconds())
+
+    def classify_weighted_rows(self, ids=None, k=30, keep_zero=True, nclasses=10, weights=WEIGHT_DISTANCE, sums=False,
+                               out=None, neighbours=False):
+        """knn_index_classify_weighted_rows: classify_rows' call (ids, the
+        keep-zero rule and its k + 1 limit as there) with the weighted vote;
+        the WeightedResult as in classify_weighted, matches counting the rows
+        predicted as their own label."""
+        a, rows = self._id_list(ids, "knn_index_classify_weighted_rows")
+        pred, sm, nb, (pp, sp, op), flags = self._predict_outputs(rows, k, np.int32,
+                                                                  max(nclasses, 0) if sums else None, neighbours, out,
+                                                                  QUERY_KEEP_ZERO if keep_zero else 0)
+        hit = ctypes.c_size_t()
+        _check(lib.knn_index_classify_weighted_rows(self._h, _ptr(a), rows if a is not None else 0, k, nclasses,
+                                                    weights, flags, pp, sp, ctypes.byref(hit), op),
+               "knn_index_classify_weighted_rows")
+        return WeightedResult(pred, hit.value, sm, nb, lib.knn_last_search_seconds())
+
+    def regress(self, Q, k=30, keep_zero=True, weights=WEIGHT_UNIFORM, out=None, neighbours=False):
+        """knn_index_regress: query's search for the rows of Q, then the mean of
+        each one's neighbours' targets -- the index's labels, read as real
+        values -- uniform or weighted by 1/distance (an exact match decides),
+        on the device.  Returns RegressResult(pred, neighbours, seconds): pred
+        mq float64 values (NaN for a query without a neighbour), bit for bit
+        what the module's regress gives for query's records; neighbours
+        (neighbours=True, or out as in classify: pred is then a torch float64
+        tensor there) the records, their .label left 0."""
+        ptr, keep, mq, lay, src, flags = self._query_source(Q, keep_zero)
+        pred, _, nb, (pp, _, op), flags = self._predict_outputs(mq, k, np.float64, None, neighbours, out, flags)
+        _check(lib.knn_index_regress(self._h, ptr, mq, lay, src, k, weights, flags, pp, op), "knn_index_regress")
+        del keep
+        return RegressResult(pred, nb, lib.knn_last_search_seconds())
+
+    def regress_rows(self, ids=None, k=30, keep_zero=True, weights=WEIGHT_UNIFORM, out=None, neighbours=False):
+        """knn_index_regress_rows: neighbours' search for the listed ids
+        (ids=None: every live row), then regress' mean over the OTHER rows'
+        targets: the leave-one-out prediction of each row.  The RegressResult
+        as in regress."""
+        a, rows = self._id_list(ids, "knn_index_regress_rows")
+        pred, _, nb, (pp, _, op), flags = self._predict_outputs(rows, k, np.float64, None, neighbours, out,
+                                                                QUERY_KEEP_ZERO if keep_zero else 0)
+        _check(lib.knn_index_regress_rows(self._h, _ptr(a), rows if a is not None else 0, k, weights, flags, pp, op),
+               "knn_index_regress_rows")
+        return RegressResult(pred, nb, lib.knn_last_search_seconds())
 
     @property
     def last_id(self):
