@@ -444,6 +444,56 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * (regression has no class checks), and KNN_ERR_INVALID for an unknown weights;
  * an index made without labels is KNN_ERR_INVALID here too.
  *
+ * knn_index_radius_count, knn_index_radius, knn_index_radius_rows_count,
+ * knn_index_radius_rows: radius search -- which live rows lie within distance
+ * r of a point, and how many (scikit-learn's radius_neighbors, FAISS's
+ * range_search); there is no k and no k limit.  For a query row q and radius
+ * r a hit is a live corpus row x with sqrt(S) <= r, S = sum_j (q_j - x_j)^2
+ * accumulated in j order in fp64 without FMA: knn_search's arithmetic, over
+ * the fp32-rounded values on an index of dtype KNN_F32 as in knn_index_query.
+ * The comparison is made on the reported distance, so no returned distance
+ * exceeds r; NaN and infinite distances are no hits.  r: a finite double >= 0.
+ * The zero rule is knn_index_query's: flags 0 -- a zero distance is no hit
+ * (the reference's rule); KNN_QUERY_KEEP_ZERO -- a hit at distance 0.0.  The
+ * _rows forms follow knn_index_neighbours: flags 0 drops the row itself and
+ * its exact duplicates; KNN_QUERY_KEEP_ZERO leaves out only the row itself, by
+ * position, and duplicates are hits at 0.0.  A query's hits come ordered by
+ * (distance, id), lower id first on ties; idx is the row's id (the stable id
+ * after removals, as in knn_index_query); .label is filled from the index's
+ * labels on host-out calls and is 0 on device-out calls or without labels.
+ *
+ * Output is CSR, caller-owned, in two calls, so that nothing is sized by
+ * guess: the _count call is the first distance pass and writes counts[q], the
+ * number of hits of query q (mq int32), and nothing else.  The caller makes
+ * indptr (mq + 1 int64), the exclusive prefix sum of those counts from any
+ * offset indptr[0] >= 0, non-decreasing, and the fill call -- the second
+ * distance pass and a per-query sort -- writes query q's hits to the records
+ * indptr[q] - indptr[0] .. indptr[q + 1] - indptr[0] - 1 of out, which holds
+ * indptr[mq] - indptr[0] records; it never writes outside a query's segment.
+ * If any query's number of hits differs from its segment's length (the index
+ * was changed between the two calls, or the arguments were) the fill call
+ * returns KNN_ERR_INVALID and out's content is unspecified.  A segment of
+ * length 0 is legal, and mq queries without a single hit are KNN_OK.
+ * KNN_INDEX_DEVICE_SRC (query forms) as in knn_index_query;
+ * KNN_INDEX_DEVICE_OUT makes counts, indptr and out device pointers on the
+ * index's device, and nothing is copied back.  ids, ids == NULL (every live
+ * row in ascending id), repeats and dead ids as in knn_index_neighbours;
+ * KNN_QUERY_TILE and the 2^18 tile limit as in knn_index_query.  How: the
+ * queries are packed (or gathered by position) into tile buffers the radius
+ * calls keep for themselves -- no context is made, and the one
+ * knn_index_query keeps is not touched -- and searched by distance kernels of
+ * their own (knn_radius.hip): on the byte path (the index has byte blocks and
+ * the batch's reduced meta passes knn_s8_spec_ok) an int8 MFMA kernel whose
+ * exact integer d^2 is compared with the one integer T that has sqrt(T) <= r <
+ * sqrt(T + 1); otherwise an exact scan in the reference's arithmetic.
+ * knn_last_search_seconds() reports the call's device span, pack or gather
+ * through the last kernel.  A failed call leaves the index answering as
+ * before.  KNN_ERR_INVALID, before any device call: a NULL index, Q, counts,
+ * indptr or out, mq == 0, a bad layout, unknown flag bits, a radius that is
+ * negative, NaN or infinite, a host indptr that decreases or starts below 0,
+ * m + mq > INT32_MAX, and the id errors of knn_index_neighbours;
+ * KNN_ERR_UNSUPPORTED: an unknown src_dtype.
+ *
  * KNN_ERR_INVALID: NULL index, X, Q or out, zero m, mq or n, k <= 0, a bad
  * layout, unknown flag bits, m + mq > INT32_MAX; KNN_ERR_UNSUPPORTED: an
  * unknown src_dtype, dtype not KNN_F64 / KNN_F32, k above the dtype's limit
@@ -487,13 +537,22 @@ KNN_API int knn_index_regress(knn_index_t *index, const void *Q, size_t mq, int 
                               int k, int weights, int flags, double *pred, knn_neighbour_t *out /* nullable */);
 KNN_API int knn_index_regress_rows(knn_index_t *index, const int32_t *ids /* nullable */, size_t count,
                                    int k, int weights, int flags, double *pred, knn_neighbour_t *out);
+KNN_API int knn_index_radius_count(knn_index_t *index, const void *Q, size_t mq, int layout, int src_dtype,
+                                   double radius, int flags, int32_t *counts /* mq */);
+KNN_API int knn_index_radius(knn_index_t *index, const void *Q, size_t mq, int layout, int src_dtype,
+                             double radius, int flags, const int64_t *indptr /* mq + 1 */,
+                             knn_neighbour_t *out /* indptr[mq] - indptr[0] records */);
+KNN_API int knn_index_radius_rows_count(knn_index_t *index, const int32_t *ids /* nullable */, size_t count,
+                                        double radius, int flags, int32_t *counts);
+KNN_API int knn_index_radius_rows(knn_index_t *index, const int32_t *ids /* nullable */, size_t count,
+                                  double radius, int flags, const int64_t *indptr, knn_neighbour_t *out);
 KNN_API int knn_index_last_id(const knn_index_t *index, size_t *last_id);
 KNN_API int knn_index_info(const knn_index_t *index, size_t *m, size_t *n, int *nblocks,
                            size_t *device_bytes, int *last_bits);
 KNN_API int knn_index_destroy(knn_index_t *index);
 
 /* Search wall time of the last knn_search() / knn_query() / knn_index_query() / knn_index_neighbours() /
- * knn_index_classify() / knn_index_classify_rows() on this thread, seconds: the
+ * knn_index_classify() / knn_index_classify_rows() / knn_index_radius*() on this thread, seconds: the
  * span the reference times (serial:70-98, blk:120-250) -- device compute
  * only, excluding load, H2D, D2H and vote. */
 KNN_API double knn_last_search_seconds(void);

@@ -42,7 +42,10 @@
  * failed call has written none of them.  classify_weighted, regress and their
  * _rows forms: the same two calls with the same vote_t, its launch the
  * weighted vote or the regression (knn_predict.hip) and its outputs of 8-byte
- * entries where those are doubles.  The
+ * entries where those are doubles.  radius_count,
+ * radius and their _rows forms: distance kernels of their own with CSR output
+ * (knn_radius.hip) behind query's packs / neighbours' gathers into tile
+ * buffers of their own, no context (radius_run).  The
  * knn_block_* operations are in knn_blocks.c; what a failed call leaves behind
  * is swept on a CPU by tests/index_trace.
  */
@@ -51,6 +54,7 @@
 #include "knn_remove_plan.h"
 #include "knn_update_plan.h"
 #include "knn_neighbours_plan.h"
+#include "knn_radius_plan.h"
 
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
@@ -114,6 +118,13 @@ struct knn_index {
     double *red;                      /* ... and its pinned host copy */
     hipEvent_t e0, e1;
     int last_bits;
+    /* the radius calls' own (no context goes with them, and the kept one
+     * stays as it is): rt_n tile buffers of capacity rt_cap, and d_rad: the
+     * offsets, the counters or cursors and the mismatch flag of a call */
+    size_t rt_cap, rt_n;
+    void **rtblk, **rts8;
+    double *rthm;
+    knn_buf_t d_rad;
 };
 
 /* a batch of mq queries: ntile tiles of tcap rows */
@@ -349,6 +360,11 @@ static void index_free(knn_index_t *ix)
     knn_buf_release(&ix->dev_bytes, &ix->d_meta);
     knn_buf_release(&ix->dev_bytes, &ix->d_ids);
     knn_buf_release(&ix->dev_bytes, &ix->d_labels);
+    if (ix->rt_n) images_release(ix, ix->rtblk, ix->rts8, ix->rt_cap, 0, ix->rt_n);
+    if (ix->d_rad.p) knn_buf_release(&ix->dev_bytes, &ix->d_rad);
+    free(ix->rtblk);
+    free(ix->rts8);
+    free(ix->rthm);
     free(ix->ids);
     if (ix->red) hipHostFree(ix->red);
     if (ix->e0) hipEventDestroy(ix->e0);
@@ -1267,7 +1283,8 @@ int knn_index_update(knn_index_t *ix, const int32_t *ids, size_t count, const vo
 
 /* ----------------------------------------------------------- neighbours */
 
-/* The query tiles of knn_index_neighbours: tile t's rows are the resident
+/* The query tiles of knn_index_neighbours (tblk, ts8 of capacity tile_cap: the
+ * index's query tiles, or the radius calls' own): tile t's rows are the resident
  * rows at positions d_pos[t tcap ..], copied out of the blocks (d_tab: the
  * element blocks' pointers, then the byte blocks' when s8).  Device to device
  * on the NULL stream, no wait, nothing read back.
@@ -1286,21 +1303,22 @@ int knn_index_update(knn_index_t *ix, const int32_t *ids, size_t count, const vo
  * zeros a pack leaves there: no kernel then computes on stale or never
  * written memory, whatever it does with the result.  The byte tile needs
  * nothing. */
-static int gather_tiles(knn_index_t *ix, const void *const *d_tab, const int32_t *d_pos, const batch_t *bt, int s8)
+static int gather_tiles(knn_index_t *ix, void *const *tblk, void *const *ts8, size_t tile_cap,
+                        const void *const *d_tab, const int32_t *d_pos, const batch_t *bt, int s8)
 {
     const size_t n = ix->n, es = knn_esize(ix->dtype), np = knn_n_pad_dt(n, ix->dtype);
-    const size_t trp = knn_rows_pad(ix->tile_cap);
+    const size_t trp = knn_rows_pad(tile_cap);
     for (size_t t = 0; t < bt->ntile; t++) {
         const size_t r0 = t * bt->tcap, rows = bt->mq - r0 < bt->tcap ? bt->mq - r0 : bt->tcap;
         const size_t pad = knn_round_up(rows, KNN_TQ) - rows;   /* (round_up(rows, KNN_TQ) <= trp) */
-        char *blk = (char *)ix->tblk[t];
-        RCHK(knn_block_gather_pos_dt(blk, ix->tile_cap, 0, d_tab, ix->cap, ix->nblk, d_pos + r0, rows, n, ix->dtype,
+        char *blk = (char *)tblk[t];
+        RCHK(knn_block_gather_pos_dt(blk, tile_cap, 0, d_tab, ix->cap, ix->nblk, d_pos + r0, rows, n, ix->dtype,
                                      NULL));
         if (pad && (hipMemsetAsync(blk + rows * np * es, 0, pad * np * es, NULL) != hipSuccess ||
                     hipMemsetAsync(blk + (trp * np + rows) * es, 0, pad * es, NULL) != hipSuccess))
             return KNN_ERR_HIP;
         if (s8)
-            RCHK(knn_block_gather_pos_s8(ix->ts8[t], ix->tile_cap, 0, d_tab + ix->nblk, ix->cap, ix->nblk, d_pos + r0,
+            RCHK(knn_block_gather_pos_s8(ts8[t], tile_cap, 0, d_tab + ix->nblk, ix->cap, ix->nblk, d_pos + r0,
                                          rows, n, NULL));
     }
     return KNN_OK;
@@ -1380,7 +1398,8 @@ static int rows_search(knn_index_t *ix, int32_t *pos, size_t mq, int k, int kz, 
          * rows and cmeta only grows.  No tile meta is read back, so the host
          * does not wait between the gathers and the searches. */
         rc = put_meta(ix, NULL, 0);
-        if (!rc) rc = gather_tiles(ix, (const void *const *)r->d_tab, r->d_pos, &bt, use_s8);
+        if (!rc)
+            rc = gather_tiles(ix, ix->tblk, ix->ts8, ix->tile_cap, (const void *const *)r->d_tab, r->d_pos, &bt, use_s8);
         knn_ctx_set_keep_zero(ix->ctx, kz);
         if (!rc) rc = search_tiles(ix, &bt, use_s8, r->d_rec);
     }
@@ -1443,6 +1462,242 @@ int knn_index_regress_rows(knn_index_t *ix, const int32_t *ids, size_t count, in
     RCHK(rows_check(ix, ids, count, k, flags));
     vote_t v = {.predict = knn_launch_predict, .rule = weights, .pred = {pred, sizeof(double), 1, NULL}};
     return rows_call(ix, ids, count, k, flags, &v, out);
+}
+
+/* --------------------------------------------------------------- radius */
+
+/* Radius search (knn_radius.hip): which live rows lie within `radius` of each
+ * query, in two calls that share everything but their last steps -- count
+ * (the first distance pass: counts) and fill (the second, its hits into the
+ * caller's CSR segments, then the segments' sort).  No context is involved
+ * and the kept one is not touched: the calls have tile buffers of their own
+ * (rtblk, rts8: filled by pack_rows / gather_tiles as query's and neighbours'
+ * are) and one buffer d_rad for the offsets, the counters and the flag.  The
+ * launchers are named by radius_run alone, which only the four radius entry
+ * points reach. */
+typedef struct {
+    double radius;
+    int flags, fill;
+    int32_t *counts;         /* count: mq entries (device under KNN_INDEX_DEVICE_OUT) */
+    const int64_t *indptr;   /* fill: mq + 1 offsets */
+    knn_neighbour_t *out;    /* fill: indptr[mq] - indptr[0] records */
+} radius_t;
+
+/* what all four refuse that is not about their queries: the outputs, the
+ * radius (a NaN fails both comparisons), a host indptr that decreases */
+static int radius_check(const radius_t *a, size_t mq)
+{
+    if (a->fill ? !a->indptr || !a->out : !a->counts) return KNN_ERR_INVALID;
+    if (!(a->radius >= 0.0) || !(a->radius <= 1.7976931348623157e308)) return KNN_ERR_INVALID;
+    if (a->fill && !(a->flags & KNN_INDEX_DEVICE_OUT)) {
+        if (a->indptr[0] < 0) return KNN_ERR_INVALID;
+        for (size_t q = 0; q < mq; q++)
+            if (a->indptr[q + 1] < a->indptr[q]) return KNN_ERR_INVALID;
+    }
+    return KNN_OK;
+}
+
+/* the calls' tile buffers for the batch: capacity doubling from
+ * KNN_INDEX_TILE_MIN as index_reserve's; the byte forms when s8 */
+static int radius_reserve(knn_index_t *ix, const batch_t *bt, int s8)
+{
+    if (bt->tcap > ix->rt_cap) {
+        if (ix->rt_n) images_release(ix, ix->rtblk, ix->rts8, ix->rt_cap, 0, ix->rt_n);
+        size_t cap = ix->rt_cap ? ix->rt_cap : KNN_INDEX_TILE_MIN;
+        while (cap < bt->tcap) cap *= 2;
+        ix->rt_cap = cap;
+    }
+    if (bt->ntile > ix->rt_n) {
+        void **a = (void **)calloc(bt->ntile, sizeof(void *)), **b = (void **)calloc(bt->ntile, sizeof(void *));
+        double *hm = (double *)calloc(bt->ntile * KNN_META_DOUBLES, sizeof(double));
+        if (!a || !b || !hm) {
+            free(a);
+            free(b);
+            free(hm);
+            return KNN_ERR_NOMEM;
+        }
+        if (ix->rt_n) {
+            memcpy(a, ix->rtblk, ix->rt_n * sizeof(void *));
+            memcpy(b, ix->rts8, ix->rt_n * sizeof(void *));
+        }
+        free(ix->rtblk);
+        free(ix->rts8);
+        free(ix->rthm);
+        ix->rtblk = a;
+        ix->rts8 = b;
+        ix->rthm = hm;
+        ix->rt_n = bt->ntile;
+    }
+    for (size_t t = 0; t < bt->ntile; t++) {
+        RCHK(image_alloc(ix, &ix->rtblk[t], ix->rt_cap, 0));
+        if (s8) RCHK(image_alloc(ix, &ix->rts8[t], ix->rt_cap, 1));
+    }
+    return KNN_OK;
+}
+
+/* one pass (count or fill) of every tile against every block, KNN_RADIUS_MAXBLK
+ * blocks a launch: d_cnt the counters / cursors, d_ip the offsets, d_self the
+ * rows' own positions (rows forms), all by query */
+static int radius_pass(const knn_index_t *ix, const batch_t *bt, int use_s8, const radius_t *a, int thr,
+                       const int32_t *d_self, int32_t *d_cnt, const int64_t *d_ip, knn_neighbour_t *d_rec)
+{
+    const int keep0 = (a->flags & KNN_QUERY_KEEP_ZERO) != 0;
+    for (size_t t = 0; t < bt->ntile; t++) {
+        const size_t r0 = t * bt->tcap, rows = bt->mq - r0 < bt->tcap ? bt->mq - r0 : bt->tcap;
+        for (size_t b0 = 0; b0 < ix->nblk; b0 += KNN_RADIUS_MAXBLK) {
+            knn_radius_blocks_t cb;
+            memset(&cb, 0, sizeof(cb));
+            cb.nblk = (int)(ix->nblk - b0 < KNN_RADIUS_MAXBLK ? ix->nblk - b0 : KNN_RADIUS_MAXBLK);
+            for (int j = 0; j < cb.nblk; j++) {
+                cb.ptr[j] = use_s8 ? ix->b.s8[b0 + j] : ix->b.blk[b0 + j];
+                cb.base[j] = (int64_t)ix->b.cbase[b0 + j];
+                cb.nc[j] = (int)ix->b.cnc[b0 + j];
+            }
+            if (use_s8)
+                RCHK(knn_launch_radius_i8(a->fill, ix->rts8[t], knn_rows_pad(ix->rt_cap), (int)rows,
+                                          d_self ? d_self + r0 : NULL, &cb, knn_rows_pad(ix->cap), (int)ix->n, thr,
+                                          keep0, d_cnt + r0, d_ip ? d_ip + r0 : NULL, d_ip, d_rec, NULL));
+            else
+                RCHK(knn_launch_radius_scan(a->fill, ix->dtype, ix->rtblk[t], (int)rows, d_self ? d_self + r0 : NULL,
+                                            &cb, (int)ix->n, a->radius, keep0, d_cnt + r0, d_ip ? d_ip + r0 : NULL,
+                                            d_ip, d_rec, NULL));
+        }
+    }
+    return KNN_OK;
+}
+
+/* A radius call behind its checks.  Q: the query forms' source; pos: the rows
+ * forms' positions (mq of them, freed here).  Every allocation and upload in
+ * front of the span; the span from the pack or gather through the last kernel;
+ * then the answers to the host (none under KNN_INDEX_DEVICE_OUT, the fill's
+ * flag excepted: the call's status depends on it). */
+static int radius_run(knn_index_t *ix, const void *Q, int32_t *pos, size_t mq, int layout, int src_dtype,
+                      const radius_t *a)
+{
+    const int dev_out = (a->flags & KNN_INDEX_DEVICE_OUT) != 0;
+    const batch_t bt = tile_shape(ix, mq);
+    const size_t ip_b = (mq + 1) * sizeof(int64_t), cnt_b = mq * sizeof(int32_t);
+    const size_t nrec = a->fill && !dev_out ? (size_t)(a->indptr[mq] - a->indptr[0]) : 0;
+    dev_src_t q = {0};
+    int32_t *d_pos = NULL;
+    void **d_tab = NULL;
+    int use_s8 = pos ? s8_stays(ix, ix->cmeta) : 0, flag = 0;
+    int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+    if (!rc) rc = own_grow(ix, &ix->d_rad, ip_b + cnt_b + sizeof(int32_t));
+    if (!rc && nrec) rc = index_out(ix, nrec);
+    /* d_rad: the offsets of a host-out fill, the call's counters or cursors,
+     * the flag; under KNN_INDEX_DEVICE_OUT counts and offsets are the caller's */
+    int32_t *d_own = ix->d_rad.p ? (int32_t *)((char *)ix->d_rad.p + ip_b) : NULL;
+    int32_t *d_cnt = !a->fill && dev_out ? a->counts : d_own;
+    int *d_flag = d_own ? (int *)(d_own + mq) : NULL;
+    const int64_t *d_ip = !a->fill ? NULL : dev_out ? a->indptr : (const int64_t *)ix->d_rad.p;
+    knn_neighbour_t *d_rec = dev_out ? a->out : (knn_neighbour_t *)ix->d_out.p;
+    if (!rc && pos) {
+        rc = scratch((void **)&d_pos, mq * sizeof(int32_t));
+        if (!rc) rc = scratch((void **)&d_tab, 2 * ix->nblk * sizeof(void *));
+        if (!rc) rc = upload(d_pos, pos, mq * sizeof(int32_t));
+        if (!rc) rc = upload(d_tab, ix->b.blk, ix->nblk * sizeof(void *));
+        if (!rc) rc = upload(d_tab + ix->nblk, ix->b.s8, ix->nblk * sizeof(void *));
+    } else if (!rc) {
+        rc = dev_src(&q, Q, mq * ix->n * knn_src_esize(src_dtype), a->flags);
+    }
+    free(pos);
+    if (!rc) rc = radius_reserve(ix, &bt, use_s8);
+    if (!rc && a->fill && !dev_out) rc = upload(ix->d_rad.p, a->indptr, ip_b);
+    if (!rc) {
+        hipEventRecord(ix->e0, NULL);
+        if (hipMemsetAsync(d_cnt, 0, cnt_b, NULL) != hipSuccess ||
+            (a->fill && hipMemsetAsync(d_flag, 0, sizeof(int), NULL) != hipSuccess))
+            rc = KNN_ERR_HIP;
+        if (!rc && d_pos) {
+            /* the queries are corpus rows: the batch's meta is the corpus's */
+            rc = gather_tiles(ix, ix->rtblk, ix->rts8, ix->rt_cap, (const void *const *)d_tab, d_pos, &bt, use_s8);
+        } else if (!rc) {
+            /* query's two parts: the element tiles and their meta, one wait,
+             * the path the reduced meta allows, the byte tiles for it */
+            rc = pack_rows(ix, ix->rtblk, bt.ntile, ix->rt_cap, bt.tcap, q.src, mq, layout, src_dtype, 0, ix->rthm);
+            if (!rc) rc = stream_wait();
+            if (!rc) {
+                double red[KNN_META_DOUBLES];
+                memcpy(red, ix->cmeta, META_BYTES);
+                meta_max(red, ix->rthm, bt.ntile);
+                use_s8 = ix->have_s8 && knn_s8_spec_ok(red, ix->n, ix->dtype);
+            }
+            if (!rc && use_s8) rc = radius_reserve(ix, &bt, 1);
+            if (!rc && use_s8)
+                rc = pack_rows(ix, ix->rts8, bt.ntile, ix->rt_cap, bt.tcap, q.src, mq, layout, src_dtype, 1, NULL);
+        }
+        const int thr = use_s8 ? (int)knn_radius_threshold(a->radius, knn_radius_d2max(ix->n)) : 0;
+        if (!rc) rc = radius_pass(ix, &bt, use_s8, a, thr, d_pos, d_cnt, d_ip, d_rec);
+        if (!rc && a->fill)
+            rc = knn_launch_radius_sort(mq, d_cnt, d_ip, d_rec, ix->ids ? (const int32_t *)ix->d_ids.p : NULL, d_flag,
+                                        NULL);
+        if (!rc) rc = span_end(ix);
+    }
+    if (!rc && !a->fill && !dev_out) rc = download(a->counts, d_cnt, cnt_b);
+    if (!rc && a->fill) rc = download(&flag, d_flag, sizeof(flag));
+    if (!rc && flag) rc = KNN_ERR_INVALID;   /* a segment is not its query's number of hits */
+    if (!rc && nrec) rc = download(a->out, d_rec, nrec * sizeof(knn_neighbour_t));
+    if (rc) hipStreamSynchronize(NULL);
+    else if (nrec && ix->labels) fill_labels(a->out, nrec, ix->labels);
+    dev_src_free(&q);
+    scratch_free(d_pos);
+    scratch_free(d_tab);
+    return rc;
+}
+
+/* the query forms: knn_index_query's checks without a k */
+static int radius_query(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, const radius_t *a)
+{
+    if (!ix || !Q || mq == 0) return KNN_ERR_INVALID;
+    if (!knn_src_esize(src_dtype)) return KNN_ERR_UNSUPPORTED;
+    if (!layout_ok(layout)) return KNN_ERR_INVALID;
+    if (a->flags & ~(KNN_QUERY_KEEP_ZERO | KNN_INDEX_DEVICE_SRC | KNN_INDEX_DEVICE_OUT)) return KNN_ERR_INVALID;
+    if (mq > 0x7fffffffULL || ix->m + mq > 0x7fffffffULL) return KNN_ERR_INVALID;
+    RCHK(radius_check(a, mq));
+    return radius_run(ix, Q, NULL, mq, layout, src_dtype, a);
+}
+
+/* the rows forms: knn_index_neighbours' checks without a k, and its plan */
+static int radius_rows(knn_index_t *ix, const int32_t *ids, size_t count, const radius_t *a)
+{
+    if (!ix || (ids ? count == 0 : count != 0)) return KNN_ERR_INVALID;
+    if (a->flags & ~(KNN_QUERY_KEEP_ZERO | KNN_INDEX_DEVICE_OUT)) return KNN_ERR_INVALID;
+    const size_t mq = ids ? count : ix->m;
+    if (mq > 0x7fffffffULL || ix->m + mq > 0x7fffffffULL) return KNN_ERR_INVALID;
+    if (!ids_ok(ix, ids, count)) return KNN_ERR_INVALID;
+    RCHK(radius_check(a, mq));
+    int32_t *pos = NULL;
+    RCHK(rows_plan(ix, ids, count, &pos));
+    return radius_run(ix, NULL, pos, mq, 0, 0, a);
+}
+
+int knn_index_radius_count(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, double radius,
+                           int flags, int32_t *counts)
+{
+    const radius_t a = {.radius = radius, .flags = flags, .counts = counts};
+    return radius_query(ix, Q, mq, layout, src_dtype, &a);
+}
+
+int knn_index_radius(knn_index_t *ix, const void *Q, size_t mq, int layout, int src_dtype, double radius, int flags,
+                     const int64_t *indptr, knn_neighbour_t *out)
+{
+    const radius_t a = {.radius = radius, .flags = flags, .fill = 1, .indptr = indptr, .out = out};
+    return radius_query(ix, Q, mq, layout, src_dtype, &a);
+}
+
+int knn_index_radius_rows_count(knn_index_t *ix, const int32_t *ids, size_t count, double radius, int flags,
+                                int32_t *counts)
+{
+    const radius_t a = {.radius = radius, .flags = flags, .counts = counts};
+    return radius_rows(ix, ids, count, &a);
+}
+
+int knn_index_radius_rows(knn_index_t *ix, const int32_t *ids, size_t count, double radius, int flags,
+                          const int64_t *indptr, knn_neighbour_t *out)
+{
+    const radius_t a = {.radius = radius, .flags = flags, .fill = 1, .indptr = indptr, .out = out};
+    return radius_rows(ix, ids, count, &a);
 }
 
 int knn_index_last_id(const knn_index_t *ix, size_t *last_id)

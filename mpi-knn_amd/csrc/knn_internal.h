@@ -318,6 +318,41 @@ int knn_launch_vote_index(knn_neighbour_t *nb, size_t mq, int k, int nclasses, i
 int knn_launch_predict(knn_neighbour_t *nb, size_t mq, int k, int nclasses, int weights, const double *labels,
                        size_t nlabels, const double *qlab, const int32_t *own_ids, void *pred, double *sums,
                        unsigned long long *matches, void *stream);
+/* knn_radius.hip: radius search over the resident index (knn_index_radius*).
+ * The corpus blocks of one launch: block b holds the rows at global positions
+ * base[b] .. base[b] + nc[b] - 1 (byte blocks for knn_launch_radius_i8,
+ * element blocks for knn_launch_radius_scan). */
+#define KNN_RADIUS_MAXBLK 8
+/* segments of at most this many records are sorted in LDS (16 bytes each),
+ * longer ones in place in global memory */
+#define KNN_RADIUS_SORT_LDS 2048
+typedef struct {
+    const void *ptr[KNN_RADIUS_MAXBLK];
+    int64_t base[KNN_RADIUS_MAXBLK];
+    int nc[KNN_RADIUS_MAXBLK];
+    int nblk;
+} knn_radius_blocks_t;
+/* nq queries of a tile (their rows 0 .. nq-1 of the byte tile qs8 / the
+ * element tile qblk) against the table's blocks.  fill == 0: counts[q] +=
+ * query q's hits (the caller zeroes counts).  fill != 0: counts is the
+ * queries' cursor (zeroed by the caller; it ends at the number of hits), and
+ * hit number s of query q, s < indptr[q + 1] - indptr[q], becomes the record
+ * {distance, position, 0} at out[indptr[q] - indptr0[0] + s].  counts, indptr
+ * and self_pos (nullable: the position a query leaves out, its own) are the
+ * tile's: entry 0 is its first query's.  keep0: a zero distance is a hit.
+ * Byte path: T the integer threshold on d^2 (knn_radius_plan.h). */
+int knn_launch_radius_i8(int fill, const void *qs8, size_t q_rows_pad, int nq, const int32_t *self_pos,
+                         const knn_radius_blocks_t *cb, size_t c_rows_pad, int n, int T, int keep0, int32_t *counts,
+                         const int64_t *indptr, const int64_t *indptr0, knn_neighbour_t *out, void *stream);
+int knn_launch_radius_scan(int fill, int dtype, const void *qblk, int nq, const int32_t *self_pos,
+                           const knn_radius_blocks_t *cb, int n, double radius, int keep0, int32_t *counts,
+                           const int64_t *indptr, const int64_t *indptr0, knn_neighbour_t *out, void *stream);
+/* every query's segment out[indptr[q] - indptr[0] ..) sorted by (distance,
+ * position), idx then position -> id (ids[position]; NULL: position + 1);
+ * *flag |= 1 where cursor[q] is not the segment's length (that segment is left
+ * as it is) */
+int knn_launch_radius_sort(size_t mq, const int32_t *cursor, const int64_t *indptr, knn_neighbour_t *out,
+                           const int32_t *ids, int *flag, void *stream);
 /* knn_pack.hip: block elements <-> int16 wire elements (cnt % 8 == 0) */
 int knn_launch_wire(int unpack, void *dst, const void *src, int dtype, size_t cnt, void *stream);
 /* knn_engine.c: the value knn_last_search_seconds() returns (this thread) */

@@ -60,6 +60,7 @@ API_SYMBOLS = (
     "knn_index_classify", "knn_index_classify_rows",
     "knn_classify_weighted", "knn_regress", "knn_index_classify_weighted", "knn_index_classify_weighted_rows",
     "knn_index_regress", "knn_index_regress_rows",
+    "knn_index_radius_count", "knn_index_radius", "knn_index_radius_rows_count", "knn_index_radius_rows",
 )
 DTYPES = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 # a pack / index SOURCE may also be unsigned bytes (KNN_U8: never a block or search dtype)
@@ -175,6 +176,10 @@ def _load():
         "knn_index_classify_weighted_rows": ([p, p, sz, i, i, i, i, p, p, psz, p], i),
         "knn_index_regress": ([p, p, sz, i, i, i, i, i, p, p], i),
         "knn_index_regress_rows": ([p, p, sz, i, i, i, p, p], i),
+        "knn_index_radius_count": ([p, p, sz, i, i, d, i, p], i),
+        "knn_index_radius": ([p, p, sz, i, i, d, i, p, p], i),
+        "knn_index_radius_rows_count": ([p, p, sz, d, i, p], i),
+        "knn_index_radius_rows": ([p, p, sz, d, i, p, p], i),
         "knn_block_gather_pos_dt": ([p, sz, sz, p, sz, sz, p, sz, sz, i, p], i),
         "knn_block_gather_pos_s8": ([p, sz, sz, p, sz, sz, p, sz, sz, p], i),
     }
@@ -908,6 +913,126 @@ class Index:
         _check(lib.knn_index_regress_rows(self._h, _ptr(a), rows if a is not None else 0, k, weights, flags, pp, op),
                "knn_index_regress_rows")
         return RegressResult(pred, nb, lib.knn_last_search_seconds())
+
+    def _radius_count(self, call, rows, flags, out):
+        """the count pass: counts as an int32 array, or into / as a torch GPU
+        int32 tensor (out: the tensor, or True to make one)"""
+        if out is not None and out is not False:
+            import torch
+            if out is True:
+                out = torch.empty(rows, dtype=torch.int32, device="cuda:0")
+            if not _is_device_tensor(out) or not out.is_contiguous() or out.dtype != torch.int32 or \
+                    out.numel() < rows:
+                raise ValueError("out must be a contiguous torch GPU int32 tensor of >= %d entries" % rows)
+            _on_index_device(out, "out")
+            call(flags | INDEX_DEVICE_OUT, ctypes.c_void_p(out.data_ptr()))
+            return out
+        counts = np.zeros(rows, dtype=np.int32)
+        call(flags, _ptr(counts))
+        return counts
+
+    def _radius_fill(self, count_call, fill_call, rows, flags, indptr, out, device):
+        """count (unless indptr is given), the offsets, fill; on the device
+        when device is set or indptr / out are torch GPU tensors"""
+        t0 = 0.0
+        if device or _is_device_tensor(indptr) or _is_device_tensor(out):
+            import torch
+            if indptr is None:
+                counts = self._radius_count(count_call, rows, flags, True)
+                t0 = lib.knn_last_search_seconds()
+                indptr = torch.zeros(rows + 1, dtype=torch.int64, device=counts.device)
+                indptr[1:] = torch.cumsum(counts[:rows], 0, dtype=torch.int64)
+            if not _is_device_tensor(indptr) or not indptr.is_contiguous() or indptr.dtype != torch.int64 or \
+                    indptr.numel() != rows + 1:
+                raise ValueError("indptr must be a contiguous torch GPU int64 tensor of %d entries" % (rows + 1))
+            total = int(indptr[-1] - indptr[0])
+            if out is None:
+                out = torch.zeros(max(total, 1) * NB_DTYPE.itemsize, dtype=torch.uint8, device=indptr.device)
+            if not _is_device_tensor(out) or not out.is_contiguous() or \
+                    out.numel() * out.element_size() < total * NB_DTYPE.itemsize:
+                raise ValueError("out must be a contiguous torch GPU buffer of >= %d bytes" %
+                                 (total * NB_DTYPE.itemsize))
+            _on_index_device(indptr, "indptr")
+            _on_index_device(out, "out")
+            fill_call(flags | INDEX_DEVICE_OUT, ctypes.c_void_p(indptr.data_ptr()), ctypes.c_void_p(out.data_ptr()))
+            self.radius_seconds = (t0, lib.knn_last_search_seconds())
+            return indptr, out
+        if indptr is None:
+            counts = self._radius_count(count_call, rows, flags, None)
+            t0 = lib.knn_last_search_seconds()
+            indptr = np.zeros(rows + 1, dtype=np.int64)
+            np.cumsum(counts, out=indptr[1:])
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        if indptr.shape != (rows + 1,):
+            raise ValueError("indptr must have %d entries, got %r" % (rows + 1, indptr.shape))
+        # (one record more than asked for: a zero-size array has no address to pass)
+        rec = np.zeros(max(int(indptr[-1] - indptr[0]), 0) + 1, dtype=NB_DTYPE)
+        fill_call(flags, _ptr(indptr), _ptr(rec))
+        self.radius_seconds = (t0, lib.knn_last_search_seconds())
+        return indptr, rec[:-1]
+
+    def radius_count(self, Q, radius, keep_zero=True, out=None):
+        """knn_index_radius_count: for every row of Q (handled as in query) the
+        number of live rows within `radius` (sqrt(S) <= radius; a zero distance
+        counts only under keep_zero).  Returns an int32 array; out: a torch GPU
+        int32 tensor (or True) receives the counts on the device and is
+        returned."""
+        ptr, keep, mq, lay, src, flags = self._query_source(Q, keep_zero)
+
+        def call(fl, cp):
+            _check(lib.knn_index_radius_count(self._h, ptr, mq, lay, src, radius, fl, cp), "knn_index_radius_count")
+        res = self._radius_count(call, mq, flags, out)
+        del keep
+        return res
+
+    def radius(self, Q, radius, keep_zero=True, indptr=None, out=None, device=False):
+        """knn_index_radius_count, the offsets by cumulative sum, and
+        knn_index_radius: every row of Q's hits within `radius`, ordered by
+        (distance, id).  Returns (indptr, records): query q's hits are
+        records[indptr[q] - indptr[0]:indptr[q + 1] - indptr[0]], indptr int64
+        of mq + 1 entries, records of NB_DTYPE.  indptr given: the count is
+        skipped (the offsets of an earlier radius_count of the same call;
+        KnnError(ERR_INVALID) if a segment is not its query's number of hits).
+        device=True, or indptr / out as torch GPU tensors (int64 offsets, a
+        byte buffer for the records as in query): counts, offsets and records
+        stay on the device.  The two calls' device seconds are kept in
+        self.radius_seconds."""
+        ptr, keep, mq, lay, src, flags = self._query_source(Q, keep_zero)
+
+        def count(fl, cp):
+            _check(lib.knn_index_radius_count(self._h, ptr, mq, lay, src, radius, fl, cp), "knn_index_radius_count")
+
+        def fill(fl, ip, op):
+            _check(lib.knn_index_radius(self._h, ptr, mq, lay, src, radius, fl, ip, op), "knn_index_radius")
+        res = self._radius_fill(count, fill, mq, flags, indptr, out, device)
+        del keep
+        return res
+
+    def radius_rows_count(self, ids=None, radius=0.0, keep_zero=True, out=None):
+        """knn_index_radius_rows_count: radius_count for resident rows, by id
+        (ids=None: every live row in ascending id); the row itself never
+        counts, its exact duplicates only under keep_zero."""
+        a, rows = self._id_list(ids, "knn_index_radius_rows_count")
+
+        def call(fl, cp):
+            _check(lib.knn_index_radius_rows_count(self._h, _ptr(a), rows if a is not None else 0, radius, fl, cp),
+                   "knn_index_radius_rows_count")
+        return self._radius_count(call, rows, QUERY_KEEP_ZERO if keep_zero else 0, out)
+
+    def radius_rows(self, ids=None, radius=0.0, keep_zero=True, indptr=None, out=None, device=False):
+        """knn_index_radius_rows: radius for resident rows, by id -- with
+        ids=None the corpus's epsilon-graph in CSR.  Arguments and result as
+        in radius, ids as in neighbours."""
+        a, rows = self._id_list(ids, "knn_index_radius_rows")
+        cnt = rows if a is not None else 0
+
+        def count(fl, cp):
+            _check(lib.knn_index_radius_rows_count(self._h, _ptr(a), cnt, radius, fl, cp),
+                   "knn_index_radius_rows_count")
+
+        def fill(fl, ip, op):
+            _check(lib.knn_index_radius_rows(self._h, _ptr(a), cnt, radius, fl, ip, op), "knn_index_radius_rows")
+        return self._radius_fill(count, fill, rows, QUERY_KEEP_ZERO if keep_zero else 0, indptr, out, device)
 
     @property
     def last_id(self):
