@@ -494,6 +494,58 @@ KNN_API int knn_query(const double *X, size_t m, const double *Q, size_t mq, siz
  * m + mq > INT32_MAX, and the id errors of knn_index_neighbours;
  * KNN_ERR_UNSUPPORTED: an unknown src_dtype.
  *
+ * knn_index_dbscan, knn_dbscan_graph: DBSCAN over the index's live rows (not
+ * in the reference), exact on every path.  The definition, in one place: take
+ * the m live rows at positions 0 .. m-1 in ascending id, eps a finite double
+ * >= 0 and min_pts an int >= 1.
+ *   Distance: d(x, y) = sqrt(S), S as in knn_index_radius* (the fp64 sum in j
+ *     order without FMA, over the fp32-rounded values on a KNN_F32 index); y
+ *     is a neighbour of x when d <= eps and d is finite.
+ *   Neighbourhood size N(x): the number of live rows y with d(x, y) <= eps,
+ *     x itself and its exact duplicates INCLUDED (scikit-learn's min_samples
+ *     convention; there is no zero rule to choose).  N(x) =
+ *     knn_index_radius_rows_count(ids = NULL, KNN_QUERY_KEEP_ZERO)[x] + 1.
+ *   Core row: N(x) >= min_pts.
+ *   Clusters: the connected components of the graph whose vertices are the
+ *     core rows and whose edges join two core rows with d <= eps, numbered
+ *     1 .. C in ascending order of each component's lowest position.
+ *   Border row: not core, with at least one core neighbour.  It takes the
+ *     cluster of its nearest core neighbour by (distance, id), lower id on
+ *     equal distances -- the order of every other answer of this library: the
+ *     first core row in the row's knn_index_radius_rows segment.
+ *   Noise: every other row, cluster 0 (this library's "nothing", as idx 0 and
+ *     pred 0; scikit-learn writes -1).
+ * The result is a function of the data, eps and min_pts alone: it does not
+ * depend on scheduling, block capacity, path or launch count.
+ * knn_index_dbscan: cluster (m int32, by ascending live id), neighbours
+ * (nullable, m int32: N(x)) and *nclusters (nullable, always host: C).  flags:
+ * 0 or KNN_INDEX_DEVICE_OUT (cluster and neighbours are device pointers and
+ * nothing is copied back but *nclusters).  How: two distance passes over the
+ * square of the corpus and O(m) work around them; nothing has size m * n or
+ * "number of pairs".  Each resident block, byte or element form, is the query
+ * tile of its own rows (no gather, no second copy of the corpus); the count
+ * pass gives N(x); the link pass, a third form of the two radius kernels,
+ * consumes each hit where it is found: two core rows are united in a lock-free
+ * union-find whose roots are lowest positions, a core row is offered to a row
+ * that is not core, which keeps the minimum by (distance, position); then the
+ * roots are ranked by a prefix sum and the clusters written.  Path and
+ * threshold as in knn_index_radius_rows.  knn_last_search_seconds() reports
+ * the device span, first kernel through last.  No context is made and the kept
+ * one is not touched; nothing of the index changes but buffers it owns (counted
+ * in knn_index_info's device_bytes); a failed call leaves the index answering
+ * as before and has written none of its host outputs.  KNN_ERR_INVALID, before
+ * any device call: a NULL index or cluster, min_pts < 1, an eps that is
+ * negative, NaN or infinite, unknown flag bits.
+ * knn_dbscan_graph: the same clustering on the host, without a device call,
+ * from the CSR knn_index_radius_rows(ids = NULL, KNN_QUERY_KEEP_ZERO) returns
+ * (indptr: m + 1 offsets, rec: indptr[m] - indptr[0] records, each segment by
+ * (distance, id)); ids: the m live ids ascending (NULL: 1 .. m).  N(x) =
+ * segment length + 1; a union-find over the records that join two core rows;
+ * a border row takes the first core record of its segment.  KNN_ERR_INVALID,
+ * with no output written: NULL indptr, rec (when there are records) or
+ * cluster, m == 0, min_pts < 1, an indptr that decreases, a record whose idx
+ * is no live id.
+ *
  * KNN_ERR_INVALID: NULL index, X, Q or out, zero m, mq or n, k <= 0, a bad
  * layout, unknown flag bits, m + mq > INT32_MAX; KNN_ERR_UNSUPPORTED: an
  * unknown src_dtype, dtype not KNN_F64 / KNN_F32, k above the dtype's limit
@@ -546,6 +598,14 @@ KNN_API int knn_index_radius_rows_count(knn_index_t *index, const int32_t *ids /
                                         double radius, int flags, int32_t *counts);
 KNN_API int knn_index_radius_rows(knn_index_t *index, const int32_t *ids /* nullable */, size_t count,
                                   double radius, int flags, const int64_t *indptr, knn_neighbour_t *out);
+KNN_API int knn_index_dbscan(knn_index_t *index, double eps, int min_pts, int flags,
+                             int32_t *cluster /* m, by ascending live id */,
+                             int32_t *neighbours /* nullable, m: N(x) */,
+                             int *nclusters /* nullable, always host */);
+KNN_API int knn_dbscan_graph(const int64_t *indptr, const knn_neighbour_t *rec,
+                             const int32_t *ids /* nullable: the m live ids ascending; NULL = 1..m */,
+                             size_t m, int min_pts, int32_t *cluster, int32_t *neighbours /* nullable */,
+                             int *nclusters /* nullable */);
 KNN_API int knn_index_last_id(const knn_index_t *index, size_t *last_id);
 KNN_API int knn_index_info(const knn_index_t *index, size_t *m, size_t *n, int *nblocks,
                            size_t *device_bytes, int *last_bits);

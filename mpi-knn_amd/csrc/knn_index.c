@@ -45,7 +45,9 @@
  * entries where those are doubles.  radius_count,
  * radius and their _rows forms: distance kernels of their own with CSR output
  * (knn_radius.hip) behind query's packs / neighbours' gathers into tile
- * buffers of their own, no context (radius_run).  The
+ * buffers of their own, no context (radius_run).  dbscan: the same distance
+ * kernels with the resident blocks as their own query tiles, a count and a
+ * link pass and O(m) kernels around them, no tile, no context (dbscan_run).  The
  * knn_block_* operations are in knn_blocks.c; what a failed call leaves behind
  * is swept on a CPU by tests/index_trace.
  */
@@ -125,6 +127,8 @@ struct knn_index {
     void **rtblk, **rts8;
     double *rthm;
     knn_buf_t d_rad;
+    /* knn_index_dbscan's own: its O(m) arrays and the element path's table */
+    knn_buf_t d_dbs;
 };
 
 /* a batch of mq queries: ntile tiles of tcap rows */
@@ -362,6 +366,7 @@ static void index_free(knn_index_t *ix)
     knn_buf_release(&ix->dev_bytes, &ix->d_labels);
     if (ix->rt_n) images_release(ix, ix->rtblk, ix->rts8, ix->rt_cap, 0, ix->rt_n);
     if (ix->d_rad.p) knn_buf_release(&ix->dev_bytes, &ix->d_rad);
+    if (ix->d_dbs.p) knn_buf_release(&ix->dev_bytes, &ix->d_dbs);
     free(ix->rtblk);
     free(ix->rts8);
     free(ix->rthm);
@@ -1535,6 +1540,18 @@ static int radius_reserve(knn_index_t *ix, const batch_t *bt, int s8)
     return KNN_OK;
 }
 
+/* the table of one launch: the (at most KNN_RADIUS_MAXBLK) blocks from b0 on */
+static void radius_table(const knn_index_t *ix, size_t b0, int use_s8, knn_radius_blocks_t *cb)
+{
+    memset(cb, 0, sizeof(*cb));
+    cb->nblk = (int)(ix->nblk - b0 < KNN_RADIUS_MAXBLK ? ix->nblk - b0 : KNN_RADIUS_MAXBLK);
+    for (int j = 0; j < cb->nblk; j++) {
+        cb->ptr[j] = use_s8 ? ix->b.s8[b0 + j] : ix->b.blk[b0 + j];
+        cb->base[j] = (int64_t)ix->b.cbase[b0 + j];
+        cb->nc[j] = (int)ix->b.cnc[b0 + j];
+    }
+}
+
 /* one pass (count or fill) of every tile against every block, KNN_RADIUS_MAXBLK
  * blocks a launch: d_cnt the counters / cursors, d_ip the offsets, d_self the
  * rows' own positions (rows forms), all by query */
@@ -1546,13 +1563,7 @@ static int radius_pass(const knn_index_t *ix, const batch_t *bt, int use_s8, con
         const size_t r0 = t * bt->tcap, rows = bt->mq - r0 < bt->tcap ? bt->mq - r0 : bt->tcap;
         for (size_t b0 = 0; b0 < ix->nblk; b0 += KNN_RADIUS_MAXBLK) {
             knn_radius_blocks_t cb;
-            memset(&cb, 0, sizeof(cb));
-            cb.nblk = (int)(ix->nblk - b0 < KNN_RADIUS_MAXBLK ? ix->nblk - b0 : KNN_RADIUS_MAXBLK);
-            for (int j = 0; j < cb.nblk; j++) {
-                cb.ptr[j] = use_s8 ? ix->b.s8[b0 + j] : ix->b.blk[b0 + j];
-                cb.base[j] = (int64_t)ix->b.cbase[b0 + j];
-                cb.nc[j] = (int)ix->b.cnc[b0 + j];
-            }
+            radius_table(ix, b0, use_s8, &cb);
             if (use_s8)
                 RCHK(knn_launch_radius_i8(a->fill, ix->rts8[t], knn_rows_pad(ix->rt_cap), (int)rows,
                                           d_self ? d_self + r0 : NULL, &cb, knn_rows_pad(ix->cap), (int)ix->n, thr,
@@ -1698,6 +1709,114 @@ int knn_index_radius_rows(knn_index_t *ix, const int32_t *ids, size_t count, dou
 {
     const radius_t a = {.radius = radius, .flags = flags, .fill = 1, .indptr = indptr, .out = out};
     return radius_rows(ix, ids, count, &a);
+}
+
+/* --------------------------------------------------------------- dbscan */
+
+/* DBSCAN (include/knn.h has the definition; the kernels are in knn_radius.hip).
+ * Two distance passes over the square of the corpus, each resident block the
+ * query tile of its own rows -- no gather, no tile buffer, no context -- and
+ * KNN_RADIUS_MAXBLK corpus blocks a launch: count (the radius calls' count
+ * form with the row itself and its duplicates counted: N(x)), then link, which
+ * consumes every hit where it is found; O(m) kernels in front (init) and
+ * behind (resolve).  One buffer, d_dbs, holds everything: five int32 arrays
+ * by position (nbr, parent, root, rank, cluster), the block sums of the rank's
+ * prefix sum with the number of clusters behind them, the border slots (16
+ * bytes a row) and, on the element path, the table of the largest launch's
+ * per-chunk minima.  Under KNN_INDEX_DEVICE_OUT cluster and nbr are the
+ * caller's.  Every allocation in front of the span, nothing uploaded; the host
+ * outputs arrive through a staging array, so that a failed call has written
+ * none.  The dbscan launchers are named here alone, and only
+ * knn_index_dbscan reaches this function. */
+static int dbscan_run(knn_index_t *ix, double eps, int min_pts, int dev_out, int32_t *cluster, int32_t *neighbours,
+                      int *nclusters)
+{
+    const size_t m = ix->m, nb256 = (m + 255) / 256, rp = knn_rows_pad(ix->cap);
+    const int use_s8 = s8_stays(ix, ix->cmeta);
+    const int thr = use_s8 ? (int)knn_radius_threshold(eps, knn_radius_d2max(ix->n)) : 0;
+    /* the element path's table: nq records a chunk of the largest launch.  Every
+     * block but the last is full (set_counts), so the first and the last block
+     * are the two query sizes there are, and a launch's largest block is its
+     * first.  (Both sizes: with fewer query workgroups a launch takes more
+     * chunks a block, so the smaller tile can need the larger table.) */
+    size_t tab_cap = 0;
+    for (int last = 0; last < 2 && !use_s8; last++) {
+        const size_t nq = ix->b.cnc[last ? ix->nblk - 1 : 0];
+        for (size_t b0 = 0; b0 < ix->nblk && nq; b0 += KNN_RADIUS_MAXBLK) {
+            const int nl = (int)(ix->nblk - b0 < KNN_RADIUS_MAXBLK ? ix->nblk - b0 : KNN_RADIUS_MAXBLK);
+            int rpc;
+            unsigned gy;
+            if (!ix->b.cnc[b0]) continue;
+            knn_radius_chunks((unsigned)((nq + 15) / 16), nl, (int)ix->b.cnc[b0], 64, &rpc, &gy);
+            if (nq * gy * (size_t)nl > tab_cap) tab_cap = nq * gy * (size_t)nl;
+        }
+    }
+    const size_t ints = knn_round_up(5 * m + nb256 + 1, 4);   /* (the records behind them: 16-byte aligned) */
+    /* the host outputs' staging: cluster, neighbours, the number of clusters
+     * (that alone under KNN_INDEX_DEVICE_OUT) */
+    const size_t nst = dev_out ? 1 : 2 * m + 1;
+    int32_t *stage = (int32_t *)malloc(nst * sizeof(int32_t));
+    if (!stage) return KNN_ERR_NOMEM;
+    int rc = hipSetDevice(0) == hipSuccess ? KNN_OK : KNN_ERR_HIP;
+    if (!rc) rc = own_grow(ix, &ix->d_dbs, ints * sizeof(int32_t) + (m + tab_cap) * sizeof(knn_neighbour_t));
+    int32_t *nbr = NULL, *lab = NULL, *bsum = NULL;
+    if (!rc) {
+        int32_t *own = (int32_t *)ix->d_dbs.p, *parent = own + m, *root = own + 2 * m, *rank = own + 3 * m;
+        knn_neighbour_t *border = (knn_neighbour_t *)(own + ints), *tab = border + m;
+        nbr = dev_out && neighbours ? neighbours : own;
+        lab = dev_out ? cluster : own + 4 * m;
+        bsum = own + 5 * m;
+        hipEventRecord(ix->e0, NULL);
+        rc = knn_launch_dbscan_init(nbr, parent, border, use_s8, m, NULL);
+        for (int link = 0; link < 2 && !rc; link++)
+            for (size_t bq = 0; bq < ix->nblk && !rc; bq++) {
+                const int nq = (int)ix->b.cnc[bq];
+                const int64_t qbase = (int64_t)ix->b.cbase[bq];
+                for (size_t b0 = 0; b0 < ix->nblk && nq && !rc; b0 += KNN_RADIUS_MAXBLK) {
+                    knn_radius_blocks_t cb;
+                    radius_table(ix, b0, use_s8, &cb);
+                    if (use_s8 && !link)
+                        rc = knn_launch_radius_i8(0, ix->b.s8[bq], rp, nq, NULL, &cb, rp, (int)ix->n, thr, 1,
+                                                  nbr + qbase, NULL, NULL, NULL, NULL);
+                    else if (use_s8)
+                        rc = knn_launch_dbscan_link_i8(ix->b.s8[bq], rp, nq, qbase, &cb, rp, (int)ix->n, thr, nbr,
+                                                       min_pts, parent, border, NULL);
+                    else if (!link)
+                        rc = knn_launch_radius_scan(0, ix->dtype, ix->b.blk[bq], nq, NULL, &cb, (int)ix->n, eps, 1,
+                                                    nbr + qbase, NULL, NULL, NULL, NULL);
+                    else
+                        rc = knn_launch_dbscan_link_scan(ix->dtype, ix->b.blk[bq], nq, qbase, &cb, (int)ix->n, eps,
+                                                         nbr, min_pts, parent, border, tab, tab_cap, NULL);
+                }
+            }
+        if (!rc) rc = knn_launch_dbscan_resolve(nbr, min_pts, parent, border, use_s8, m, root, rank, bsum, lab, NULL);
+        if (!rc) rc = span_end(ix);
+    }
+    if (!rc && !dev_out) rc = download(stage, lab, m * sizeof(int32_t));
+    if (!rc && !dev_out && neighbours) rc = download(stage + m, nbr, m * sizeof(int32_t));
+    if (!rc && nclusters) rc = download(stage + nst - 1, bsum + nb256, sizeof(int32_t));
+    if (rc) {
+        hipStreamSynchronize(NULL);
+    } else {
+        if (!dev_out) memcpy(cluster, stage, m * sizeof(int32_t));
+        if (!dev_out && neighbours) memcpy(neighbours, stage + m, m * sizeof(int32_t));
+        if (nclusters) *nclusters = (int)stage[nst - 1];
+    }
+    free(stage);
+    return rc;
+}
+
+int knn_index_dbscan(knn_index_t *ix, double eps, int min_pts, int flags, int32_t *cluster, int32_t *neighbours,
+                     int *nclusters)
+{
+    if (!ix || !cluster || min_pts < 1) return KNN_ERR_INVALID;
+    if (!(eps >= 0.0) || !(eps <= 1.7976931348623157e308)) return KNN_ERR_INVALID;   /* (a NaN fails both) */
+    if (flags & ~KNN_INDEX_DEVICE_OUT) return KNN_ERR_INVALID;
+    if (ix->m == 0) {   /* nothing to cluster */
+        if (nclusters) *nclusters = 0;
+        return KNN_OK;
+    }
+    return dbscan_run(ix, eps, min_pts, (flags & KNN_INDEX_DEVICE_OUT) != 0, cluster, neighbours, nclusters);
 }
 
 int knn_index_last_id(const knn_index_t *ix, size_t *last_id)

@@ -353,6 +353,31 @@ int knn_launch_radius_scan(int fill, int dtype, const void *qblk, int nq, const 
  * as it is) */
 int knn_launch_radius_sort(size_t mq, const int32_t *cursor, const int64_t *indptr, knn_neighbour_t *out,
                            const int32_t *ids, int *flag, void *stream);
+/* knn_radius.hip: knn_index_dbscan's launches (include/knn.h has the
+ * definition).  All arrays are by position, m entries.  init: nbr 0, parent[i]
+ * = i, no border winner (border: 16 bytes a row; the byte path, s8, uses 8).
+ * The count pass is knn_launch_radius_i8 / _scan with fill 0, keep0 1, no
+ * self_pos and counts = nbr + qbase.  link: the third form of the same two
+ * distance loops, the nq rows of a resident block (positions qbase ..) as the
+ * queries against the table's blocks -- two core rows (nbr >= min_pts) at
+ * distance <= eps are united in parent (lock-free, the lower position the
+ * root); a core row is offered to a query that is not core, which keeps the
+ * minimum by (distance, position) in border.  The element form passes through
+ * tab, room for tab_cap records: nq a chunk of the launch's grid
+ * (knn_radius_chunks, unit 64: gy chunks a block), folded into border by a
+ * small kernel behind the launch.  resolve: root (a core row's lowest
+ * position), rank (the roots numbered 1 .. C in ascending position, by a
+ * prefix sum through bsum: ceil(m / 256) + 1 entries, the last one C) and
+ * cluster. */
+int knn_launch_dbscan_init(int32_t *nbr, int32_t *parent, void *border, int s8, size_t m, void *stream);
+int knn_launch_dbscan_link_i8(const void *qs8, size_t q_rows_pad, int nq, int64_t qbase,
+                              const knn_radius_blocks_t *cb, size_t c_rows_pad, int n, int T, const int32_t *nbr,
+                              int min_pts, int32_t *parent, void *border, void *stream);
+int knn_launch_dbscan_link_scan(int dtype, const void *qblk, int nq, int64_t qbase, const knn_radius_blocks_t *cb,
+                                int n, double eps, const int32_t *nbr, int min_pts, int32_t *parent, void *border,
+                                void *tab, size_t tab_cap, void *stream);
+int knn_launch_dbscan_resolve(const int32_t *nbr, int min_pts, const int32_t *parent, const void *border, int s8,
+                              size_t m, int32_t *root, int32_t *rank, int32_t *bsum, int32_t *cluster, void *stream);
 /* knn_pack.hip: block elements <-> int16 wire elements (cnt % 8 == 0) */
 int knn_launch_wire(int unpack, void *dst, const void *src, int dtype, size_t cnt, void *stream);
 /* knn_engine.c: the value knn_last_search_seconds() returns (this thread) */

@@ -30,8 +30,16 @@
 // Both distance kernels take several corpus blocks in one launch through a
 // block table (knn_radius_blocks_t: grid.z the block, grid.y a chunk of its
 // rows); a block's rows past nc never hit.
+//
+// A third form of the same two loops, link, is knn_index_dbscan's second pass
+// (include/knn.h has the definition): the queries are a resident block's own
+// rows, and a hit is consumed where it is found -- two core rows are united in
+// a lock-free union-find over parent[], a core row is offered to a row that
+// is not core as its border winner -- and never written.  The O(m) kernels
+// around the two passes (k_dbscan_*) are at the end of the file.
 #include "knn_device.h"
 #include "knn_i8_dev.h"
+#include "knn_radius_plan.h"
 
 #include <type_traits>
 
@@ -55,6 +63,75 @@ __device__ __forceinline__ radius_blk radius_pick(const knn_radius_blocks_t &cb,
             o.nc = cb.nc[j];
         }
     return o;
+}
+
+// what a distance kernel does with a hit
+enum { RADIUS_COUNT = 0, RADIUS_FILL = 1, RADIUS_LINK = 2 };
+
+// The link form's own arguments.  The queries are the rows at positions
+// qbase .. of the index; nbr: every row's N(x) by position, a row is core when
+// nbr >= min_pts.  border: the byte path's slot a row, the minimum of
+// d^2 << 32 | position over the row's core neighbours (one 64-bit atomicMin is
+// the whole (distance, id) rule: d^2 is an exact non-negative int32).  tab:
+// the element path's minima, tab[chunk * nq + q] the (distance, position)
+// minimum of query q over workgroup chunk blockIdx.z * gridDim.y + blockIdx.y
+// (k_dbscan_border folds them: an (fp64, int32) key fits no atomic).
+struct radius_link {
+    const int32_t *nbr;
+    int32_t *parent;
+    unsigned long long *border;
+    knn_neighbour_t *tab;
+    int min_pts, qbase;
+};
+
+// Union-find over parent[], parent[x] <= x at all times: the only writes are a
+// compare-and-swap that hooks a root under a lower position and an atomicMin
+// that moves a row's parent to one of its ancestors.  So there are no cycles,
+// a component's root is its lowest position, and no thread waits for another:
+// a failed swap means another thread hooked that root, and the loop goes on
+// from where it now points.  Reads are device-scope atomic loads (they are not
+// served from a CU's L1, which nothing keeps coherent with another CU's
+// atomics); a value read late is still an ancestor.
+__device__ __forceinline__ int uf_load(const int32_t *parent, int x)
+{
+    return __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ int uf_find(int32_t *parent, int x)
+{
+    const int p0 = uf_load(parent, x);
+    int r = p0, p;
+    while ((p = uf_load(parent, r)) != r) r = p;
+    if (r != p0) atomicMin(&parent[x], r);   // compression: x straight under the root found
+    return r;
+}
+
+__device__ __forceinline__ void uf_union(int32_t *parent, int a, int b)
+{
+    a = uf_find(parent, a);
+    b = uf_find(parent, b);
+    while (a != b) {
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = atomicCAS(&parent[a], a, b);   // the larger root under the smaller
+        if (old == a) return;
+        a = uf_find(parent, old);
+    }
+}
+
+// a hit (query at position qpos, row at position pos, pos != qpos) of the
+// byte path's link form
+__device__ __forceinline__ void link_hit_i8(const radius_link &lk, bool qcore, int qpos, int pos, int d2)
+{
+    if (lk.nbr[pos] < lk.min_pts) return;
+    if (qcore) {
+        if (pos < qpos) uf_union(lk.parent, qpos, pos);
+    } else {
+        atomicMin(&lk.border[qpos], ((unsigned long long)(unsigned)d2 << 32) | (unsigned)pos);
+    }
 }
 
 // a hit of query q in fill mode: its slot from the cursor, written when inside
@@ -86,13 +163,13 @@ __device__ __forceinline__ void radius_emit(int32_t *cursor, const int64_t *indp
 // words (i8_norm_of; rows of more than 4 K-steps keep a zero init word, which
 // is not read), 16 consecutive words a lane (i8_norm_pos order).
 // ---------------------------------------------------------------------------
-template <bool FILL, int KC>
+template <int MODE, int KC>
 __global__ __launch_bounds__(256) void k_radius_i8(const signed char *__restrict__ qrows,
                                                    const int *__restrict__ qnorm, int q_rows_pad, int nq,
                                                    const int32_t *__restrict__ self_pos, knn_radius_blocks_t cb,
                                                    int c_rows_pad, int rs, int rows_per_chunk, int T, int keep0,
                                                    int32_t *counts, const int64_t *indptr, const int64_t *indptr0,
-                                                   knn_neighbour_t *out)
+                                                   knn_neighbour_t *out, radius_link lk)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = lane & 31, h = lane >> 5;
@@ -110,7 +187,12 @@ __global__ __launch_bounds__(256) void k_radius_i8(const signed char *__restrict
     for (int s = 0; s < KC * 4; s++)
         qf[s] = s < ks ? *(const knn_v4i *)(qrows + (size_t)qc * rs + 32 * s + 16 * h) : (knn_v4i){0, 0, 0, 0};
     const int qn = i8_norm_of(qnorm[i8_norm_pos(qc)], longrow ? 0 : qnorm[q_rows_pad + i8_norm_pos(qc)]);
-    const int self = self_pos ? self_pos[qc] : -1;
+    int self = self_pos ? self_pos[qc] : -1;
+    bool qcore = false;
+    if constexpr (MODE == RADIUS_LINK) {
+        self = lk.qbase + qc;   // the query is that row
+        qcore = lk.nbr[self] >= lk.min_pts;
+    }
     const signed char *crow = (const signed char *)blk.ptr;
     const int *cnorm = (const int *)(crow + (size_t)c_rows_pad * rs);
     int cnt = 0;
@@ -142,14 +224,16 @@ __global__ __launch_bounds__(256) void k_radius_i8(const signed char *__restrict
             const int d2 = qn + i8_norm_of(k2[reg >> 2][reg & 3], iw[reg >> 2][reg & 3]) - 2 * acc[reg];
             const int pos = (int)(blk.base + row);
             const bool hit = qv && row < blk.nc && d2 <= T && (keep0 || d2 != 0) && pos != self;
-            if constexpr (FILL) {
+            if constexpr (MODE == RADIUS_FILL) {
                 if (hit) radius_emit(counts, indptr, indptr0, out, q, sqrt((double)d2), pos);
+            } else if constexpr (MODE == RADIUS_LINK) {
+                if (hit) link_hit_i8(lk, qcore, self, pos, d2);
             } else {
                 cnt += hit ? 1 : 0;
             }
         }
     }
-    if constexpr (!FILL) {
+    if constexpr (MODE == RADIUS_COUNT) {
         cnt += __shfl_xor(cnt, 32);   // the query's other lane
         if (h == 0 && qv && cnt) atomicAdd(&counts[q], cnt);
     }
@@ -163,12 +247,12 @@ __global__ __launch_bounds__(256) void k_radius_i8(const signed char *__restrict
 // Rows are zero padded to n_pad (whole 128 bytes) in query tiles and corpus
 // blocks alike, and S + (0 - 0)^2 = S.
 // ---------------------------------------------------------------------------
-template <typename TE, bool FILL>
+template <typename TE, int MODE>
 __global__ __launch_bounds__(256) void k_radius_scan(const TE *__restrict__ qblk, int nq,
                                                      const int32_t *__restrict__ self_pos, knn_radius_blocks_t cb,
                                                      int n_pad, int rows_per_chunk, double radius, int keep0,
                                                      int32_t *counts, const int64_t *indptr, const int64_t *indptr0,
-                                                     knn_neighbour_t *out)
+                                                     knn_neighbour_t *out, radius_link lk)
 {
 #pragma clang fp contract(off)
     constexpr int QW = 4, U = 8;
@@ -185,6 +269,10 @@ __global__ __launch_bounds__(256) void k_radius_scan(const TE *__restrict__ qblk
     const TE *qp[QW];
     int self[QW], cnt[QW];
     bool done[QW];
+    // link: the query's core flag, and the lane's best core neighbour so far
+    bool qcore[QW];
+    double bd[QW];
+    int bp[QW];
 #pragma unroll
     for (int x = 0; x < QW; x++) {
         done[x] = slot0 + x >= nq;
@@ -192,6 +280,13 @@ __global__ __launch_bounds__(256) void k_radius_scan(const TE *__restrict__ qblk
         qp[x] = qblk + (size_t)q * n_pad;
         self[x] = self_pos ? self_pos[q] : -1;
         cnt[x] = 0;
+        qcore[x] = false;
+        bd[x] = KNN_INF;
+        bp[x] = -1;
+        if constexpr (MODE == RADIUS_LINK) {
+            self[x] = lk.qbase + q;   // the query is that row
+            qcore[x] = lk.nbr[self[x]] >= lk.min_pts;
+        }
     }
     for (int row = row0 + lane; row < row1; row += 64) {
         const vec_t *cr = (const vec_t *)(cblk + (size_t)row * n_pad);
@@ -218,14 +313,52 @@ __global__ __launch_bounds__(256) void k_radius_scan(const TE *__restrict__ qblk
         for (int x = 0; x < QW; x++) {
             const double d = sqrt(S[x]);
             const bool hit = !done[x] && d <= radius && d < KNN_INF && (keep0 || d != 0.0) && pos != self[x];
-            if constexpr (FILL) {
+            if constexpr (MODE == RADIUS_FILL) {
                 if (hit) radius_emit(counts, indptr, indptr0, out, slot0 + x, d, pos);
+            } else if constexpr (MODE == RADIUS_LINK) {
+                if (hit && lk.nbr[pos] >= lk.min_pts) {
+                    if (qcore[x]) {
+                        if (pos < self[x]) uf_union(lk.parent, self[x], pos);
+                    } else if (bp[x] < 0 || d < bd[x]) {   // (the lane's positions ascend)
+                        bd[x] = d;
+                        bp[x] = pos;
+                    }
+                }
             } else {
                 cnt[x] += hit ? 1 : 0;
             }
         }
     }
-    if constexpr (!FILL) {
+    if constexpr (MODE == RADIUS_LINK) {
+        // Every wave that has queries writes its record a query, idx -1 where
+        // the chunk is empty (row0 >= row1) or holds no core neighbour:
+        // k_dbscan_border reads all gridDim.y * gridDim.z chunks of a query
+        // and the table is never cleared.  This kernel must therefore keep no
+        // early return for an empty chunk (k_radius_i8 has one).
+        const size_t chunk = (size_t)blockIdx.z * gridDim.y + blockIdx.y;
+#pragma unroll
+        for (int x = 0; x < QW; x++) {
+            double d = bd[x];
+            int p = bp[x];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const double od = __shfl_xor(d, off);
+                const int op = __shfl_xor(p, off);
+                if (op >= 0 && (p < 0 || od < d || (od == d && op < p))) {
+                    d = od;
+                    p = op;
+                }
+            }
+            if (lane == 0 && !done[x]) {
+                knn_neighbour_t rec;
+                rec.distance = d;
+                rec.idx = p;
+                rec.label = 0;
+                lk.tab[chunk * (size_t)nq + slot0 + x] = rec;
+            }
+        }
+    }
+    if constexpr (MODE == RADIUS_COUNT) {
 #pragma unroll
         for (int x = 0; x < QW; x++) {
             int c = cnt[x];
@@ -303,20 +436,6 @@ __global__ __launch_bounds__(256) void k_radius_sort(const int32_t *__restrict__
     }
 }
 
-// rows of a chunk (a multiple of `unit`) and the chunks a block, so that the
-// launch has about 2048 workgroups
-void radius_chunks(unsigned gx, int nblk, int max_nc, int unit, int *rows_per_chunk, unsigned *gy)
-{
-    const long long wg = (long long)gx * nblk;
-    long long chunks = (2048 + wg - 1) / wg;
-    const long long most = (max_nc + unit - 1) / unit;
-    if (chunks > most) chunks = most;
-    if (chunks < 1) chunks = 1;
-    const long long rpc = ((max_nc + chunks - 1) / chunks + unit - 1) / unit * unit;
-    *rows_per_chunk = (int)rpc;
-    *gy = (unsigned)((max_nc + rpc - 1) / rpc);
-}
-
 int radius_blocks_ok(const knn_radius_blocks_t *cb, int *max_nc)
 {
     if (!cb || cb->nblk < 1 || cb->nblk > KNN_RADIUS_MAXBLK) return 0;
@@ -328,46 +447,49 @@ int radius_blocks_ok(const knn_radius_blocks_t *cb, int *max_nc)
     return 1;
 }
 
-template <bool FILL, int KC>
+template <int MODE, int KC>
 void launch_radius_i8(dim3 grid, hipStream_t s, const void *qs8, size_t q_rows_pad, int nq, const int32_t *self_pos,
                       const knn_radius_blocks_t *cb, size_t c_rows_pad, int rs, int rpc, int T, int keep0,
-                      int32_t *counts, const int64_t *indptr, const int64_t *indptr0, knn_neighbour_t *out)
+                      int32_t *counts, const int64_t *indptr, const int64_t *indptr0, knn_neighbour_t *out,
+                      const radius_link &lk)
 {
     const signed char *qrows = (const signed char *)qs8;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radius_i8<FILL, KC>), grid, dim3(256), 0, s, qrows,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radius_i8<MODE, KC>), grid, dim3(256), 0, s, qrows,
                        (const int *)(qrows + q_rows_pad * (size_t)rs), (int)q_rows_pad, nq, self_pos, *cb,
-                       (int)c_rows_pad, rs, rpc, T, keep0, counts, indptr, indptr0, out);
+                       (int)c_rows_pad, rs, rpc, T, keep0, counts, indptr, indptr0, out, lk);
 }
-
-}   // namespace
 
 #define RADIUS_I8_CASE(KC_)                                                                                          \
     case KC_:                                                                                                        \
-        if (fill)                                                                                                    \
-            launch_radius_i8<true, KC_>(grid, s, qs8, q_rows_pad, nq, self_pos, cb, c_rows_pad, rs, rpc, T, keep0,   \
-                                        counts, indptr, indptr0, out);                                               \
+        if (mode == RADIUS_FILL)                                                                                     \
+            launch_radius_i8<RADIUS_FILL, KC_>(grid, s, qs8, q_rows_pad, nq, self_pos, cb, c_rows_pad, rs, rpc, T,   \
+                                               keep0, counts, indptr, indptr0, out, lk);                             \
+        else if (mode == RADIUS_LINK)                                                                                \
+            launch_radius_i8<RADIUS_LINK, KC_>(grid, s, qs8, q_rows_pad, nq, self_pos, cb, c_rows_pad, rs, rpc, T,   \
+                                               keep0, counts, indptr, indptr0, out, lk);                             \
         else                                                                                                         \
-            launch_radius_i8<false, KC_>(grid, s, qs8, q_rows_pad, nq, self_pos, cb, c_rows_pad, rs, rpc, T, keep0,  \
-                                         counts, indptr, indptr0, out);                                              \
+            launch_radius_i8<RADIUS_COUNT, KC_>(grid, s, qs8, q_rows_pad, nq, self_pos, cb, c_rows_pad, rs, rpc, T,  \
+                                                keep0, counts, indptr, indptr0, out, lk);                            \
         break;
 
-extern "C" int knn_launch_radius_i8(int fill, const void *qs8, size_t q_rows_pad, int nq, const int32_t *self_pos,
-                                    const knn_radius_blocks_t *cb, size_t c_rows_pad, int n, int T, int keep0,
-                                    int32_t *counts, const int64_t *indptr, const int64_t *indptr0,
-                                    knn_neighbour_t *out, void *stream)
+// the byte path's launch in any mode (lk: the link form's arguments, which
+// stands in for counts there)
+int radius_i8(int mode, const void *qs8, size_t q_rows_pad, int nq, const int32_t *self_pos,
+              const knn_radius_blocks_t *cb, size_t c_rows_pad, int n, int T, int keep0, int32_t *counts,
+              const int64_t *indptr, const int64_t *indptr0, knn_neighbour_t *out, const radius_link &lk, void *stream)
 {
     int max_nc = 0;
-    if (!qs8 || nq <= 0 || n <= 0 || n > KNN_I8_MAX_N || !counts || !radius_blocks_ok(cb, &max_nc))
-        return KNN_ERR_INVALID;
+    if (!qs8 || nq <= 0 || n <= 0 || n > KNN_I8_MAX_N || !radius_blocks_ok(cb, &max_nc)) return KNN_ERR_INVALID;
+    if (mode == RADIUS_LINK ? !lk.nbr || !lk.parent || !lk.border || lk.qbase < 0 : !counts) return KNN_ERR_INVALID;
     if ((size_t)nq > q_rows_pad || (size_t)max_nc > c_rows_pad || T < 0) return KNN_ERR_INVALID;
-    if (fill && (!indptr || !indptr0)) return KNN_ERR_INVALID;
+    if (mode == RADIUS_FILL && (!indptr || !indptr0)) return KNN_ERR_INVALID;
     if (max_nc == 0) return KNN_OK;
     hipStream_t s = (hipStream_t)stream;
     const int rs = (int)knn_s8_rs((size_t)n);
     const unsigned gx = (unsigned)((nq + 127) / 128);
     int rpc;
     unsigned gy;
-    radius_chunks(gx, cb->nblk, max_nc, 32, &rpc, &gy);
+    knn_radius_chunks(gx, cb->nblk, max_nc, 32, &rpc, &gy);
     const dim3 grid(gx, gy, (unsigned)cb->nblk);
     switch ((rs / 32 + 3) / 4) {
         RADIUS_I8_CASE(1)
@@ -383,34 +505,246 @@ extern "C" int knn_launch_radius_i8(int fill, const void *qs8, size_t q_rows_pad
     return hip_status();
 }
 
-extern "C" int knn_launch_radius_scan(int fill, int dtype, const void *qblk, int nq, const int32_t *self_pos,
-                                      const knn_radius_blocks_t *cb, int n, double radius, int keep0,
-                                      int32_t *counts, const int64_t *indptr, const int64_t *indptr0,
-                                      knn_neighbour_t *out, void *stream)
+// the element path's launch in any mode; tab_cap: the entries lk.tab has room
+// for (link: nq a chunk, *nchunk chunks)
+int radius_scan(int mode, int dtype, const void *qblk, int nq, const int32_t *self_pos, const knn_radius_blocks_t *cb,
+                int n, double radius, int keep0, int32_t *counts, const int64_t *indptr, const int64_t *indptr0,
+                knn_neighbour_t *out, const radius_link &lk, size_t tab_cap, int *nchunk, void *stream)
 {
     int max_nc = 0;
-    if (!qblk || nq <= 0 || n <= 0 || !counts || !radius_blocks_ok(cb, &max_nc)) return KNN_ERR_INVALID;
+    if (!qblk || nq <= 0 || n <= 0 || !radius_blocks_ok(cb, &max_nc)) return KNN_ERR_INVALID;
+    if (mode == RADIUS_LINK ? !lk.nbr || !lk.parent || !lk.tab || lk.qbase < 0 : !counts) return KNN_ERR_INVALID;
     if (dtype != KNN_F64 && dtype != KNN_F32) return KNN_ERR_INVALID;
-    if (fill && (!indptr || !indptr0)) return KNN_ERR_INVALID;
+    if (mode == RADIUS_FILL && (!indptr || !indptr0)) return KNN_ERR_INVALID;
+    if (nchunk) *nchunk = 0;
     if (max_nc == 0) return KNN_OK;
     hipStream_t s = (hipStream_t)stream;
     const int n_pad = (int)knn_n_pad_dt((size_t)n, dtype);
     const unsigned gx = (unsigned)((nq + 15) / 16);
     int rpc;
     unsigned gy;
-    radius_chunks(gx, cb->nblk, max_nc, 64, &rpc, &gy);
+    knn_radius_chunks(gx, cb->nblk, max_nc, 64, &rpc, &gy);
     const dim3 grid(gx, gy, (unsigned)cb->nblk);
-#define RADIUS_SCAN(TE_, FILL_)                                                                                     \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radius_scan<TE_, FILL_>), grid, dim3(256), 0, s, (const TE_ *)qblk, nq,    \
-                       self_pos, *cb, n_pad, rpc, radius, keep0, counts, indptr, indptr0, out)
+    if (mode == RADIUS_LINK && (size_t)gy * (size_t)cb->nblk * (size_t)nq > tab_cap) return KNN_ERR_INVALID;
+    if (nchunk) *nchunk = (int)(gy * (unsigned)cb->nblk);
+#define RADIUS_SCAN(TE_, MODE_)                                                                                     \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radius_scan<TE_, MODE_>), grid, dim3(256), 0, s, (const TE_ *)qblk, nq,    \
+                       self_pos, *cb, n_pad, rpc, radius, keep0, counts, indptr, indptr0, out, lk)
     if (dtype == KNN_F64) {
-        if (fill) RADIUS_SCAN(double, true);
-        else RADIUS_SCAN(double, false);
+        if (mode == RADIUS_FILL) RADIUS_SCAN(double, RADIUS_FILL);
+        else if (mode == RADIUS_LINK) RADIUS_SCAN(double, RADIUS_LINK);
+        else RADIUS_SCAN(double, RADIUS_COUNT);
     } else {
-        if (fill) RADIUS_SCAN(float, true);
-        else RADIUS_SCAN(float, false);
+        if (mode == RADIUS_FILL) RADIUS_SCAN(float, RADIUS_FILL);
+        else if (mode == RADIUS_LINK) RADIUS_SCAN(float, RADIUS_LINK);
+        else RADIUS_SCAN(float, RADIUS_COUNT);
     }
 #undef RADIUS_SCAN
+    return hip_status();
+}
+
+// ---------------------------------------------------------------------------
+// knn_index_dbscan's O(m) kernels, one thread a row (position).
+// ---------------------------------------------------------------------------
+
+// the exclusive prefix of v over the workgroup's 256 threads; *sum: the total
+__device__ __forceinline__ int block_scan_excl(int v, int *sum)
+{
+    __shared__ int ws[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int t = __shfl_up(inc, off);
+        if (lane >= off) inc += t;
+    }
+    if (lane == 63) ws[wave] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        if (w < wave) base += ws[w];
+        tot += ws[w];
+    }
+    __syncthreads();   // ws is free for the next call
+    *sum = tot;
+    return base + inc - v;
+}
+
+// every row its own root, no border winner yet, no neighbour counted
+__global__ __launch_bounds__(256) void k_dbscan_init(int32_t *nbr, int32_t *parent, void *border, int s8, int m)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    nbr[i] = 0;
+    parent[i] = i;
+    if (s8) {
+        ((unsigned long long *)border)[i] = ~0ULL;
+    } else {
+        knn_neighbour_t none;
+        none.distance = KNN_INF;
+        none.idx = -1;
+        none.label = 0;
+        ((knn_neighbour_t *)border)[i] = none;
+    }
+}
+
+// element path, behind each link launch: the launch's per-chunk minima of query
+// q folded into the row's slot by (distance, position)
+__global__ __launch_bounds__(256) void k_dbscan_border(const knn_neighbour_t *__restrict__ tab, int nq, int nchunk,
+                                                       knn_neighbour_t *border, int qbase)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= nq) return;
+    knn_neighbour_t best = border[qbase + q];
+    for (int c = 0; c < nchunk; c++) {
+        const knn_neighbour_t t = tab[(size_t)c * nq + q];
+        if (t.idx >= 0 && (best.idx < 0 || t.distance < best.distance ||
+                           (t.distance == best.distance && t.idx < best.idx)))
+            best = t;
+    }
+    border[qbase + q] = best;
+}
+
+// root[i]: a core row's component, its lowest position (parent is only read
+// here); -1 for the others.  bsum[workgroup]: its rows that are their own root.
+__global__ __launch_bounds__(256) void k_dbscan_roots(const int32_t *__restrict__ parent,
+                                                      const int32_t *__restrict__ nbr, int min_pts, int m,
+                                                      int32_t *root, int32_t *bsum)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int r = -1;
+    if (i < m && nbr[i] >= min_pts) {
+        r = i;
+        int p;
+        while ((p = parent[r]) != r) r = p;
+    }
+    if (i < m) root[i] = r;
+    int tot;
+    block_scan_excl(i < m && r == i, &tot);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+
+// bsum -> its exclusive prefix, in place; bsum[nb]: the total, the number of
+// clusters.  One workgroup.
+__global__ __launch_bounds__(256) void k_dbscan_scan(int32_t *bsum, int nb)
+{
+    int carry = 0;
+    for (int b0 = 0; b0 < nb; b0 += 256) {   // (workgroup-uniform)
+        const int b = b0 + threadIdx.x;
+        const int v = b < nb ? bsum[b] : 0;
+        int tot;
+        const int ex = block_scan_excl(v, &tot);
+        if (b < nb) bsum[b] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) bsum[nb] = carry;
+}
+
+// rank[i]: a root's cluster number, 1 .. C in ascending position
+__global__ __launch_bounds__(256) void k_dbscan_rank(const int32_t *__restrict__ root,
+                                                     const int32_t *__restrict__ bsum, int m, int32_t *rank)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int is_root = i < m && root[i] == i;
+    int tot;
+    const int ex = block_scan_excl(is_root, &tot);
+    if (i < m) rank[i] = is_root ? bsum[blockIdx.x] + ex + 1 : 0;
+}
+
+// cluster[i]: a core row's root's rank; a border row's winner's root's rank; 0
+__global__ __launch_bounds__(256) void k_dbscan_label(const int32_t *__restrict__ root,
+                                                      const int32_t *__restrict__ rank, const void *border, int s8,
+                                                      int m, int32_t *cluster)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    int at = root[i];
+    if (at < 0) {
+        int win;
+        if (s8) {
+            const unsigned long long key = ((const unsigned long long *)border)[i];
+            win = key == ~0ULL ? -1 : (int)(unsigned)(key & 0xffffffffULL);
+        } else {
+            win = ((const knn_neighbour_t *)border)[i].idx;
+        }
+        at = win >= 0 ? root[win] : -1;
+    }
+    cluster[i] = at >= 0 ? rank[at] : 0;
+}
+
+}   // namespace
+
+extern "C" int knn_launch_radius_i8(int fill, const void *qs8, size_t q_rows_pad, int nq, const int32_t *self_pos,
+                                    const knn_radius_blocks_t *cb, size_t c_rows_pad, int n, int T, int keep0,
+                                    int32_t *counts, const int64_t *indptr, const int64_t *indptr0,
+                                    knn_neighbour_t *out, void *stream)
+{
+    const radius_link none = {};
+    return radius_i8(fill ? RADIUS_FILL : RADIUS_COUNT, qs8, q_rows_pad, nq, self_pos, cb, c_rows_pad, n, T, keep0,
+                     counts, indptr, indptr0, out, none, stream);
+}
+
+extern "C" int knn_launch_radius_scan(int fill, int dtype, const void *qblk, int nq, const int32_t *self_pos,
+                                      const knn_radius_blocks_t *cb, int n, double radius, int keep0,
+                                      int32_t *counts, const int64_t *indptr, const int64_t *indptr0,
+                                      knn_neighbour_t *out, void *stream)
+{
+    const radius_link none = {};
+    return radius_scan(fill ? RADIUS_FILL : RADIUS_COUNT, dtype, qblk, nq, self_pos, cb, n, radius, keep0, counts,
+                       indptr, indptr0, out, none, 0, NULL, stream);
+}
+
+// ---- knn_index_dbscan's launchers (knn_internal.h) --------------------------
+
+extern "C" int knn_launch_dbscan_init(int32_t *nbr, int32_t *parent, void *border, int s8, size_t m, void *stream)
+{
+    if (!nbr || !parent || !border || m == 0 || m > 0x7fffffffULL) return KNN_ERR_INVALID;
+    hipLaunchKernelGGL(k_dbscan_init, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nbr, parent,
+                       border, s8, (int)m);
+    return hip_status();
+}
+
+extern "C" int knn_launch_dbscan_link_i8(const void *qs8, size_t q_rows_pad, int nq, int64_t qbase,
+                                         const knn_radius_blocks_t *cb, size_t c_rows_pad, int n, int T,
+                                         const int32_t *nbr, int min_pts, int32_t *parent, void *border, void *stream)
+{
+    if (qbase < 0 || qbase > 0x7fffffffLL) return KNN_ERR_INVALID;
+    const radius_link lk = {nbr, parent, (unsigned long long *)border, NULL, min_pts, (int)qbase};
+    return radius_i8(RADIUS_LINK, qs8, q_rows_pad, nq, NULL, cb, c_rows_pad, n, T, 1, NULL, NULL, NULL, NULL, lk,
+                     stream);
+}
+
+extern "C" int knn_launch_dbscan_link_scan(int dtype, const void *qblk, int nq, int64_t qbase,
+                                           const knn_radius_blocks_t *cb, int n, double eps, const int32_t *nbr,
+                                           int min_pts, int32_t *parent, void *border, void *tab, size_t tab_cap,
+                                           void *stream)
+{
+    if (qbase < 0 || qbase > 0x7fffffffLL || !border) return KNN_ERR_INVALID;
+    const radius_link lk = {nbr, parent, NULL, (knn_neighbour_t *)tab, min_pts, (int)qbase};
+    int nchunk = 0;
+    const int rc = radius_scan(RADIUS_LINK, dtype, qblk, nq, NULL, cb, n, eps, 1, NULL, NULL, NULL, NULL, lk, tab_cap,
+                               &nchunk, stream);
+    if (rc || !nchunk) return rc;
+    hipLaunchKernelGGL(k_dbscan_border, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const knn_neighbour_t *)tab, nq, nchunk, (knn_neighbour_t *)border, (int)qbase);
+    return hip_status();
+}
+
+extern "C" int knn_launch_dbscan_resolve(const int32_t *nbr, int min_pts, const int32_t *parent, const void *border,
+                                         int s8, size_t m, int32_t *root, int32_t *rank, int32_t *bsum,
+                                         int32_t *cluster, void *stream)
+{
+    if (!nbr || !parent || !border || !root || !rank || !bsum || !cluster || m == 0 || m > 0x7fffffffULL)
+        return KNN_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned nb = (unsigned)((m + 255) / 256);
+    hipLaunchKernelGGL(k_dbscan_roots, dim3(nb), dim3(256), 0, s, parent, nbr, min_pts, (int)m, root, bsum);
+    hipLaunchKernelGGL(k_dbscan_scan, dim3(1), dim3(256), 0, s, bsum, (int)nb);
+    hipLaunchKernelGGL(k_dbscan_rank, dim3(nb), dim3(256), 0, s, (const int32_t *)root, (const int32_t *)bsum, (int)m,
+                       rank);
+    hipLaunchKernelGGL(k_dbscan_label, dim3(nb), dim3(256), 0, s, (const int32_t *)root, (const int32_t *)rank, border,
+                       s8, (int)m, cluster);
     return hip_status();
 }
 

@@ -31,4 +31,21 @@ static inline int64_t knn_radius_threshold(double r, int64_t d2max)
     return t;
 }
 
+/* The grid of a distance launch (knn_radius.hip): gx workgroups of queries
+ * against nblk blocks of at most max_nc rows.  Rows of a chunk (a multiple of
+ * `unit`) and the chunks a block, so that the launch has about 2048
+ * workgroups.  On the host as well: knn_index_dbscan sizes its table of
+ * per-chunk minima from *gy before the launch. */
+static inline void knn_radius_chunks(unsigned gx, int nblk, int max_nc, int unit, int *rows_per_chunk, unsigned *gy)
+{
+    const long long wg = (long long)gx * nblk;
+    long long chunks = (2048 + wg - 1) / wg;
+    const long long most = (max_nc + unit - 1) / unit;
+    if (chunks > most) chunks = most;
+    if (chunks < 1) chunks = 1;
+    const long long rpc = ((max_nc + chunks - 1) / chunks + unit - 1) / unit * unit;
+    *rows_per_chunk = (int)rpc;
+    *gy = (unsigned)((max_nc + rpc - 1) / rpc);
+}
+
 #endif

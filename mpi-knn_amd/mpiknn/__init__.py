@@ -61,6 +61,7 @@ API_SYMBOLS = (
     "knn_classify_weighted", "knn_regress", "knn_index_classify_weighted", "knn_index_classify_weighted_rows",
     "knn_index_regress", "knn_index_regress_rows",
     "knn_index_radius_count", "knn_index_radius", "knn_index_radius_rows_count", "knn_index_radius_rows",
+    "knn_index_dbscan", "knn_dbscan_graph",
 )
 DTYPES = {"f64": F64, "f32": F32, F64: F64, F32: F32}
 # a pack / index SOURCE may also be unsigned bytes (KNN_U8: never a block or search dtype)
@@ -180,6 +181,8 @@ def _load():
         "knn_index_radius": ([p, p, sz, i, i, d, i, p, p], i),
         "knn_index_radius_rows_count": ([p, p, sz, d, i, p], i),
         "knn_index_radius_rows": ([p, p, sz, d, i, p, p], i),
+        "knn_index_dbscan": ([p, d, i, i, p, p, p], i),
+        "knn_dbscan_graph": ([p, p, p, sz, i, p, p, p], i),
         "knn_block_gather_pos_dt": ([p, sz, sz, p, sz, sz, p, sz, sz, i, p], i),
         "knn_block_gather_pos_s8": ([p, sz, sz, p, sz, sz, p, sz, sz, p], i),
     }
@@ -207,6 +210,27 @@ def _ptr(a):
 
 
 # ---------------------------------------------------------------- host API
+
+def dbscan_graph(indptr, records, min_pts, ids=None):
+    """knn_dbscan_graph: Index.dbscan's clustering on the host, from the CSR
+    Index.radius_rows(None, eps, keep_zero=True) returns (ids: the live ids
+    ascending after removals; None: 1 .. m).  Returns DbscanResult(cluster,
+    neighbours, nclusters, None)."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    records = np.ascontiguousarray(records, dtype=NB_DTYPE)
+    if indptr.ndim != 1 or len(indptr) < 2:
+        raise ValueError("indptr must have m + 1 >= 2 entries, got shape %r" % (indptr.shape,))
+    m = len(indptr) - 1
+    a = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32)
+    if a is not None and a.shape != (m,):
+        raise ValueError("ids must have %d entries, got %r" % (m, a.shape))
+    cl = np.zeros(m, dtype=np.int32)
+    nb = np.zeros(m, dtype=np.int32)
+    nc = ctypes.c_int(0)
+    _check(lib.knn_dbscan_graph(_ptr(indptr), _ptr(records) if len(records) else None, _ptr(a), m, min_pts,
+                                _ptr(cl), _ptr(nb), ctypes.byref(nc)), "knn_dbscan_graph")
+    return DbscanResult(cl, nb, nc.value, None)
+
 
 def load_mat(path, xvar="train_X", lvar="train_labels"):
     """knn_load_mat (replaces matOpen/matGetVariable/mxGetPr, serial:40-52).
@@ -521,6 +545,7 @@ IndexInfo = collections.namedtuple("IndexInfo", "m n nblocks device_bytes last_b
 ClassifyResult = collections.namedtuple("ClassifyResult", "pred matches counts neighbours seconds")
 WeightedResult = collections.namedtuple("WeightedResult", "pred matches sums neighbours seconds")
 RegressResult = collections.namedtuple("RegressResult", "pred neighbours seconds")
+DbscanResult = collections.namedtuple("DbscanResult", "cluster neighbours nclusters seconds")
 _NP_SRC = {np.dtype(np.uint8): U8, np.dtype(np.float32): F32, np.dtype(np.float64): F64}
 
 
@@ -1033,6 +1058,39 @@ class Index:
         def fill(fl, ip, op):
             _check(lib.knn_index_radius_rows(self._h, _ptr(a), cnt, radius, fl, ip, op), "knn_index_radius_rows")
         return self._radius_fill(count, fill, rows, QUERY_KEEP_ZERO if keep_zero else 0, indptr, out, device)
+
+    def dbscan(self, eps, min_pts=5, neighbours=False, device=False):
+        """knn_index_dbscan: DBSCAN over the live rows, on the device, without
+        the epsilon-graph (include/knn.h has the definition).  A row is core
+        when at least min_pts live rows -- itself and its exact duplicates
+        included, scikit-learn's min_samples convention -- lie within eps of
+        it; clusters are the connected components of the core rows, numbered
+        1 .. nclusters in ascending order of their lowest id; a border row takes
+        the cluster of its nearest core neighbour by (distance, id); noise is
+        cluster 0 (scikit-learn writes -1 there).  Returns DbscanResult(cluster,
+        neighbours, nclusters, seconds): cluster an int32 array by ascending
+        live id, neighbours (on request) every row's neighbourhood size, both
+        torch GPU tensors with device=True."""
+        if not self._h:
+            raise ValueError("the index is closed")
+        m = self.info().m
+        nc = ctypes.c_int(0)
+        if device:
+            import torch
+            cl = torch.zeros(max(m, 1), dtype=torch.int32, device="cuda:0")
+            nb = torch.zeros(max(m, 1), dtype=torch.int32, device="cuda:0") if neighbours else None
+            _check(lib.knn_index_dbscan(self._h, eps, min_pts, INDEX_DEVICE_OUT, ctypes.c_void_p(cl.data_ptr()),
+                                        ctypes.c_void_p(nb.data_ptr()) if neighbours else None, ctypes.byref(nc)),
+                   "knn_index_dbscan")
+            cl, nb = cl[:m], nb[:m] if neighbours else None
+        else:
+            # (one entry more than asked for: a zero-size array has no address to pass)
+            cl = np.zeros(m + 1, dtype=np.int32)
+            nb = np.zeros(m + 1, dtype=np.int32) if neighbours else None
+            _check(lib.knn_index_dbscan(self._h, eps, min_pts, 0, _ptr(cl), _ptr(nb), ctypes.byref(nc)),
+                   "knn_index_dbscan")
+            cl, nb = cl[:m], nb[:m] if neighbours else None
+        return DbscanResult(cl, nb, nc.value, lib.knn_last_search_seconds())
 
     @property
     def last_id(self):
